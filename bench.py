@@ -22,6 +22,12 @@ divided by the average duration of the dominant kernel (k_integrate) measured wi
 the stream it runs on.  cpu_baseline times the REFERENCE's own code (oracle/_ref, built from
 /root/reference/Integrate/*.cpp unmodified, 8 OpenMP threads as hard-coded there) on a bounded
 sample of the same frames; when that build is absent it falls back to the oracle port and says so.
+
+A plain run (no --full) does only what the headline needs: set-up, --warmup W steps (and, when W < K, one untimed pass of
+the K steps), ONE timed pass of exactly K steps (no HIP events in it), --dump-outputs if given, the result line.  --full adds everything else described above and in the
+options -- repeated passes up to --min-seconds, the per-kernel roofline figures, the k_integrate-alone and streamed passes,
+the CPU baseline with its parity check, the ICP / FragmentOptimizer legs, the boundary leg, the child runs of configs 4 / 5
+and, with N > 1, configs[3]'s strong-scaling leg.
 """
 import argparse
 import ctypes
@@ -141,15 +147,16 @@ def compact_line(out):
                                                    "ring_equivalent_bytes") if k in ms}
         c["config"]["merge_result"] = (cfg.get("merge_result") or "").split(" ")[0]
     kint = _get(rf, "kernels", "k_integrate") or {}
-    c["roofline"] = {"bound": rf.get("bound"), "kernel": rf.get("kernel"), "frac": rf.get("frac"), "achieved": rf.get("achieved"),
-                     "peak": rf.get("peak"), "unit": rf.get("unit"), "algorithmic_bytes_per_pass": rf.get("algorithmic_bytes_per_pass"),
-                     "kernel_frac": rf.get("kernel_frac"), "kernel_frac_rocprof": rf.get("kernel_frac_rocprof"),
-                     "kernel_achieved": kint.get("achieved"), "kernel_bytes_per_launch": kint.get("algorithmic_bytes_per_launch"),
-                     "avg_launch_ms": rf.get("avg_launch_ms"), "launches": rf.get("launches"),
-                     "kernel_alone_frac": _get(rf, "kernel_alone", "frac"), "kernel_alone_ms": _get(rf, "kernel_alone", "avg_launch_ms"),
-                     "traffic": rf.get("traffic"), "hbm_physical_frac": rf.get("hbm_physical_frac"),
-                     "valu_issue_frac": _get(rf, "valu_issue", "frac"), "valu_job_frac": _get(rf, "valu_issue", "job_frac"),
-                     "static_stale": _get(rf, "static_figures", "stale")}
+    if rf:
+        c["roofline"] = {"bound": rf.get("bound"), "kernel": rf.get("kernel"), "frac": rf.get("frac"), "achieved": rf.get("achieved"),
+                         "peak": rf.get("peak"), "unit": rf.get("unit"), "algorithmic_bytes_per_pass": rf.get("algorithmic_bytes_per_pass"),
+                         "kernel_frac": rf.get("kernel_frac"), "kernel_frac_rocprof": rf.get("kernel_frac_rocprof"),
+                         "kernel_achieved": kint.get("achieved"), "kernel_bytes_per_launch": kint.get("algorithmic_bytes_per_launch"),
+                         "avg_launch_ms": rf.get("avg_launch_ms"), "launches": rf.get("launches"),
+                         "kernel_alone_frac": _get(rf, "kernel_alone", "frac"), "kernel_alone_ms": _get(rf, "kernel_alone", "avg_launch_ms"),
+                         "traffic": rf.get("traffic"), "hbm_physical_frac": rf.get("hbm_physical_frac"),
+                         "valu_issue_frac": _get(rf, "valu_issue", "frac"), "valu_job_frac": _get(rf, "valu_issue", "job_frac"),
+                         "static_stale": _get(rf, "static_figures", "stale")}
     cb = out.get("cpu_baseline")
     if cb:
         c["cpu_baseline"] = {"value": cb.get("value"), "unit": cb.get("unit"), "cores": cb.get("cores"), "kind": cb.get("kind"),
@@ -260,6 +267,31 @@ def emit(out, full_path):
 
 
 
+def dump_outputs(vol, path, sample_units=16, seed=0):
+    """--dump-outputs: what a caller of the timed path receives -- the volume after the last timed step -- as .npy files, 33 MB at most:
+    unit_keys (sorted), unit_weight_sum and unit_sdf_weight_sum (float64 sums over each unit's voxels) for EVERY unit, and the whole
+    sdf_ / weight_ planes of a seeded sample of `sample_units` of them (sample_keys, sample_sdf, sample_weight: float32)."""
+    import numpy as np
+    from elasticreconstruction_amd.tsdf import UNIT_VOX
+    os.makedirs(path, exist_ok=True)
+    vol.synchronize()
+    keys = np.sort(vol.unit_keys())
+    pick = np.sort(np.random.default_rng(seed).choice(len(keys), min(sample_units, len(keys)), replace=False))
+    w_sum, sw_sum = np.zeros(len(keys)), np.zeros(len(keys))
+    s_sdf, s_w = np.zeros((len(pick), UNIT_VOX), np.float32), np.zeros((len(pick), UNIT_VOX), np.float32)
+    slot = {int(u): n for n, u in enumerate(pick)}
+    for u, k in enumerate(keys):
+        sdf, w = vol.read_unit(k)
+        w64 = w.astype(np.float64)
+        w_sum[u], sw_sum[u] = w64.sum(), (sdf.astype(np.float64) * w64).sum()
+        if u in slot:
+            s_sdf[slot[u]], s_w[slot[u]] = sdf, w
+    arrays = {"unit_keys": keys.astype(np.float64), "unit_weight_sum": w_sum, "unit_sdf_weight_sum": sw_sum,
+              "sample_keys": keys[pick].astype(np.float64), "sample_sdf": s_sdf, "sample_weight": s_w}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def strong_scaling_leg(args, dist, dev, local, rank, world, comm, dry, stream):
     """BASELINE.json configs[3] INSIDE an N > 1 run: the 10 000-frame job of the drifting path cut into `world` contiguous blocks,
     every rank its block into a private volume, the merge (by unit owner; result distributed) inside the timed region -- the strong-scaling line of
@@ -338,8 +370,8 @@ def main():
                     help="frames handed to the hot path per step (one er_tsdf_integrate_frames call); 0 = as many whole fragments "
                          "as it takes for --steps steps to cover all %d frames of configs[1] (150 at the default 20 steps)" % CONFIG2_FRAMES)
     ap.add_argument("--min-seconds", type=float, default=2.5,
-                    help="repeat the K-step pass on an emptied volume until the passes add up to this much timed work (>= 2 s, so that a "
-                         "utilisation sampler sees the GPU leg of the run)")
+                    help="(--full only; a plain run times ONE pass of K steps) repeat the K-step pass on an emptied volume until the passes "
+                         "add up to this much timed work (>= 2 s, so that a utilisation sampler sees the GPU leg of the run)")
     ap.add_argument("--max-passes", type=int, default=400)
     ap.add_argument("--no-warp", action="store_true", help="rigid --ref_traj style run (no control grid)")
     ap.add_argument("--cpu-sample", type=int, default=200, help="frames timed on the CPU reference (0 = skip)")
@@ -375,10 +407,25 @@ def main():
     ap.add_argument("--scaling-child", type=int, default=1,
                     help="(--gpus N > 1, --config 2) after the weak-scaling headline also run configs[3]'s 10 000-frame job cut into N blocks over the same "
                          "communicator and attach it as other_configs['configs[3]'] (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: repeated passes up to --min-seconds, HIP events on every "
+                         "--event-stride-th launch and the roofline figures, the k_integrate-alone and streamed passes, --cpu-sample, "
+                         "--icp-pairs (with the FragmentOptimizer leg), --boundary, --other-configs, --scaling-child and configs[4]'s "
+                         "all-pairs leg.  Without it all of these are off whatever their own options say")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed (the volume after the last timed step: every unit's key and "
+                         "float64 sums of its weight_ and sdf_ x weight_, the full planes of a seeded sample of units) as DIR/<name>.npy; "
+                         "rank 0's volume when N > 1")
     ap.add_argument("--full-json", default=os.path.join(ROOT, "bench_full.json"),
                     help="where rank 0 writes the FULL result object (per-phase tables, definitions, A/B leftovers, the children's objects); "
                          "stdout carries only the compact line (< 4 KB) made from it by compact_line()")
     args = ap.parse_args()
+    if not args.full:                                      # a plain run: set-up, warm-up, ONE pass of exactly K timed steps, the line
+        args.min_seconds, args.max_passes, args.event_stride = 0.0, 1, 0
+        args.no_alone = args.no_streamed = True
+        args.cpu_sample = args.icp_pairs = args.other_configs = args.boundary = args.scaling_child = 0
+    if args.dump_outputs and args.dry_run:
+        raise SystemExit("--dump-outputs: a dry run computes nothing")
     global _quiet
     _quiet = QuietStdout()
 
@@ -492,6 +539,11 @@ def main():
     vol.set_stream(stream.cuda_stream if stream is not None else None)
     # ---- warm-up (the volume is emptied afterwards) --------------------------------------------
     run_steps(vol, min(W, K), depth_host)
+    if not args.full and W < K:
+        # the first pass over the K steps pays one-time host work per step (about 1.8x a later pass at K = 20); a --full run's median pass
+        # never contains it, so a plain run, which times ONE pass, first runs the K steps once untimed
+        vol.reset()
+        run_steps(vol, K, depth_host)
     if use_dist:
         merge(vol)                # also warms RCCL (communicator set-up, allocator) outside the timed region
     vol.synchronize()
@@ -531,6 +583,8 @@ def main():
             break
     prof = vol.get_profile()
     vol.set_profiling(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(vol, args.dump_outputs)
     # k_integrate WITHOUT the overlap: one more (untimed) pass, one 50-frame launch at a time with a synchronise after each,
     # so the kernel runs alone on the chip.  In the timed passes it shares the SIMDs with the pre-passes of the next two
     # batches, which is faster for the job and slower for the kernel; both durations are reported.
@@ -583,7 +637,7 @@ def main():
         arena.close()
 
     icp = None
-    if dry and (args.config == 5 or (args.icp_pairs > 0 and args.config == 2)):
+    if dry and ((args.config == 5 and args.full) or (args.icp_pairs > 0 and args.config == 2)):
         # the stand-in carries exactly the keys the gating below reads and rewrites
         icp = {"dry_run": True, "pairs_per_s": 1.0, "pairs": args.icp_pairs, "pairs_total": 4950, "nn_queries_per_s": 1.0, "_pass_s": 1.0 + 0.01 * rank}
     if dry and icp is not None:
@@ -597,7 +651,7 @@ def main():
         elif use_dist:
             icp.update({"pairs_per_s": world * args.icp_pairs / icp_pass_s, "pairs": world * args.icp_pairs, "nn_queries_per_s": None,
                         "sharding": "%d GPUs x %d pairs, no collective; slowest rank's median pass" % (world, args.icp_pairs)})
-    elif args.config == 5:
+    elif args.config == 5 and args.full:
         icp = allpairs_section(100, local, rank, world, with_cpu=(rank == 0))
         ap_s = icp.pop("_pass_s")
         if use_dist:
@@ -673,7 +727,7 @@ def main():
         per_step = -(-S // 64)                                     # er_tsdf_integrate_frames: ceil(S / 64) launches of equal size per step
         launches = n_pass * K * per_step
         frames_per_launch = S / float(per_step)
-        if prof["integrate_ms"] > 0:
+        if args.full and prof["integrate_ms"] > 0:
             bytes_pass = 16.0 * sum_w + FRAME_BYTES_FIXED * n_frames + (2 * FRAME_BYTES_RAW * n_frames if warp_on else 0)
             per_launch = bytes_pass * n_pass / launches
             ach = per_launch / (ms_launch * 1e-3) / 1e9
@@ -779,7 +833,7 @@ def main():
                             "k_integrate alone on the chip, priced with 16 x (voxel updates per launch) only.  kernel_frac above is the same "
                             "figure inside the TIMED region, where the kernel shares the SIMDs with the pre-pass kernels of the next two "
                             "batches (three-stream pipeline)"}
-        else:
+        elif args.full:
             out["roofline"] = {"bound": "hbm", "contract_bound": "hbm", "kernel": "k_integrate", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                "frac": None, "traffic": None, "avg_launch_ms": ms_launch, "launches": launches}
         if streamed is not None:

@@ -693,7 +693,7 @@ def other_configs(device):
     its error text here and never touches the headline line."""
     import subprocess
     import time
-    res = {"what": "python bench.py --config 4 | 5 --min-seconds 0.2 --cpu-sample 100, run after the headline measurement in child "
+    res = {"what": "python bench.py --config 4 | 5 --full --min-seconds 0.2 --cpu-sample 100, run after the headline measurement in child "
                    "processes; one GPU: configs[3] forces the frame-split merge (er_tsdf_allreduce on a 1-rank communicator); "
                    "parity_checked = 100 frames sampled across the job (first fragment to last, true frame ids and lattices) against "
                    "the reference's own CIntegrateApp::Execute, bit for bit"}
@@ -704,7 +704,7 @@ def other_configs(device):
         t0 = time.time()
         full = os.path.join(tempfile.gettempdir(), "bench_child_%d_%d.json" % (os.getpid(), cfg))
         try:
-            p = subprocess.run([sys.executable, BENCH_PY, "--config", str(cfg), "--min-seconds", "0.2", "--cpu-sample", "100",
+            p = subprocess.run([sys.executable, BENCH_PY, "--config", str(cfg), "--full", "--min-seconds", "0.2", "--cpu-sample", "100",
                                 "--no-alone", "--no-streamed", "--other-configs", "0", "--full-json", full], env=env, stdout=subprocess.PIPE,
                                stderr=subprocess.PIPE, timeout=240)
             if p.returncode != 0 or not os.path.exists(full):

@@ -19,11 +19,12 @@ echo "# HEAD $HEAD_ID" > gpurun_out/smoke_$TAG.log
 timeout 120 python -c "import __graft_entry__ as g; g.smoke()" >> gpurun_out/smoke_$TAG.log 2>&1; SRC=$?; echo "smoke exit $SRC" >> gpurun_out/smoke_$TAG.log; tail -2 gpurun_out/smoke_$TAG.log
 echo "== t=${SECONDS}s bench"
 BT=$((LIMIT - SECONDS - 5)); [ $BT -gt 300 ] && BT=300; [ $BT -lt 20 ] && BT=20
-if [ "${GATE_BENCH:-1}" = "1" ]; then timeout $BT python bench.py --full-json gpurun_out/bench_full_$TAG.json > gpurun_out/bench_default_$TAG.json 2> gpurun_out/bench_default_$TAG.err; BRC=$?; else BRC=0; fi
-python - "$TAG" "$HEAD_ID" <<'PY'
-import json, sys
+D="$(dirname "$LOG")"                              # the bench files go next to the pytest log
+if [ "${GATE_BENCH:-1}" = "1" ]; then timeout $BT python bench.py --full --full-json "$D/bench_full_$TAG.json" > "$D/bench_default_$TAG.json" 2> "$D/bench_default_$TAG.err"; BRC=$?; else BRC=0; fi
+python - "$TAG" "$HEAD_ID" "$D" <<'PY'
+import json, os, sys
 tag, head = sys.argv[1], sys.argv[2]
-p = "gpurun_out/bench_default_%s.json" % tag
+p = os.path.join(sys.argv[3], "bench_default_%s.json" % tag)
 try:
     lines = [l for l in open(p).read().splitlines() if l.strip()]
     d = json.loads(lines[-1])                                  # the LAST stdout line is the compact line (< 4 KB) the driver parses

@@ -20,6 +20,22 @@ def golden():
         return json.load(f)
 
 
+def reference_example_data(dest):
+    """The reference's Matlab example data files the format tests read (Matlab_Toolbox/Example/Data: Trajectory/traj_gt.log and four files of
+    RegistrationEvaluation/livingroom1), committed gzipped under tests/golden/reference_data: unpacked into `dest` with the same layout."""
+    import gzip
+    import shutil
+    src = os.path.join(GOLD, "reference_data")
+    for d, _, files in os.walk(src):
+        for f in files:
+            if f.endswith(".gz"):
+                out = os.path.join(str(dest), os.path.relpath(os.path.join(d, f[:-3]), src))
+                os.makedirs(os.path.dirname(out), exist_ok=True)
+                with gzip.open(os.path.join(d, f), "rb") as fi, open(out, "wb") as fo:
+                    shutil.copyfileobj(fi, fo)
+    return str(dest)
+
+
 def golden_rigid():
     """(poses [6,4,4], depth uint16 [6, 307200]) of tests/golden, depth digest verified."""
     z = np.load(os.path.join(GOLD, "tsdf_inputs.npz"))

@@ -210,7 +210,7 @@ def json_line(stdout):
     return json.loads(lines[0])
 
 
-def _bench_dry_run(nproc, extra, timeout=420):
+def _bench_dry_run(nproc, extra, timeout=420, full_run=True):
     """`python -m torch.distributed.run ... bench.py --gpus N ... --dry-run` exactly as the driver launches the real thing (README /
     the task contract), on CPU: returns the parsed JSON line of rank 0."""
     import json
@@ -222,12 +222,13 @@ def _bench_dry_run(nproc, extra, timeout=420):
     import tempfile
     full = os.path.join(tempfile.mkdtemp(prefix="er_bench_dry_"), "bench_full.json")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--dry-run", "--full-json", full] + extra
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--dry-run"] + (["--full"] if full_run else []) + ["--full-json", full] + extra
     env = dict(os.environ, OMP_NUM_THREADS="1", ER_ORACLE_QUIET="1")
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=timeout, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     compact = json_line(r.stdout)
-    check_compact_line(r.stdout, compact)
+    if full_run:
+        check_compact_line(r.stdout, compact)
     with open(full) as fh:
         out = json.load(fh)
     # the compact line is made FROM the full object: the headline numbers agree
@@ -317,6 +318,16 @@ def test_compact_line_of_a_full_headline_object_stays_under_4k():
     assert c["parity_checked"]["bit_exact"] is True
     assert c["icp"]["pairs_per_s"] > 0 and c["icp"]["realistic_pairs_per_s"] > 0 and c["icp"]["cpu_baseline"]["kind"] == "reference"
     assert set(c["other_configs"]) == {"configs[3]", "configs[4]"} and c["other_configs"]["configs[3]"]["bit_exact"] is True
+
+
+def test_bench_plain_dry_run_times_exactly_the_steps_asked_for():
+    """A plain run (no --full) does only what its headline needs: ONE timed pass of exactly --steps steps, whatever --min-seconds says, and none
+    of the legs that --full adds, whatever their own options say; the result line still carries the headline's keys."""
+    out = _bench_dry_run(2, ["--steps", "3", "--warmup", "1", "--frames-per-step", "50", "--icp-pairs", "5", "--min-seconds", "5"], full_run=False)
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["timing"]["passes"] == 1
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 * out["steps"] - 2 * 150) < 1e-6 * 300
+    for k in ("roofline", "icp", "cpu_baseline", "parity_checked", "streamed", "other_configs", "boundary", "fragment_optimizer"):
+        assert k not in out, k
 
 
 def test_bench_dry_run_config4_and_config5_two_ranks():

@@ -81,7 +81,7 @@ def test_bench_two_ranks_over_rccl(gpu, tmp_path):
     s.close()
     full = str(tmp_path / "bench_full.json")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--min-seconds", "0.3", "--icp-pairs", "0", "--full-json", full]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "4", "--warmup", "1", "--min-seconds", "0.3", "--icp-pairs", "0", "--full-json", full]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     last = [l for l in r.stdout.splitlines() if l.strip()][-1]

@@ -3,6 +3,8 @@ import numpy as np
 
 from elasticreconstruction_amd import formats, synth
 
+import helpers
+
 
 def test_log_info_ctr_camera_corres_roundtrip(tmp_path):
     T = [formats.FramedTransformation(i, i + 1, 7 if i else -1, synth.perturbation(i, 30, 1.0)) for i in range(4)]
@@ -213,7 +215,10 @@ def test_host_program_text_parsers_agree_with_the_python_mirror(tmp_path):
     for a, b, c in zip(traj, back, mine):
         assert (a.id1, a.id2, a.frame) == (b.id1, b.id2, b.frame) == (c.id1, c.id2, c.frame)
         assert np.abs(a.T - b.T).max() < 2e-8 and np.abs(a.T - c.T).max() < 1e-8
-    for ref_log in sorted(glob.glob("/root/reference/Matlab_Toolbox/Example/Data/**/*.log", recursive=True))[:3]:
+    ref_data = helpers.reference_example_data(tmp_path / "ref_data")
+    ref_logs = sorted(glob.glob(os.path.join(ref_data, "**", "*.log"), recursive=True))[:3]
+    assert len(ref_logs) == 3
+    for ref_log in ref_logs:
         r = subprocess.run([exe, "log", ref_log, out], check=True, capture_output=True, text=True)
         mine = formats.load_log(ref_log)
         back = formats.load_log(out)
