@@ -29,13 +29,8 @@
 namespace {
 
 constexpr int kBlock = 256;
-#ifndef ER_FOPT_CHUNK
-#define ER_FOPT_CHUNK 512
-#endif
-#ifndef ER_FOPT_MINBLOCKS
-#define ER_FOPT_MINBLOCKS 2
-#endif
-constexpr int kChunkMax = ER_FOPT_CHUNK;   // correspondences per wave task
+constexpr int kChunkMax = 512;   // correspondences per wave task
+constexpr int kGramMinBlocks = 2;
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
@@ -113,7 +108,7 @@ __global__ void k_fopt_update_pn(const int* __restrict__ idx0, const float* __re
 // the regularizer only).  MODE 2 writes block-sparse output: G11 / G22 into the per-fragment, per-cell 24x24 blocks `JJ`
 // ([fragment][corner vertex][24][24], both triangles like AddHessian) and G12 into `Jb` = one 24x24 block per group.
 template <int MODE>
-__global__ __launch_bounds__(kBlock, ER_FOPT_MINBLOCKS) void k_fopt_gram(const Chunk* __restrict__ chunks, int n_chunks, const FragPtr* __restrict__ frags,
+__global__ __launch_bounds__(kBlock, kGramMinBlocks) void k_fopt_gram(const Chunk* __restrict__ chunks, int n_chunks, const FragPtr* __restrict__ frags,
                                                       const int* __restrict__ first, const int* __restrict__ second,
                                                       const double* __restrict__ rot_t, int num, int res, int N,
                                                       double* __restrict__ JJ, double* __restrict__ Jb, double* __restrict__ score) {

@@ -47,15 +47,8 @@ constexpr int kAcc = 32;   // 21 ATA + 6 ATb + sum d^2 + count (+ padding)
 
 // PairDev carries its pointers through memory, so the compiler emits FLAT loads for them (64-bit VALU address arithmetic, both wait counters).
 // The hot accesses go through explicitly GLOBAL pointer types: global_load with a scalar base and a 32-bit offset, vmcnt only.
-#ifndef ER_ICP_GLOBAL_PTR
-#define ER_ICP_GLOBAL_PTR 1
-#endif
 typedef float f4v __attribute__((ext_vector_type(4)));
-#if ER_ICP_GLOBAL_PTR
 #define ER_GLOBAL __attribute__((address_space(1)))
-#else
-#define ER_GLOBAL
-#endif
 typedef const ER_GLOBAL f4v* gp_f4;
 typedef const ER_GLOBAL float* gp_f;
 typedef const ER_GLOBAL int* gp_i;
@@ -67,9 +60,7 @@ typedef ER_GLOBAL int* gp_iw;
 // searched only if its home cell lies within one cell of the box, so every cell of its 27-neighbourhood EXISTS -- no flags, range tests or clamps -- and
 // the four bounds L, O, R, E of a row's three cells x-1, x, x+1 are four consecutive ints of cell_start: one 16-byte load per row.
 // (What was tried on this search and dropped, with numbers: profiles/HISTORY.md "Path B: the search, rounds 3-6".)
-#ifndef ER_NN_PAD_BATCH
-#define ER_NN_PAD_BATCH 4      // rows whose four bounds are in flight at a time (4 registers per row; 8 = all rows: +11 VGPRs, within the noise)
-#endif
+constexpr int kPadBatch = 4;   // rows whose four bounds are in flight at a time (4 registers per row; 8 = all rows: +11 VGPRs, within the noise)
 typedef int i4v __attribute__((ext_vector_type(4), aligned(4)));   // (the four bounds of a row start at an arbitrary cell: 4-byte alignment only)
 struct Grid {
   const float4* pts;
@@ -79,7 +70,7 @@ struct Grid {
   int dim[3];      // cells of the bounding box per axis (the array has dim + 4 per axis: two rings of empty cells)
   float slack;     // absolute part of nn_block's pruning margin (square metres), from the grid's extent: grid_slack()
   int pnx, pny;    // dim[0] + 4, dim[1] + 4: strides of the padded array
-  const unsigned char* occ;   // [cells] 1 = some cell of this cell's 27-neighbourhood holds a point (round 6; see ER_NN_OCC)
+  const unsigned char* occ;   // [cells] 1 = some cell of this cell's 27-neighbourhood holds a point (round 6; see nn_block)
 };
 
 // The pruning margin of nn_block.  A cell (or row of cells) is skipped when the squared distance f'^2 from the query to its nearest face, as the
@@ -112,19 +103,10 @@ struct Mat12f { float m[12]; };
 // Why: ~1.7 of the 8 neighbour rows survive for an average query, but a SIMT loop runs every row ANY lane needs; compacting the survivors across the
 // workgroup removes that waste.  Candidates are scanned kUnroll at a time (the 16-byte loads are issued together).  What bounds it (counters,
 // profiles/r04w_*, r05f_*): VALU issue in the straight-line part every query runs (~360 of ~735 instructions per slice of 64 queries) and LDS traffic per task.
-#ifndef ER_ICP_UNROLL
-#define ER_ICP_UNROLL 4
-#endif
-constexpr int kUnroll = ER_ICP_UNROLL;
+constexpr int kUnroll = 4;
 constexpr unsigned long long kNoHit = ((unsigned long long)0x7f7fffffu << 32) | 0xffffffffull;   // (FLT_MAX, -1)
 
-#ifndef ER_NN_TASKCAP
-#define ER_NN_TASKCAP (kBlock * 4)
-#endif
-#ifndef ER_NN_OCC
-#define ER_NN_OCC 1
-#endif
-constexpr int kTaskCap = ER_NN_TASKCAP;   // (query, row) tasks of phase 1 held in LDS; a task beyond that is scanned by the thread that found it
+constexpr int kTaskCap = kBlock * 4;   // (query, row) tasks of phase 1 held in LDS; a task beyond that is scanned by the thread that found it
 
 struct NnShared {
   unsigned long long best[kBlock];
@@ -139,9 +121,6 @@ struct NnShared {
 // The kU loads of a trip are NOT clamped to the range: a trip that starts inside [s0, s1) may read up to kU - 1 entries past s1.  Those are points of the
 // cells that follow in the cell-sorted array -- REAL points of the same cloud, so the minimum over the wider set is still the exact nearest neighbour --
 // or, behind the cloud's last point, the kSentinel entries of +inf er_cloud_create appends (distance inf / NaN: a bit pattern that never wins).
-#ifndef ER_NN_NOCLAMP
-#define ER_NN_NOCLAMP 1
-#endif
 constexpr int kSentinel = 8;            // float4 entries of +inf behind every cloud's sorted array (>= the largest kU - 1)
 template <int kU = kUnroll>
 __device__ __forceinline__ unsigned long long scan_range(const Grid& g, int s0, int s1, float qx, float qy, float qz, unsigned long long key) {
@@ -152,11 +131,7 @@ __device__ __forceinline__ unsigned long long scan_range(const Grid& g, int s0, 
   for (unsigned o = (unsigned)s0 * 16u; o <= last && s0 < s1; o += 16u * kU) {
     f4v p[kU];
 #pragma unroll
-#if ER_NN_NOCLAMP
     for (int u = 0; u < kU; u++) p[u] = *(const ER_GLOBAL f4v*)(base + o + 16u * (unsigned)u);
-#else
-    for (int u = 0; u < kU; u++) p[u] = *(const ER_GLOBAL f4v*)(base + min(o + 16u * (unsigned)u, last));
-#endif
 #pragma unroll
     for (int u = 0; u < kU; u++) {
       const float dx = qx - p[u].x, dy = qy - p[u].y, dz = qz - p[u].z;
@@ -189,14 +164,10 @@ __device__ __forceinline__ int nn_block(NnShared& sh, const Grid& g, bool active
   const int ix = inside ? (int)cx : 0, iy = inside ? (int)cy : 0, iz = inside ? (int)cz : 0;
   __syncthreads();                                            // (sh.ntask is zero)
   unsigned long long key = kNoHit;
-#if ER_NN_OCC
   // A query whose whole 27-neighbourhood is empty (55-63 % of the queries of a fragment pair: the part of the source that does not overlap the target)
   // has no neighbour within the radius; one byte per cell (k_chunk_occ) says so before the row tests.  Queries come in the source's cell order: whole
   // waves leave here (9-10 % of the ICP phase, profiles/r06c_*).
   const bool live = inside && ER_GP(const ER_GLOBAL unsigned char*, g.occ)[(unsigned)(((iz + 2) * g.pny + (iy + 2)) * g.pnx + (ix + 2))] != 0;
-#else
-  const bool live = inside;
-#endif
   if (live) {
     // distance from q to the lower / upper face of its own cell along x, y and z (metres), squared
     const float xlo = (ux - cx) * g.cell, xhi = g.cell - xlo, ylo = (uy - cy) * g.cell, yhi = g.cell - ylo, zlo = (uz - cz) * g.cell,
@@ -231,16 +202,16 @@ __device__ __forceinline__ int nn_block(NnShared& sh, const Grid& g, bool active
     const float yl2 = ylo * ylo, yh2 = yhi * yhi, zl2 = zlo * zlo, zh2 = zhi * zhi;
     int r_s0[8], r_n[8];
 #pragma unroll
-    for (int j0 = 0; j0 < 8; j0 += ER_NN_PAD_BATCH) {           // (ER_NN_PAD_BATCH rows' bounds in flight at a time: 4 registers per row)
-      i4v rb[ER_NN_PAD_BATCH];
+    for (int j0 = 0; j0 < 8; j0 += kPadBatch) {                 // (kPadBatch rows' bounds in flight at a time: 4 registers per row)
+      i4v rb[kPadBatch];
 #pragma unroll
-      for (int jj = 0; jj < ER_NN_PAD_BATCH; jj++) {
+      for (int jj = 0; jj < kPadBatch; jj++) {
         const int j = j0 + jj, pass = j < 4 ? j : j + 1;
         const int dy = pass % 3 - 1, dz = pass / 3 - 1;
         rb[jj] = *(const ER_GLOBAL i4v*)(csb + (unsigned)(home + (dz * pny + dy) * pnx) * 4u);
       }
 #pragma unroll
-      for (int jj = 0; jj < ER_NN_PAD_BATCH; jj++) {
+      for (int jj = 0; jj < kPadBatch; jj++) {
         const int j = j0 + jj, pass = j < 4 ? j : j + 1;
         const int dy = pass % 3 - 1, dz = pass / 3 - 1;
         const float e2 = (dy < 0 ? yl2 : (dy > 0 ? yh2 : 0.f)) + (dz < 0 ? zl2 : (dz > 0 ? zh2 : 0.f));
@@ -1242,9 +1213,7 @@ Grid grid_of(const er_cloud_s* c) { return c->grid; }
 // The pool is never freed behind the HIP runtime's back (er_icp_release_workspaces does it).
 struct Group {
   int device = 0;
-  hipStream_t stream = nullptr, copy_stream = nullptr, copy_stream2 = nullptr;   // copy streams: list copies alternate between them ...
-  hipStream_t copy_more[2] = {nullptr, nullptr};    // ... and two more (round 6; created on first use): which SDMA engine a stream's copies run on is the
-                                                    // runtime's choice, and two streams that share one engine move 83 MB of lists in 4.4 instead of 1.6 ms
+  hipStream_t stream = nullptr, copy_stream = nullptr, copy_stream2 = nullptr;   // copy streams: list copies alternate between them
   hipEvent_t ev = nullptr, ev2 = nullptr;
   std::vector<hipEvent_t> sub_ev, sub_ev2;  // per sub-group of er_find_correspondence_batch (grown on demand): done / scanned
   int cap_pairs = 0;
@@ -1294,11 +1263,6 @@ void group_destroy(Group* g) {
   if (g->stream) (void)hipStreamSynchronize(g->stream);
   if (g->copy_stream) (void)hipStreamSynchronize(g->copy_stream);
   if (g->copy_stream2) (void)hipStreamSynchronize(g->copy_stream2);
-  for (hipStream_t x : g->copy_more)
-    if (x) {
-      (void)hipStreamSynchronize(x);
-      (void)hipStreamDestroy(x);
-    }
   group_free_slabs(g);
   group_free_pairs(g);
   if (g->stage) (void)hipHostFree(g->stage);
@@ -1315,18 +1279,10 @@ void group_destroy(Group* g) {
 }
 
 int nblocks_of(int n) { return (std::max(n, 1) + kBlock - 1) / kBlock; }
-#ifndef ER_ICP_FIXED_PTS
-#define ER_ICP_FIXED_PTS 0
-#endif
-#ifndef ER_PRECHECK_WGS
-#define ER_PRECHECK_WGS 16384    // workgroups of one k_count_inliers launch (each strides over its pair's slices; 8192: +3 % time, 32768: the same)
-#endif
+constexpr int kPrecheckWgs = 16384;    // workgroups of one k_count_inliers launch (each strides over its pair's slices; 8192: +3 % time, 32768: the same)
 // Slices of 256 points per workgroup of k_icp_iter when `blocks` slices are to be searched in one launch (the 29 cross-lane sums are paid
 // once per workgroup, so more slices per workgroup are cheaper as long as the launch still fills the chip).
-int icp_pts(long blocks) {
-  if (ER_ICP_FIXED_PTS) return ER_ICP_FIXED_PTS;
-  return blocks >= 1024 ? kIcpPtsMax : 1;
-}
+int icp_pts(long blocks) { return blocks >= 1024 ? kIcpPtsMax : 1; }
 int nparts_of(int n, int pts) { return (std::max(n, 1) + kBlock * pts - 1) / (kBlock * pts); }
 
 // Room for `pairs` descriptors and, when per-point scratch is needed, for `points` source points in `blocks` / `parts` blocks.
@@ -1355,8 +1311,6 @@ int group_reserve(Group* g, int pairs, size_t points, size_t blocks, size_t part
     ER_HIP_TRY(hipStreamSynchronize(g->stream));
     if (g->copy_stream) ER_HIP_TRY(hipStreamSynchronize(g->copy_stream));
     if (g->copy_stream2) ER_HIP_TRY(hipStreamSynchronize(g->copy_stream2));
-    for (hipStream_t x : g->copy_more)
-      if (x) ER_HIP_TRY(hipStreamSynchronize(x));
     const size_t cp = std::max(points + points / 8, g->cap_points), cb = std::max(blocks + blocks / 8, g->cap_blocks),
                  cq = std::max(parts + parts / 8, g->cap_parts);
     group_free_slabs(g);
@@ -1426,8 +1380,6 @@ struct GroupLease {             // RAII: the group of one API call
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     if (g->copy_stream) (void)hipStreamSynchronize(g->copy_stream);
     if (g->copy_stream2) (void)hipStreamSynchronize(g->copy_stream2);
-    for (hipStream_t x : g->copy_more)
-      if (x) (void)hipStreamSynchronize(x);
     std::lock_guard<std::mutex> lock(pool().mu);
     pool().idle.push_back(g);
   }
@@ -1530,22 +1482,14 @@ int max_points(int i0, int m, const er_cloud_t* src) {
 // Lists are written in place by k_compact when the GPU can address the destination: device memory (no device-to-device copy) and page-locked host
 // memory (no hipMemcpyAsync).  For a host destination that is 2.1-2.5 ms per 50-pair list whatever the state of the process: the copies it replaces
 // took 1.6-1.9 ms when their two streams ran on separate SDMA engines and 4.3-4.7 ms when they shared one -- the runtime's choice, whole processes
-// long (profiles/r06h_realistic_probe.txt, r06l_fc_modes.txt).  ER_ICP_DIRECT_LISTS=0 copies everything, =d only device destinations are written in place.
-static int direct_lists() {
-  static const int mode = [] { const char* e = getenv("ER_ICP_DIRECT_LISTS"); return e ? (e[0] == '0' ? 0 : (e[0] == 'd' ? 1 : 2)) : 2; }();
-  return mode;                                                 // 0: never, 1: device destinations, 2: device and page-locked host destinations
-}
+// long (profiles/r06h_realistic_probe.txt, r06l_fc_modes.txt).
 // Set by er_registration_batch's share workers: several shares are in flight, each on a thread and workspace of its own, so a share's list copies run
 // behind the other shares' kernels -- and six shares' PCIe-bound compaction kernels at once are slower than their copies (fused list 6.05 against 4.28 ms,
 // profiles/r06q_fused_modes.txt).  A single caller has nothing to hide a copy behind: its lists are written in place.
 static thread_local bool tl_lists_by_copy = false;
 
-// Copy streams the list copies of one call are dealt to when lists ARE copied (pageable or too small destinations): ER_ICP_COPY_STREAMS = 1 .. 4,
-// default 2 (four streams: 2.5-3.0 ms whatever the engines do, two: 1.6 or 4.4 ms; profiles/r06j_fc_modes.txt).
-static int list_copy_streams() {
-  static const int n = [] { const char* e = getenv("ER_ICP_COPY_STREAMS"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : (v > 4 ? 4 : v); }();
-  return n;
-}
+// When lists ARE copied (pageable or too small destinations), the copies of one call are dealt to the group's two copy streams (four streams:
+// 2.5-3.0 ms whatever the engines do, two: 1.6 or 4.4 ms; profiles/r06j_fc_modes.txt).
 
 // Where a caller's list buffer lives: 0 = pageable host memory (staged through the group's page-locked block), 1 = page-locked host memory (the copy
 // goes straight there), 2 = DEVICE memory of `device` (round 5: the list stays in HBM -- a device-to-device copy of exactly the list, no PCIe; what a
@@ -1593,7 +1537,6 @@ void expand_information(const double* acc, double* I) {
 // pipeline (the third one meets the stop rule) and 4 on a few: one chunk usually ends the job; workgroups of a chunk that come after a pair's
 // stop decision return at once.
 constexpr int kIcpChunk = 4;
-static int icp_chunk() { const char* e = getenv("ER_ICP_CHUNK"); const int v = e ? atoi(e) : kIcpChunk; return v < 1 ? 1 : (v > 20 ? 20 : v); }   // (A/B switch)
 
 }  // namespace
 
@@ -1950,7 +1893,7 @@ int er_icp_count_inliers_batch(int n, const er_cloud_t* src, const er_cloud_t* t
     const int mx = max_points(i0, m, src);
     if (mx > 0) {
       // a few thousand workgroups in flight fill the chip; each strides over its pair's points (one atomic per workgroup)
-      const int bx = std::max(1, std::min(nblocks_of(mx), std::max(64, ER_PRECHECK_WGS / m)));
+      const int bx = std::max(1, std::min(nblocks_of(mx), std::max(64, kPrecheckWgs / m)));
       hipLaunchKernelGGL(k_count_inliers, dim3(bx, m), dim3(kBlock), 0, g->stream, g->d_pairs, (float)max_dist, max_dist * max_dist, g->d_counts);
       ER_HIP_TRY(hipGetLastError());
     }
@@ -2008,7 +1951,7 @@ int er_icp_align_batch(int n, const er_cloud_t* src, const er_cloud_t* tgt, cons
       // the first chunk ends the job for most pairs; the stragglers then run twice as many iterations per host visit.  A launch pair whose pairs
       // are all done costs ~12 us (every workgroup leaves at once), a host visit ~60 us plus the ramp of the next launch: chunks err on the long side
       // (round 5: 4 then 8 iterations instead of 3 then 6 -- the one pair of the bench list that needs a fourth iteration no longer costs a second visit)
-      const int chunk_len = chunk_no++ == 0 ? icp_chunk() : 2 * icp_chunk();
+      const int chunk_len = chunk_no++ == 0 ? kIcpChunk : 2 * kIcpChunk;
       ER_HIP_TRY(hipMemcpyAsync(g->d_active, g->h_active, (size_t)n_active * sizeof(int), hipMemcpyHostToDevice, g->stream));
       // points per thread of k_icp_iter for THIS chunk: as many slices of 256 points per workgroup as still leave ~4 workgroups per CU in
       // flight -- 8 for a full list, 1 for the two or three stragglers of a hard list on their way to the iteration limit (round 4: the
@@ -2198,7 +2141,7 @@ int er_find_correspondence_batch(int n, const er_cloud_t* src, const er_cloud_t*
   size_t stage_need = 0;
   std::vector<char> direct((size_t)n, 0);                      // destination is page-locked: the list is copied straight into it
   // A list whose buffer the GPU can address and that has room for the largest possible list (one pair per source point) can be written THERE by k_compact:
-  // no copy at all (direct_lists()).  The copies of the other lists are dealt to up to four copy streams: with two, both could land on ONE SDMA engine --
+  // no copy at all.  The copies of the other lists are dealt to two copy streams, and both could land on ONE SDMA engine --
   // 83 MB of lists in 4.4 instead of 1.6 ms (20 against 51 GB/s), whole processes long, flipping after unrelated calls created more streams
   // (profiles/r06h_realistic_probe.txt; BENCH_r05's kinfu-like figure sat in the slow mode).
   std::vector<int*> written((size_t)n, nullptr);
@@ -2210,7 +2153,7 @@ int er_find_correspondence_batch(int n, const er_cloud_t* src, const er_cloud_t*
       if (kind < 0) return er::fail("er_find_correspondence: the list buffer of pair %d lives on another GPU than its clouds", i);
       direct[(size_t)i] = (char)kind;                                           // 1: page-locked host, 2: device memory -- both are copied to directly
       if (!direct[(size_t)i]) stage_need += (size_t)std::min(capacity[i], src[i]->n) * 2;
-      if (kind > 0 && view && capacity[i] >= src[i]->n && ((uintptr_t)view & 7u) == 0 && direct_lists() >= (kind == 2 ? 1 : 2) && !(kind == 1 && tl_lists_by_copy)) written[(size_t)i] = static_cast<int*>(view);
+      if (kind > 0 && view && capacity[i] >= src[i]->n && ((uintptr_t)view & 7u) == 0 && !(kind == 1 && tl_lists_by_copy)) written[(size_t)i] = static_cast<int*>(view);
     }
   }
   GroupLease L;
@@ -2221,14 +2164,10 @@ int er_find_correspondence_batch(int n, const er_cloud_t* src, const er_cloud_t*
   size_t stage_used = 0;
   const int G = group_cfg();
   int rc = 0;
-  const int ncs = list_copy_streams();
-  for (int q = 0; q < 2 && q + 2 < ncs; q++)
-    if (!g->copy_more[q]) ER_HIP_TRY(hipStreamCreateWithFlags(&g->copy_more[q], hipStreamNonBlocking));
-  hipStream_t cs[4] = {g->copy_stream, ncs > 1 ? g->copy_stream2 : g->copy_stream, ncs > 2 ? g->copy_more[0] : g->copy_stream,
-                       ncs > 3 ? g->copy_more[1] : (ncs > 1 ? g->copy_stream2 : g->copy_stream)};
+  hipStream_t cs[2] = {g->copy_stream, g->copy_stream2};
   for (int i0 = 0; i0 < n; i0 += G) {
     const int m = std::min(G, n - i0);
-    for (int q = 0; q < 4; q++) ER_HIP_TRY(hipStreamSynchronize(cs[q]));          // the previous group's lists have left the slabs
+    for (int q = 0; q < 2; q++) ER_HIP_TRY(hipStreamSynchronize(cs[q]));          // the previous group's lists have left the slabs
     if (group_describe(g, i0, m, src, tgt, T, true, written.data())) return 1;
     ER_HIP_TRY(hipMemsetAsync(g->d_info, 0, (size_t)m * kAcc * sizeof(double), g->stream));
     // sub-groups exist to put the list copies of one behind the kernels of the next (PCIe); when every list of this group stays in HBM there is nothing
@@ -2236,14 +2175,14 @@ int er_find_correspondence_batch(int n, const er_cloud_t* src, const er_cloud_t*
     bool all_dev = true;
     for (int q = 0; q < m; q++) all_dev = all_dev && (capacity[i0 + q] <= 0 || direct[(size_t)(i0 + q)] == 2 || written[(size_t)(i0 + q)]);
     // Sub-groups put list COPIES behind the next kernels.  Lists that k_compact writes into HOST memory cross PCIe with its stores (1.5 ms for the 83 MB of
-    // a 50-pair list: the link's rate, scripts/ubench/d2h_paths.hip) while the searches need 0.7 ms of the GPU: the group is cut into ER_ICP_FC_SPLIT parts;
+    // a 50-pair list: the link's rate, scripts/ubench/d2h_paths.hip) while the searches need 0.7 ms of the GPU: the group is cut into kFcSplit parts;
     // searches, counts and scans stay on the compute stream, the compactions go to two side streams behind an event each, so that one part's stores
     // leave while the next part searches.
     bool host_written = false;
     for (int q = 0; q < m; q++) host_written = host_written || (written[(size_t)(i0 + q)] && direct[(size_t)(i0 + q)] == 1);
-    static const int fc_split = [] { const char* e = getenv("ER_ICP_FC_SPLIT"); const int v = e ? atoi(e) : 4; return v < 1 ? 1 : (v > 16 ? 16 : v); }();
-    const bool split = all_dev && host_written && fc_split > 1 && m >= 2 * fc_split;
-    const int sub = all_dev ? (split ? (m + fc_split - 1) / fc_split : std::max(m, 1)) : kCorrSub;
+    constexpr int kFcSplit = 4;
+    const bool split = all_dev && host_written && m >= 2 * kFcSplit;
+    const int sub = all_dev ? (split ? (m + kFcSplit - 1) / kFcSplit : std::max(m, 1)) : kCorrSub;
     const int nsub = (m + sub - 1) / sub;
     hipStream_t ks[2] = {g->stream, g->stream};
     while (split && (int)g->sub_ev2.size() < nsub) {
@@ -2286,7 +2225,7 @@ int er_find_correspondence_batch(int n, const er_cloud_t* src, const er_cloud_t*
         if (n_pairs[i] > capacity[i]) rc = er::fail("er_find_correspondence: %d pairs exceed the capacity %d", n_pairs[i], capacity[i]);
       }
       // copies of this sub-group's lists on the copy stream (its kernels are done: evs[s] has been waited for)
-      for (int q = 0; q < ncs; q++) ER_HIP_TRY(hipStreamWaitEvent(cs[q], evs[(size_t)s], 0));
+      for (int q = 0; q < 2; q++) ER_HIP_TRY(hipStreamWaitEvent(cs[q], evs[(size_t)s], 0));
       for (int q = 0; q < ms; q++) {
         const int i = i0 + s0 + q, ncopy = std::min(n_pairs[i], capacity[i]);
         if (ncopy <= 0 || written[(size_t)i]) continue;          // (written in place by k_compact)
@@ -2297,7 +2236,7 @@ int er_find_correspondence_batch(int n, const er_cloud_t* src, const er_cloud_t*
           stage_used += (size_t)ncopy * 2;
         }
         if (hipMemcpyAsync(dst, g->h_pairs[s0 + q].pairs, (size_t)ncopy * 2 * sizeof(int), direct[(size_t)i] == 2 ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                           cs[i % ncs]) != hipSuccess) {
+                           cs[i % 2]) != hipSuccess) {
           cleanup();
           return er::fail("er_find_correspondence: %s", hipGetErrorString(hipGetLastError()));
         }
@@ -2305,7 +2244,7 @@ int er_find_correspondence_batch(int n, const er_cloud_t* src, const er_cloud_t*
     }
     cleanup();
   }
-  for (int q = 0; q < 4; q++) ER_HIP_TRY(hipStreamSynchronize(cs[q]));
+  for (int q = 0; q < 2; q++) ER_HIP_TRY(hipStreamSynchronize(cs[q]));
   for (int i = 0; i < n; i++)
     if (staged[(size_t)i] >= 0) memcpy(pairs_host[i], g->stage + staged[(size_t)i], (size_t)std::min(n_pairs[i], capacity[i]) * 2 * sizeof(int));
   return rc;

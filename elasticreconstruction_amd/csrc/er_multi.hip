@@ -2,12 +2,12 @@
 // library itself so that the C++ drop-in programs (and any other host) need neither torch nor MPI.
 //
 //   frames (path A, as BASELINE.json prescribes): contiguous frame blocks per GPU into private volumes, then
-//       er_tsdf_allreduce = [agree on the key count: all-reduce(MAX) of one int] -> [all-gather of the touched unit keys,
-//       padded to that count] -> union + who touched what -> ONE ncclReduce / ncclAllReduce (sum, float) over the
-//       [key][sdf*weight | weight] planes of the units two or more ranks touched -> import (weight = W, sdf = SW / W), and one
-//       grouped ncclSend / ncclRecv step for the units only one rank touched (raw, bit for bit; er_merge_protocol.h).  The running
-//       mean with unit weights is a sum (TSDFVolume.cpp:93-94: sdf' = (sdf w + tsdf) / (w + 1), w' = w + 1), so this equals the
-//       sequential result up to the float32 rounding order: weights exact, sdf within 1e-5 (exact in single-toucher units).
+//       er_tsdf_allreduce = the owner merge of er_merge_protocol.h: [agree on the key count: all-reduce(MAX)] -> [all-gather of
+//       the touched unit keys and their band sizes] -> every unit gets an owner -> ONE grouped ncclSend / ncclRecv step carries the
+//       other touchers' band records to the owner, which adds them in rank order (weight = W, sdf = SW / W) -> the finished units
+//       travel to the root / to everybody in a second grouped step (or stay distributed).  The running mean with unit weights is a
+//       sum (TSDFVolume.cpp:93-94: sdf' = (sdf w + tsdf) / (w + 1), w' = w + 1), so this equals the sequential result up to the
+//       float32 rounding order: weights exact, sdf within 1e-5 (exact in single-toucher units), bit-reproducible from run to run.
 //   units  (the bit-exact alternative): er_tsdf_set_unit_shard in er_tsdf.hip -- no collective at all.
 //   pairs  (path B): independent, no collective (BuildCorrespondence --gpus).
 //
@@ -40,7 +40,6 @@ struct Rccl {
   decltype(&ncclCommInitAll) CommInitAll = nullptr;
   decltype(&ncclCommDestroy) CommDestroy = nullptr;
   decltype(&ncclAllReduce) AllReduce = nullptr;
-  decltype(&ncclReduce) Reduce = nullptr;
   decltype(&ncclAllGather) AllGather = nullptr;
   decltype(&ncclSend) Send = nullptr;
   decltype(&ncclRecv) Recv = nullptr;
@@ -75,7 +74,6 @@ Rccl* rccl() {
     ER_SYM(CommInitAll, "ncclCommInitAll");
     ER_SYM(CommDestroy, "ncclCommDestroy");
     ER_SYM(AllReduce, "ncclAllReduce");
-    ER_SYM(Reduce, "ncclReduce");
     ER_SYM(AllGather, "ncclAllGather");
     ER_SYM(Send, "ncclSend");
     ER_SYM(Recv, "ncclRecv");
@@ -83,9 +81,9 @@ Rccl* rccl() {
     ER_SYM(GroupEnd, "ncclGroupEnd");
     ER_SYM(GetErrorString, "ncclGetErrorString");
 #undef ER_SYM
-    R.ok = R.GetUniqueId && R.CommInitRank && R.CommInitAll && R.CommDestroy && R.AllReduce && R.Reduce && R.AllGather && R.Send && R.Recv &&
+    R.ok = R.GetUniqueId && R.CommInitRank && R.CommInitAll && R.CommDestroy && R.AllReduce && R.AllGather && R.Send && R.Recv &&
            R.GroupStart && R.GroupEnd && R.GetErrorString;
-    if (!R.ok) snprintf(R.why, sizeof R.why, "librccl.so.1 lacks one of the twelve nccl* entry points");
+    if (!R.ok) snprintf(R.why, sizeof R.why, "librccl.so.1 lacks one of the eleven nccl* entry points");
   });
   return R.ok ? &R : nullptr;
 }
@@ -102,9 +100,8 @@ Rccl* rccl() {
 
 // ---- loopback communicator (round 5): N ranks = N host threads of ONE process, all on ONE device ----------------------------------------------
 // RCCL refuses two ranks on one GPU and the builder's boxes have one, so until round 5 no N > 1 merge had ever touched a device volume.  The loopback
-// transport runs the SAME protocol header over the SAME device volumes, export / import kernels and plane buffers; only the wire is replaced: the sum
-// reduction is a kernel that adds the ranks' plane buffers in rank order, the point-to-point step is a device-to-device copy, the small host collectives
-// go through a mutex / condition-variable barrier.  It is what `bin/Integrate --gpus N --same_device` and tests/test_tsdf_gpu.py use; it says nothing
+// transport runs the SAME protocol header over the SAME device volumes, band-record kernels and buffers; only the wire is replaced: the point-to-point
+// step is a device-to-device copy, the small host collectives go through a mutex / condition-variable barrier.  It is what `bin/Integrate --gpus N --same_device` and tests/test_tsdf_gpu.py use; it says nothing
 // about xGMI.
 struct ErLoop {
   int world = 1, device = 0;
@@ -113,14 +110,11 @@ struct ErLoop {
   int arrived = 0, generation = 0;
   std::vector<const int*> iptr;
   std::vector<int> ibuf;
-  std::vector<float*> fptr;
-  std::vector<const float*> xsend;
-  std::vector<size_t> xcount;
-  std::vector<std::vector<int>> xto;
-  std::vector<std::vector<size_t>> voff, vcnt;                  // exchange_v: every rank's per-receiver offsets and counts
+  std::vector<const float*> xsend;                              // exchange_v: every rank's send block, its per-receiver offsets and counts
+  std::vector<std::vector<size_t>> voff, vcnt;
   int pending_vote = 0, result_vote = 0;
   explicit ErLoop(int w, int dev)
-      : world(w), device(dev), iptr((size_t)w), fptr((size_t)w), xsend((size_t)w), xcount((size_t)w), xto((size_t)w), voff((size_t)w), vcnt((size_t)w) {}
+      : world(w), device(dev), iptr((size_t)w), xsend((size_t)w), voff((size_t)w), vcnt((size_t)w) {}
   // `last` runs inside the critical section of the last arriver.  Returns the OR of every rank's `vote`: how a failure that only ONE rank saw
   // (a kernel launch, a copy) reaches all of them before anybody decides to skip a later step the others would wait in.
   template <class F> int barrier(F last, int vote = 0) {
@@ -145,16 +139,10 @@ struct er_comm_s {
   std::shared_ptr<ErLoop> loop;   // set: a loopback communicator (comm stays NULL)
   ncclComm_t comm = nullptr;
   int rank = 0, world = 1, device = 0;
-  float* buf = nullptr;        // [multi-toucher units][sdf*w | w][64^3] planes of the reduction (grow-only)
-  size_t buf_units = 0;
-  float *sbuf = nullptr, *rbuf = nullptr;   // raw single-toucher units on their way out / in (grow-only)
-  size_t sbuf_units = 0, rbuf_units = 0;
-  er::MergeStats last;         // what the last merge moved (ring protocol)
-  er::OwnerMergeStats last_owner;   // ... (owner protocol)
-  int last_impl = 0;           // 0 = ring (er::merge_protocol), 1 = owner (er::merge_protocol_owner)
-  float* vbuf[2] = {nullptr, nullptr};      // owner merge: incoming records of step 1 / step 3 (grow-only)
+  er::OwnerMergeStats last_owner;           // what the last merge moved
+  float* vbuf[2] = {nullptr, nullptr};      // incoming records of step 1 / step 3 (grow-only)
   size_t vbuf_floats[2] = {0, 0};
-  float* xbuf = nullptr;       // owner merge: outgoing records (grow-only)
+  float* xbuf = nullptr;       // outgoing records (grow-only)
   size_t xbuf_floats = 0;
   int* ikeys = nullptr;        // device scratch: [1 + max_keys * (world + 1)] ints (grow-only)
   size_t ikeys_cap = 0;
@@ -197,40 +185,7 @@ struct RcclTransport : er::MergeTransport {
     ER_HIP_TRY(hipStreamSynchronize(S));
     return 0;
   }
-  int reduce_sum(float* planes, size_t count, int root) override {
-    if (root < 0)
-      ER_NCCL_TRY(R, R->AllReduce(planes, planes, count, ncclFloat32, ncclSum, c->comm, S));   // the only data-path collective
-    else
-      ER_NCCL_TRY(R, R->Reduce(planes, planes, count, ncclFloat32, ncclSum, root, c->comm, S));
-    return 0;
-  }
-  // the single-toucher units: every send and receive of this rank in ONE group (RCCL pairs them up across the ranks; over xGMI each pair is a
-  // direct link).  A rank with nothing to send or receive issues nothing.
-  int exchange(const float* send, size_t send_count, const std::vector<int>& send_to, float* recv, const std::vector<size_t>& recv_count) override {
-    bool any = !send_to.empty() && send_count > 0;
-    for (size_t n : recv_count) any = any || n > 0;
-    if (!any) return 0;
-    ER_NCCL_TRY(R, R->GroupStart());
-    ncclResult_t bad = ncclSuccess;
-    if (send_count > 0)
-      for (int q : send_to) {
-        const ncclResult_t e = R->Send(send, send_count, ncclFloat32, q, c->comm, S);
-        if (e != ncclSuccess) bad = e;
-      }
-    size_t off = 0;
-    for (int q = 0; q < c->world; q++) {
-      const size_t n = recv_count[(size_t)q];
-      if (!n) continue;
-      const ncclResult_t e = R->Recv(recv + off, n, ncclFloat32, q, c->comm, S);
-      if (e != ncclSuccess) bad = e;
-      off += n;
-    }
-    const ncclResult_t e2 = R->GroupEnd();                      // (always closed, whatever a call inside said)
-    if (bad != ncclSuccess || e2 != ncclSuccess)
-      return ::er::fail("er_tsdf_allreduce: ncclSend / ncclRecv failed: %s", R->GetErrorString(bad != ncclSuccess ? bad : e2));
-    return 0;
-  }
-  // owner merge: a block of its own per receiver, every send and receive of this rank in ONE group -- over xGMI every (sender, owner) pair is a
+  // a block of its own per receiver, every send and receive of this rank in ONE group -- over xGMI every (sender, owner) pair is a
   // direct link, so the seven links of a GPU carry their records at the same time (a ring reduction crosses them one after the other)
   int exchange_v(const float* send, const std::vector<size_t>& send_off, const std::vector<size_t>& send_count, float* recv,
                  const std::vector<size_t>& recv_count) override {
@@ -261,17 +216,6 @@ struct RcclTransport : er::MergeTransport {
   }
 };
 
-// (RcclTransport::exchange_v is defined below the class: it shares the group logic)
-// dst[i] = ((src_0[i] + src_1[i]) + ...) + src_{n-1}[i]: the ranks' plane buffers added in rank order (dst may be one of the sources)
-struct LoopSrc { const float* p[16]; };
-__global__ __launch_bounds__(256) void k_loop_sum(LoopSrc S, int n, float* __restrict__ dst, size_t count) {
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) {
-    float a = S.p[0][i];
-    for (int q = 1; q < n; q++) a += S.p[q][i];
-    dst[i] = a;
-  }
-}
-
 // er::MergeTransport over an ErLoop: every rank is a host thread of this process, every buffer lives on the one device.
 struct LoopTransport : er::MergeTransport {
   er_comm_t c;
@@ -301,51 +245,6 @@ struct LoopTransport : er::MergeTransport {
     L.barrier([] {});
     return 0;
   }
-  int reduce_sum(float* planes, size_t count, int root) override {
-    if (L.world > 16) return ::er::fail("er_tsdf_allreduce: the loopback communicator holds at most 16 ranks");
-    int rc = 0;
-    if (hipStreamSynchronize(S) != hipSuccess) rc = 1;         // this rank's export kernel has written `planes`
-    L.fptr[(size_t)c->rank] = planes;
-    rc = L.barrier([] {}, rc);                                  // (from here on rc is the SAME on every rank: nobody skips a barrier the others wait in)
-    const int owner = root < 0 ? 0 : root;                      // the rank that adds; with root < 0 the others copy its result
-    int mine = 0;
-    if (c->rank == owner && !rc) {
-      LoopSrc src;
-      for (int q = 0; q < 16; q++) src.p[q] = q < L.world ? L.fptr[(size_t)q] : nullptr;
-      const unsigned blocks = (unsigned)std::min<size_t>((count + 255) / 256, 16384);
-      hipLaunchKernelGGL(k_loop_sum, dim3(blocks), dim3(256), 0, S, src, L.world, planes, count);
-      if (hipGetLastError() != hipSuccess || hipStreamSynchronize(S) != hipSuccess) mine = 1;
-    }
-    rc = L.barrier([] {}, rc | mine);
-    mine = 0;
-    if (root < 0 && c->rank != owner && !rc) {
-      if (hipMemcpyAsync(planes, L.fptr[(size_t)owner], count * sizeof(float), hipMemcpyDeviceToDevice, S) != hipSuccess || hipStreamSynchronize(S) != hipSuccess) mine = 1;
-    }
-    rc = L.barrier([] {}, rc | mine);                           // the owner's buffer stays untouched until everybody has copied
-    return rc ? ::er::fail("er_tsdf_allreduce (loopback): a rank of the communicator failed in the sum step (%s)", hipGetErrorString(hipGetLastError())) : 0;
-  }
-  int exchange(const float* send, size_t send_count, const std::vector<int>& send_to, float* recv, const std::vector<size_t>& recv_count) override {
-    int rc = 0;
-    if (hipStreamSynchronize(S) != hipSuccess) rc = 1;         // this rank's raw export has written `send`
-    L.xsend[(size_t)c->rank] = send;
-    L.xcount[(size_t)c->rank] = send_count;
-    L.xto[(size_t)c->rank] = send_to;
-    rc = L.barrier([] {}, rc);
-    int mine = 0;
-    size_t off = 0;
-    for (int q = 0; q < L.world && !rc && !mine; q++) {
-      const size_t n = recv_count[(size_t)q];
-      if (!n) continue;
-      const std::vector<int>& to = L.xto[(size_t)q];           // what I expect from q must be what q sends to me
-      if (q == c->rank || n != L.xcount[(size_t)q] || std::find(to.begin(), to.end(), c->rank) == to.end()) mine = 2;
-      else if (hipMemcpyAsync(recv + off, L.xsend[(size_t)q], n * sizeof(float), hipMemcpyDeviceToDevice, S) != hipSuccess) mine = 1;
-      off += n;
-    }
-    if (!rc && !mine && hipStreamSynchronize(S) != hipSuccess) mine = 1;
-    rc = L.barrier([] {}, rc | mine);                           // the senders' blocks stay untouched until everybody has copied
-    if (rc & 2) return ::er::fail("er_tsdf_allreduce (loopback): the ranks disagree about who sends what");
-    return rc ? ::er::fail("er_tsdf_allreduce (loopback): a rank of the communicator failed in the point-to-point step (%s)", hipGetErrorString(hipGetLastError())) : 0;
-  }
   int exchange_v(const float* send, const std::vector<size_t>& send_off, const std::vector<size_t>& send_count, float* recv,
                  const std::vector<size_t>& recv_count) override {
     int rc = 0;
@@ -372,8 +271,8 @@ struct LoopTransport : er::MergeTransport {
   }
 };
 
-// er::MergeVolume over an er_tsdf_t; the planes live in the communicator's grow-only device buffer.
-struct DeviceVolume : er::OwnerMergeVolume {
+// er::MergeVolume over an er_tsdf_t; the records live in the communicator's grow-only device buffers.
+struct DeviceVolume : er::MergeVolume {
   er_tsdf_t h;
   er_comm_t c;
   DeviceVolume(er_tsdf_t vol, er_comm_t comm) : h(vol), c(comm) {}
@@ -387,39 +286,7 @@ struct DeviceVolume : er::OwnerMergeVolume {
     keys.resize((size_t)n);
     return 0;
   }
-  int export_planes(const int* uk, int nu, float** planes) override {
-    if (c->buf_units < (size_t)nu) {
-      if (c->buf) (void)hipFree(c->buf);
-      c->buf = nullptr;
-      c->buf_units = 0;
-      ER_HIP_TRY(hipMalloc((void**)&c->buf, (size_t)nu * 2 * ER_UNIT_VOX * sizeof(float)));
-      c->buf_units = (size_t)nu;
-    }
-    *planes = c->buf;
-    return er_tsdf_export_weighted(h, uk, nu, c->buf);          // on the volume's stream, like the collectives
-  }
-  int import_planes(const int* uk, int nu, const float* planes) override { return er_tsdf_import_weighted(h, uk, nu, planes); }
-  static int grow(float** b, size_t* have, int units) {
-    if (*have >= (size_t)units) return 0;
-    if (*b) (void)hipFree(*b);
-    *b = nullptr;
-    *have = 0;
-    ER_HIP_TRY(hipMalloc((void**)b, (size_t)units * 2 * ER_UNIT_VOX * sizeof(float)));
-    *have = (size_t)units;
-    return 0;
-  }
-  int export_raw(const int* uk, int nu, float** block) override {
-    if (grow(&c->sbuf, &c->sbuf_units, nu)) return 1;
-    *block = c->sbuf;
-    return er_tsdf_export_raw(h, uk, nu, c->sbuf);
-  }
-  int receive_buffer(int nu, float** block) override {
-    if (grow(&c->rbuf, &c->rbuf_units, nu)) return 1;
-    *block = c->rbuf;
-    return 0;
-  }
-  int import_raw(const int* uk, int nu, const float* block) override { return er_tsdf_import_raw(h, uk, nu, block); }
-  // ---- owner merge: band records (er_tsdf.hip) ----
+  // ---- band records (er_tsdf.hip) ----
   static int grow_floats(float** b, size_t* have, size_t floats) {
     if (*have >= floats) return 0;
     if (*b) (void)hipFree(*b);
@@ -561,9 +428,6 @@ int er_comm_create_loopback(int n, int device, er_comm_t* out) {
 int er_comm_destroy(er_comm_t c) {
   if (!c) return 0;
   (void)hipSetDevice(c->device);
-  if (c->buf) (void)hipFree(c->buf);
-  if (c->sbuf) (void)hipFree(c->sbuf);
-  if (c->rbuf) (void)hipFree(c->rbuf);
   if (c->xbuf) (void)hipFree(c->xbuf);
   if (c->vbuf[0]) (void)hipFree(c->vbuf[0]);
   if (c->vbuf[1]) (void)hipFree(c->vbuf[1]);
@@ -582,7 +446,7 @@ int er_comm_world(er_comm_t c) { return c ? c->world : -1; }
 // The frame-split merge (see the file header): er_merge_protocol.h's steps over RCCL and the device-resident volume.  Every
 // rank of the communicator calls it once, each from its own host thread / process; root < 0 leaves the merged volume on
 // every rank, otherwise only on `root`.  A rank-local failure -- a bad `root`, a volume that lives on another device than the
-// communicator, a unit pool / hash table overflow, a failed allocation of the plane buffer -- is carried through the next collective
+// communicator, a unit pool / hash table overflow, a failed allocation of a record buffer -- is carried through the next collective
 // as a status, so ALL ranks return nonzero together instead of the healthy ones waiting for ever (the small device scratch the
 // status travels in is allocated by er_comm_create*, not here).  What stays fatal for the whole communicator: a NULL handle, RCCL
 // missing, and a HIP / RCCL error inside a collective itself (MERGE_TRANSPORT_FAILURE) -- after those the peers' state is unknown.
@@ -590,14 +454,9 @@ int er_tsdf_allreduce(er_tsdf_t h, er_comm_t c, int root, int* union_units) {
   if (!h || !c) return er::fail("er_tsdf_allreduce: NULL argument");
   Rccl* R = c->loop ? nullptr : rccl();
   if (!c->loop && !R) return er::fail("er_tsdf_allreduce: librccl.so.1 could not be loaded (%s)", rccl_reason());
-  // which protocol: the owner merge (round 6; reduce-scatter by unit, band records, rank-ordered sums) unless ER_MERGE_IMPL=ring asks for round 5's
-  // ring reduction of whole planes; a distributed result (root == ER_MERGE_DISTRIBUTED) only exists in the owner merge
-  const char* impl_env = getenv("ER_MERGE_IMPL");
-  const bool ring = impl_env && std::string(impl_env) == "ring";
   int pre = 0;
   if (root >= c->world || root < ER_MERGE_DISTRIBUTED) pre = er::fail("er_tsdf_allreduce: root %d not in [0,%d) and neither ER_MERGE_ALL nor ER_MERGE_DISTRIBUTED", root, c->world);
-  else if (ring && root == ER_MERGE_DISTRIBUTED) pre = er::fail("er_tsdf_allreduce: ER_MERGE_IMPL=ring cannot leave the result distributed (root = ER_MERGE_DISTRIBUTED)");
-  else if (!ring && c->world > 17) pre = er::fail("er_tsdf_allreduce: the owner merge adds at most 17 ranks per unit (ER_MERGE_IMPL=ring has no such limit)");
+  else if (c->world > 17) pre = er::fail("er_tsdf_allreduce: the owner merge adds at most 17 ranks per unit");
   else if (er::tsdf_device(h) != c->device)
     pre = er::fail("er_tsdf_allreduce: the volume lives on device %d, the communicator on %d", er::tsdf_device(h), c->device);
   const hipError_t e = hipSetDevice(c->device);
@@ -608,11 +467,8 @@ int er_tsdf_allreduce(er_tsdf_t h, er_comm_t c, int root, int* union_units) {
   std::unique_ptr<LoopTransport> t_loop(c->loop ? new LoopTransport(c, stream) : nullptr);
   er::MergeTransport& t = c->loop ? static_cast<er::MergeTransport&>(*t_loop) : static_cast<er::MergeTransport&>(t_rccl);
   DeviceVolume v(h, c);
-  c->last = er::MergeStats();
   c->last_owner = er::OwnerMergeStats();
-  c->last_impl = ring ? 0 : 1;
-  const int r = ring ? er::merge_protocol(t, v, root, union_units, pre ? 1 : 0, &c->last)
-                     : er::merge_protocol_owner(t, v, root, union_units, pre ? 1 : 0, &c->last_owner);
+  const int r = er::merge_protocol_owner(t, v, root, union_units, pre ? 1 : 0, &c->last_owner);
   if (r == er::MERGE_OK) {
     ER_HIP_TRY(hipStreamSynchronize(er::tsdf_stream(h)));
     return 0;
@@ -626,7 +482,7 @@ int er_tsdf_allreduce(er_tsdf_t h, er_comm_t c, int root, int* union_units) {
 int er_comm_merge_stats_owner(er_comm_t c, long long stats[12]) {
   if (!c || !stats) return er::fail("er_comm_merge_stats_owner: NULL argument");
   const er::OwnerMergeStats& m = c->last_owner;
-  stats[0] = c->last_impl;
+  stats[0] = 1;                                                   // the owner merge (the only protocol)
   stats[1] = m.union_units; stats[2] = m.multi_units; stats[3] = m.single_units; stats[4] = m.owned_units; stats[5] = m.owned_multi; stats[6] = m.dropped_units;
   stats[7] = (long long)(m.sent_floats[0] * sizeof(float));
   stats[8] = (long long)(m.received_floats[0] * sizeof(float));
@@ -638,19 +494,11 @@ int er_comm_merge_stats_owner(er_comm_t c, long long stats[12]) {
 
 int er_comm_merge_stats(er_comm_t c, long long stats[8]) {
   if (!c || !stats) return er::fail("er_comm_merge_stats: NULL argument");
-  if (c->last_impl == 1) {                                        // the owner merge in the ring protocol's terms
-    const er::OwnerMergeStats& o = c->last_owner;
-    stats[0] = o.union_units; stats[1] = o.multi_units; stats[2] = o.single_units; stats[3] = o.dropped_units; stats[4] = o.owned_multi;
-    stats[5] = 0;                                                 // nothing goes through a reduction collective
-    stats[6] = (long long)((o.sent_floats[0] + o.sent_floats[1]) * sizeof(float));
-    stats[7] = (long long)((o.received_floats[0] + o.received_floats[1]) * sizeof(float));
-    return 0;
-  }
-  const er::MergeStats& m = c->last;
-  stats[0] = m.union_units; stats[1] = m.multi_units; stats[2] = m.single_units; stats[3] = m.sent_units; stats[4] = m.received_units;
-  stats[5] = (long long)(m.reduced_floats * sizeof(float));
-  stats[6] = (long long)(m.sent_floats * sizeof(float));
-  stats[7] = (long long)(m.received_floats * sizeof(float));
+  const er::OwnerMergeStats& o = c->last_owner;                   // the owner merge in the 8-slot terms of round 5's ring protocol
+  stats[0] = o.union_units; stats[1] = o.multi_units; stats[2] = o.single_units; stats[3] = o.dropped_units; stats[4] = o.owned_multi;
+  stats[5] = 0;                                                   // nothing goes through a reduction collective
+  stats[6] = (long long)((o.sent_floats[0] + o.sent_floats[1]) * sizeof(float));
+  stats[7] = (long long)((o.received_floats[0] + o.received_floats[1]) * sizeof(float));
   return 0;
 }
 

@@ -233,24 +233,15 @@ __global__ void k_zbuf_to_depth(uint32_t* __restrict__ zbuf, uint16_t* __restric
 // few hash entries with device-scope atomics at the same moment (measured: 90 % of wave time waiting).
 // Frames of the scaled-depth buffer are kScaledPad floats apart beyond their pixels; the pad stays 0.0f for ever (zero-filled at
 // create, never written): a voxel whose projection misses the image gathers from it instead of taking a predicated load.
-#ifndef ER_FRAMES_TRANSPOSED
-#define ER_FRAMES_TRANSPOSED 1           // k_integrate's culling reads the frame constants component-major (Staging::fxT); 0: frames[lane]
-#endif
-#ifndef ER_TILE_FRAME_FASTEST
-#define ER_TILE_FRAME_FASTEST 1          // tile_max / tile_lo / tile_lo_fine as [tile][frame of the batch] (0: [frame][tile], rounds 1-5)
-#endif
+// tile_max / tile_lo / tile_lo_fine are laid out [tile][frame of the batch]: see k_integrate's culling.
 constexpr int kScaledPad = 64;
 constexpr int kTile = 32;
 // Granularity of tile_lo_fine, the second-level per-tile MINIMUM of the scaled depth behind k_integrate's "full" verdict: 2^kLoShift pixels.
 // 16-pixel tiles next to the 32-pixel tiles of tile_max / tile_lo: a pixel without usable depth (the warp's scatter leaves holes) spoils the
 // minimum of its whole tile.  The fine tiles are the SECOND level of the verdict (er_tsdf_math.h: patch_may_update_box): the 32-pixel minimum
 // decides first, the fine ones are read only when it fails for a patch that lies clearly in front of everything under it.
-#ifndef ER_TILE_LO_SHIFT
-#define ER_TILE_LO_SHIFT 4
-#endif
-constexpr int kLoShift = ER_TILE_LO_SHIFT;
-static_assert(kLoShift >= 3 && kLoShift <= 5, "tile_lo tiles of 8, 16 or 32 pixels");
-constexpr int kLoSub = kTile >> kLoShift;               // tile_lo tiles per side of a 32 x 32 k_prepare tile: 4, 2 or 1
+constexpr int kLoShift = 4;
+constexpr int kLoSub = kTile >> kLoShift;               // tile_lo tiles per side of a 32 x 32 k_prepare tile: 2
 constexpr int kTileKeys = 96;
 
 // Marks frame f in the unit's mask; the first toucher of the unit IN THIS BATCH (unique: its atomicOr
@@ -385,25 +376,17 @@ __global__ __launch_bounds__(kPrepThreads) void k_prepare(
     float m = 0.0f, lo = 3.0e38f;
     for (int w = 0; w < kPrepThreads / 64; w++) m = fmaxf(m, s_wmax[w]);
     for (int e = 0; e < kLoSub * kLoSub * (kPrepThreads / 64); e++) lo = fminf(lo, (&s_wlo[0][0][0])[e]);
-#if ER_TILE_FRAME_FASTEST
     const size_t t = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * ER_MAX_BATCH + f;      // [tile][frame]: see k_integrate's culling
-#else
-    const size_t t = ((size_t)f * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-#endif
     tile_max[t] = m;
     tile_lo[t] = lo;                                      // the 32-pixel minimum: first level of the full verdict
   }
-  if (kLoShift < 5 && (int)threadIdx.x < kLoSub * kLoSub) {
+  if ((int)threadIdx.x < kLoSub * kLoSub) {
     const int sr = threadIdx.x / kLoSub, sg = threadIdx.x % kLoSub;
     float lo = 3.0e38f;
     for (int w = 0; w < kPrepThreads / 64; w++) lo = fminf(lo, s_wlo[sr][sg][w]);
     const int lx = blockIdx.x * kLoSub + sg, ly = blockIdx.y * kLoSub + sr;
     const int lo_tx = (cols + (1 << kLoShift) - 1) >> kLoShift, lo_ty = (rows + (1 << kLoShift) - 1) >> kLoShift;
-#if ER_TILE_FRAME_FASTEST
     if (lx < lo_tx && ly < lo_ty) tile_lo_fine[((size_t)ly * lo_tx + lx) * ER_MAX_BATCH + f] = lo;
-#else
-    if (lx < lo_tx && ly < lo_ty) tile_lo_fine[((size_t)f * lo_ty + ly) * lo_tx + lx] = lo;
-#endif
   }
   const int n = min(s_n, kTileKeys);
   if ((int)threadIdx.x < n) {
@@ -518,15 +501,9 @@ __global__ __launch_bounds__(256) void k_plan(const int* __restrict__ batch, con
 // the frame constants arrive by scalar loads) -- per voxel exactly the reference's frame-by-frame sequence.
 // Items come from ONE global work queue in cost order (k_plan), claimed when the workgroup is free.  (Static deals, per-XCD queues and look-ahead
 // claims were all measured slower: profiles/HISTORY.md "Path A: the schedule of k_integrate".)
-#ifndef ER_INT_LANE_SHAPE
-#define ER_INT_LANE_SHAPE 1              // lanes of a wave of k_integrate: 1 = 2 x 4 x 8 voxels (ships), 0 = 1 x 8 x 8 (rounds 2-5)
-#endif
-#ifndef ER_INT_MIN_BLOCKS
-#define ER_INT_MIN_BLOCKS 5
-#endif
-constexpr int kIntMinBlocks = ER_INT_MIN_BLOCKS;          // register budget handed to the compiler: 5 workgroups of 4 waves per CU = 102 VGPRs (the kernel uses 93 with 3, 4
+constexpr int kIntMinBlocks = 5;                          // register budget handed to the compiler: 5 workgroups of 4 waves per CU = 102 VGPRs (the kernel uses 93 with 3, 4
                                           // or 5; with 6 it spills).  Same instructions, another register assignment: +1.0 % on the job against 4, five
-                                          // interleaved runs out of five (profiles/r06v_ab_min_blocks.txt).  The grid launches ER_INT_BLOCKS_PER_CU = 3
+                                          // interleaved runs out of five (profiles/r06v_ab_min_blocks.txt).  The grid launches kIntBlocksPerCu = 3
                                           // workgroups per CU -- the free registers go to the co-running pre-pass kernels
 // kSure: the square-root-free "sure" path of the frame loop (voxel_classify needs dp < 64 m; the host picks the instantiation
 // from integration_trunc, which bounds every scaled depth).
@@ -549,9 +526,6 @@ __global__ __launch_bounds__(kBlock, kIntMinBlocks) void k_integrate(
   const int wave = threadIdx.x >> 6;
   const int pixels = cols * rows;
   const int lo_tiles_x = (cols + (1 << kLoShift) - 1) >> kLoShift;
-#if !ER_TILE_FRAME_FASTEST
-  const int lo_tiles = lo_tiles_x * ((rows + (1 << kLoShift) - 1) >> kLoShift);
-#endif
   const int n_items = plan->n_units * kItemsPerUnit;
   // Work queue: the items are sorted by descending cost (k_plan) and every workgroup claims the next one when it is done with its own (one atomic per
   // item and workgroup; 3 persistent workgroups per CU): longest-processing-time-first.  The culling and the full / sure shortcuts make the real cost of
@@ -570,23 +544,14 @@ __global__ __launch_bounds__(kBlock, kIntMinBlocks) void k_integrate(
     // (i = i0 + il + 2 r); the workgroup's item = 8 x 8 x 16 voxels (waves: 2 along j, 2 along k).  Why this shape: a depth gather costs the vector L1
     // ~0.6 clocks per DISTINCT address (profiles/r06y_gather_rates.txt) and k_integrate lives on its gathers (every gather issued twice: -19 % frames/s,
     // profiles/r06z_ab_lane_shape.txt); the 64 voxels of an 8 x 8 plane -- rounds 2-5: lanes = one slab, rows = 4 slabs -- project onto 64 distinct pixels
-    // seen face-on, a 2 x 4 x 8 block onto fewer from every direction.  +4 % on the job against the 1 x 8 x 8 lanes (ER_INT_LANE_SHAPE 0, kept for that
-    // comparison); 4 x 4 x 4, 2 x 8 x 4, 2 x 2 x 16, 4 x 2 x 8, 1 x 4 x 16 lanes and two other item shapes measured behind it.  A compact box keeps a tight
+    // seen face-on, a 2 x 4 x 8 block onto fewer from every direction.  +4 % on the job against the 1 x 8 x 8 lanes; 4 x 4 x 4, 2 x 8 x 4, 2 x 2 x 16, 4 x 2 x 8, 1 x 4 x 16 lanes and two other item shapes measured behind it.  A compact box keeps a tight
     // pixel hull (culling, the "inside" verdict), few idle lanes at surfaces and frustum borders and few patches that cross a surface; four rows per lane
     // keep the longest items short and the kernel at 93 VGPRs.  Voxel accesses: eight 8-byte voxels = one 64-byte segment per (il, jl).
-#if ER_INT_LANE_SHAPE == 0
-    const int ilane = 0;
-    const int i = ((item >> 4) & 15) * 4;
-    const int j0 = ((item >> 2) & 3) * 16 + (wave >> 1) * 8;
-    const int jlane = lane >> 3, k0 = (item & 3) * 16 + (wave & 1) * 8, klane = lane & 7;
-    constexpr int jspan = 8, kspan = 8, ispan = kRows, istep = 1;
-#else
     const int ilane = lane >> 5;
     const int i = ((item >> 5) & 7) * 8 + ilane;
     const int j0 = ((item >> 2) & 7) * 8 + (wave >> 1) * 4;
     const int jlane = (lane >> 3) & 3, k0 = (item & 3) * 16 + (wave & 1) * 8, klane = lane & 7;
     constexpr int jspan = 4, kspan = 8, ispan = 2 * kRows, istep = 2;
-#endif
     const int ibox = i - ilane;                                          // (wave-uniform: the box's first slab)
     const int key = rec.key, slot = rec.slot;
     if (slot < 0) continue;                                             // pool overflow: reported by the host
@@ -617,7 +582,6 @@ __global__ __launch_bounds__(kBlock, kIntMinBlocks) void k_integrate(
     unsigned long long m_in, m_full;
     {
       bool keep = ((m >> lane) & 1ull) != 0ull, inside = false, full = false;
-#if ER_FRAMES_TRANSPOSED
       // lane f tests frame f: its 16 constants come from the component-major copy behind frames[] (Staging::fxT) -- 64 lanes x 4 consecutive bytes per
       // load where frames[lane] is one 64-byte line per lane
       FrameXform fl;
@@ -630,22 +594,13 @@ __global__ __launch_bounds__(kBlock, kIntMinBlocks) void k_integrate(
         fl.tz = fT[14 * ER_MAX_BATCH];
         fl.pad = 0.f;
       }
-#else
-      const FrameXform& fl = frames[lane];
-#endif
       if (keep)
         keep = patch_may_update_box(grid_coord(ibox, xs), grid_coord(ibox + ispan - 1, xs), grid_coord(j0, ys), grid_coord(j0 + jspan - 1, ys),
                                     grid_coord(k0, zs), grid_coord(k0 + kspan - 1, zs), fl, cam, cols, rows,
-#if ER_TILE_FRAME_FASTEST
                                     // tiles FRAME-fastest: lane f of this test is frame f, and consecutive frames of a sweep see the box under the
                                     // same tiles -- 64 lanes x 4 consecutive bytes per load instead of 64 lines 1.2 KB apart
-                                    tile_max + lane, tiles_x, tiles_y, &inside, tile_lo + lane, &full, kLoShift, lo_tiles_x,
-                                    kLoShift < 5 ? tile_lo_fine + lane : (const float*)nullptr, ER_MAX_BATCH);
-#else
-                                    tile_max + (size_t)lane * tiles_x * tiles_y, tiles_x, tiles_y, &inside,
-                                    tile_lo + (size_t)lane * tiles_x * tiles_y, &full, kLoShift, lo_tiles_x,
-                                    kLoShift < 5 ? tile_lo_fine + (size_t)lane * lo_tiles : (const float*)nullptr);
-#endif
+                                    tile_max + lane, tiles_x, tiles_y, &inside, tile_lo + lane, &full, kLoShift, lo_tiles_x, tile_lo_fine + lane,
+                                    ER_MAX_BATCH);
       m = __ballot(keep);
       m_in = __ballot(keep && inside);
       m_full = __ballot(keep && full);
@@ -1499,10 +1454,7 @@ int run_batch(er_tsdf_t h, int n, const uint16_t* depth_dev, const double* T, co
   hipStream_t X = h->aux_stream[a], S = h->stream;
   int* nbatch = h->counters + kNbatchSlot[p];
 
-#ifndef ER_INT_BLOCKS_PER_CU
-#define ER_INT_BLOCKS_PER_CU 3
-#endif
-  constexpr int kIntBlocksPerCu = ER_INT_BLOCKS_PER_CU;       // persistent workgroups fed by the queue.  Fewer than fit: the pre-pass kernels need register
+  constexpr int kIntBlocksPerCu = 3;                          // persistent workgroups fed by the queue.  Fewer than fit: the pre-pass kernels need register
                                            // space next to them (2 -> 172.0 k, 3 -> 174.3 k, 4 -> 170.0 k, 5 -> 169.6 k frames/s, profiles/r05n_*)
   const int wide_grid = h->n_cu * kIntBlocksPerCu;
   uint32_t* zsrc = nullptr;
@@ -2201,7 +2153,7 @@ int er_tsdf_import_raw(er_tsdf_t h, const int* keys_host, int n_keys, const floa
   return import_units(h, keys_host, n_keys, dev_buf, 1, "er_tsdf_import_raw");
 }
 
-// ---- band records behind the C ABI (the device half of er_merge_protocol.h's OwnerMergeVolume) ------------------------------------------------
+// ---- band records behind the C ABI (the device half of er_merge_protocol.h's MergeVolume) -----------------------------------------------------
 // chunk counts of the given units -> host: obs[n], band[n], wide[n]; the device copies stay in the band scratch ([counts n x 256 | wide n | offsets n]).
 static int band_unit_counts(er_tsdf_t h, const int* keys_host, int n, std::vector<int>& obs, std::vector<int>& band, std::vector<int>& wide, const char* who) {
   if (resolve_slots(h, keys_host, n, false)) return 1;

@@ -611,9 +611,6 @@ ER_HD void lattice_vertex(const float* __restrict__ ctr, unsigned byte_off, floa
 // seg: rows 0..2 of the float64 4x4 followed by the three rounding bounds of cube_coords (15 doubles used, stride 16);
 // madj: rows 0..2 (12 doubles).  ctr: one grid, (res+1)^3 * 3 floats.
 // On success returns true and the target cell (row-major pixel index) plus the 16-bit depth dd.
-#ifndef ER_LATTICE_SCALAR
-#define ER_LATTICE_SCALAR 1     // reproject_px on the device: the lattice cell's eight vertices through the scalar cache when the wave lies in one cell
-#endif
 template <typename Lattice>
 ER_HD bool reproject_px(int u, int v, uint16_t d, const Camera& c, const CameraInv& ci, int cols, int rows, const double* seg,
                         const double* madj, const Lattice* __restrict__ ctr, int res, float grid_ul, int& cell, uint16_t& dd,
@@ -647,7 +644,7 @@ ER_HD bool reproject_px(int u, int v, uint16_t d, const Camera& c, const CameraI
                      base + vs, base + vs + s2, base + vs + s1, base + vs + s1 + s2};
   // ControlGrid::GetPosition, ControlGrid.h:82-87: left-to-right float32 sum
   float pos[3], vt[3];
-#if defined(__HIP_DEVICE_COMPILE__) && ER_LATTICE_SCALAR
+#if defined(__HIP_DEVICE_COMPILE__)
   // The 64 pixels of a wave nearly always lie in ONE lattice cell (a cell is 37.5 cm wide): then the eight vertices are the same for every lane and come
   // through the scalar cache (a wave-uniform offset makes the loads scalar) instead of eight 12-byte gathers from the vector L1.  Same values, same sums.
   {
@@ -679,7 +676,7 @@ ER_HD bool reproject_px(int u, int v, uint16_t d, const Camera& c, const CameraI
     pos[1] = pos[1] + val[t] * vt[1];
     pos[2] = pos[2] + val[t] * vt[2];
   }
-#if defined(__HIP_DEVICE_COMPILE__) && ER_LATTICE_SCALAR
+#if defined(__HIP_DEVICE_COMPILE__)
 blended:
 #endif
   double pa = (double)pos[0], pb = (double)pos[1], pc = (double)pos[2];

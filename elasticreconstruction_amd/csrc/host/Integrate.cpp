@@ -449,10 +449,6 @@ int main(int argc, char* argv[]) {
   if (gpus < 1) gpus = 1;
   if (shard != "frame" && shard != "unit") { fprintf(stderr, "Integrate: --shard must be frame or unit\n"); return 1; }
   if (merge_root != ER_MERGE_DISTRIBUTED && (merge_root < 0 || merge_root >= gpus)) { fprintf(stderr, "Integrate: --merge_root must name one of the %d workers\n", gpus); return 1; }
-  {
-    const char* impl = getenv("ER_MERGE_IMPL");                          // round 5's ring protocol cannot leave the result distributed
-    if (impl && std::string(impl) == "ring" && merge_root == ER_MERGE_DISTRIBUTED) merge_root = 0;
-  }
   const bool unit_shard = shard == "unit";
   if (same_device && !unit_shard && gpus > 16) { fprintf(stderr, "Integrate: --same_device --shard frame takes at most 16 workers\n"); return 1; }
   if (!same_device && gpus > 1 && er_device_count() > 0 && app.device_ + gpus > er_device_count()) {

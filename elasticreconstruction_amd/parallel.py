@@ -7,14 +7,15 @@
                    all-gather of the touched unit keys -> union, ONE reduce(sum) to rank 0 (or all-reduce) over
                    the [key][sdf*weight | weight] planes of the union, per-voxel divide on import.
                    (Since round 5 only the units two or more ranks touched go through the sum; a unit one rank touched travels raw,
-                   bit for bit, from its owner to where the result is wanted: csrc/er_merge_protocol.h -- er_tsdf_allreduce behind
-                   AbiComm is the product path, merge_volumes below the torch.distributed cross-check of the same protocol.)
+                   bit for bit, from its owner to where the result is wanted.)  This is merge_volumes below: a separate
+                   torch.distributed cross-check that sums whole planes.  The product path is er_tsdf_allreduce behind AbiComm, a
+                   different protocol since round 6 (the owner merge of csrc/er_merge_protocol.h: band records, rank-ordered sums).
                    (The running mean with unit weights is a sum: w = sum_g w_g, sdf = sum_g sdf_g*w_g / w;
                    TSDFVolume.cpp:93-94 applied sequentially gives the same value up to float rounding
                    order, hence tolerance 1e-5 instead of bit parity for this mode.)
 
 The functions only need an object with unit_keys() / export_weighted(keys, ptr) / import_weighted(keys, ptr) / export_raw(keys, ptr) /
-import_raw(keys, ptr) / synchronize(), so the CPU tests can drive the identical protocol over gloo with a host-memory volume.
+import_raw(keys, ptr) / synchronize(), so the CPU tests can drive the same functions over gloo with a host-memory volume.
 """
 import numpy as np
 
@@ -46,7 +47,7 @@ def _agree_max(values, dist, device):
 def gather_keys(local_keys, dist, device, status=0):
     """Every rank's touched unit keys on every rank: the ranks first AGREE on the padded length -- one all_reduce(MAX) of {key count, status} --
     then exchange the keys in ONE fixed-size all-gather (padded with -1), so every rank issues the same collectives with the same shapes
-    whatever it touched (csrc/er_merge_protocol.h, steps 2-3).  status != 0 on any rank makes every rank raise MergeError after the first
+    whatever it touched.  status != 0 on any rank makes every rank raise MergeError after the first
     collective.  Returns [sorted int32 numpy array of rank q's keys for q in range(world)]."""
     import torch
     world = dist.get_world_size()
@@ -76,7 +77,7 @@ def union_keys(local_keys, dist, device, status=0):
 
 
 def merge_plan(per_rank_keys, rank, root):
-    """Who touched what (csrc/er_merge_protocol.h step 3, the same arithmetic): (union, multi, send, recv) with multi = the keys two or more ranks
+    """Who touched what: (union, multi, send, recv) with multi = the keys two or more ranks
     touched (they go through the sum), send = this rank's single-toucher keys that have to travel (to `root`, or to everybody for root < 0),
     recv = {owner: keys} of the single-toucher units that arrive here.  All arrays sorted."""
     world = len(per_rank_keys)
@@ -98,8 +99,8 @@ def merge_plan(per_rank_keys, rank, root):
 
 
 def merge_volumes(vol, dist, device, sync_stream=None, mode="reduce", root=0):
-    """Frame-split merge over torch.distributed -- the cross-check of the product path (er_tsdf_allreduce, same protocol:
-    csrc/er_merge_protocol.h, since round 5 including its sparse data path).  mode "reduce" (default): ONE reduce(sum) to `root` over the
+    """Frame-split merge over torch.distributed -- a separate cross-check of the product path (er_tsdf_allreduce, whose owner merge
+    exchanges band records and sums in rank order): this one sums whole planes.  mode "reduce" (default): ONE reduce(sum) to `root` over the
     [key][sdf*weight | weight] planes of the units TWO OR MORE ranks touched -- the "final reduce of per-GPU TSDF volume-unit weights" of
     BASELINE.json -- and one send per owner of the units only ONE rank touched, raw, bit for bit; afterwards `root` holds the complete volume
     (the other ranks keep their partial volumes).  mode "all_reduce": an all-reduce and one broadcast per owner; every rank ends with the
@@ -213,11 +214,10 @@ def _merge_stats(lib, handle):
     out = {n: int(v) for n, v in zip(names, st)}
     so = (C.c_longlong * 12)()
     _ffi.check(lib.er_comm_merge_stats_owner(handle, so), "er_comm_merge_stats_owner")
-    out["impl"] = "owner" if so[0] == 1 else "ring"
-    if so[0] == 1:
-        out.update({"units_owned": int(so[4]), "units_summed_here": int(so[5]), "units_handed_over": int(so[6]),
-                    "to_owners_bytes_sent": int(so[7]), "to_owners_bytes_received": int(so[8]),
-                    "to_root_bytes_sent": int(so[9]), "to_root_bytes_received": int(so[10]), "ring_equivalent_bytes": int(so[11])})
+    out["impl"] = "owner"
+    out.update({"units_owned": int(so[4]), "units_summed_here": int(so[5]), "units_handed_over": int(so[6]),
+                "to_owners_bytes_sent": int(so[7]), "to_owners_bytes_received": int(so[8]),
+                "to_root_bytes_sent": int(so[9]), "to_root_bytes_received": int(so[10]), "ring_equivalent_bytes": int(so[11])})
     return out
 
 

@@ -193,7 +193,7 @@ int er_unit_owner(int key, int world);          /* (xi + yi + zi) mod world: dia
  *                                        communicator (ncclCommInitRank; collective: all ranks must call it);
  *   er_comm_create_local                 ONE process, n GPUs, one host thread per GPU afterwards (ncclCommInitAll).
  * er_tsdf_allreduce merges the private volumes of the ranks after each integrated its own contiguous frame block
- * (er_frame_block).  Every rank calls it once.  Since round 6 it is the OWNER MERGE (csrc/er_merge_protocol.h: merge_protocol_owner), a
+ * (er_frame_block).  Every rank calls it once.  It is the OWNER MERGE (round 6; csrc/er_merge_protocol.h: merge_protocol_owner), a
  * reduce-scatter by volume unit:
  *   agree on the key count; all-gather the touched unit keys with their observed-voxel counts -- every rank then knows who touched what and how
  *   much; every unit of the union gets an OWNER, the toucher that observed most of it; every other toucher sends the owner a band record of
@@ -205,12 +205,12 @@ int er_unit_owner(int key, int world);          /* (xi + yi + zi) mod world: dia
  * TSDFVolume.cpp:104-132: bin/Integrate --gpus N concatenates the ranks' extractions by key).  root >= 0: the owners then send their finished
  * units, as band records, to `root` in a second grouped step; root == ER_MERGE_ALL (-1): to every other rank.  Units only ONE rank touched are
  * that rank's: they stay where they are (distributed) or travel bit for bit (records restore a unit exactly).
- * ER_MERGE_IMPL=ring in the environment of EVERY rank selects round 5's protocol instead (ONE ncclReduce / ncclAllReduce over whole
- * [sdf*weight | weight] planes of the units two or more ranks touched, summed in RCCL's order; raw point-to-point for the others; root >= 0 or -1 only).
+ * A communicator of more than 17 ranks is refused (an owner adds the records of at most 16 other touchers).  Round 5's ring reduction of whole
+ * planes is gone; ER_MERGE_IMPL, which selected it, is no longer read.
  * union_units (nullable) receives the size of the key union; er_comm_merge_stats what the last merge of this communicator moved: stats[0] union,
- * [1] multi-toucher units, [2] single-toucher units, [3] units this rank sent (owner merge: handed over), [4] units this rank received (owner merge:
- * summed here), [5] bytes handed to a reduction collective (owner merge: 0), [6] bytes this rank sent, [7] bytes received.  er_comm_merge_stats_owner:
- * [0] protocol of the last merge (0 ring, 1 owner), [1] union, [2] multi-toucher, [3] single-toucher, [4] units this rank owns afterwards, [5] of
+ * [1] multi-toucher units, [2] single-toucher units, [3] units this rank handed over, [4] units this rank summed, [5] bytes handed to a
+ * reduction collective (always 0: the slot of round 5's ring reduction), [6] bytes this rank sent, [7] bytes received.  er_comm_merge_stats_owner:
+ * [0] protocol of the last merge (always 1, the owner merge), [1] union, [2] multi-toucher, [3] single-toucher, [4] units this rank owns afterwards, [5] of
  * which it summed, [6] units it handed over, [7] / [8] bytes sent / received in the step to the owners, [9] / [10] in the step to the root /
  * everybody, [11] bytes round 5's ring reduction would have been handed for the same key sets (2 MiB per multi-toucher unit). */
 typedef struct er_comm_s* er_comm_t;
@@ -219,8 +219,7 @@ int er_comm_unique_id(unsigned char id[ER_COMM_ID_BYTES]);
 int er_comm_create(const unsigned char id[ER_COMM_ID_BYTES], int rank, int world, int device, er_comm_t* out);
 int er_comm_create_local(int n, const int* devices, er_comm_t* out /* n handles */);
 /* n <= 16 ranks = n host threads of this process, ALL on one device, no RCCL: the same merge protocol over the same device volumes and
- * export / import kernels, the sum reduction as a kernel that adds the ranks' plane buffers in rank order, the point-to-point step as
- * device-to-device copies.  For boxes with one GPU (RCCL refuses two ranks on one device): `Integrate --gpus N --same_device`, tests. */
+ * band-record kernels, the point-to-point steps as device-to-device copies.  For boxes with one GPU (RCCL refuses two ranks on one device): `Integrate --gpus N --same_device`, tests. */
 int er_comm_create_loopback(int n, int device, er_comm_t* out /* n handles */);
 int er_comm_destroy(er_comm_t c);
 int er_comm_rank(er_comm_t c);

@@ -124,17 +124,16 @@ def band_record_bytes(words):
     return 4 * int(words)
 
 
-def check_frame_split_merge(make_comms, devices, root, impl="owner", per=100, max_units=2048, repeat=1):
+def check_frame_split_merge(make_comms, devices, root, per=100, max_units=2048, repeat=1):
     """len(devices) ranks integrate their blocks into volumes of their own, er_tsdf_allreduce merges them (root >= 0, -1 = on every rank, -2 = left
     distributed), and the result is compared with ONE volume that integrated the same blocks in order:
       * key sets: the union, nothing lost, (distributed) every unit on exactly one rank -- a toucher that observed most of it;
       * units one rank touched: BIT-IDENTICAL to the single volume (no frame of another rank ever reached them);
-      * units two or more ranks touched: weights exact, sdf within 1e-5 of the single volume (TSDFVolume.cpp:93-94 summed in another order) and, for the
-        owner merge, BIT-IDENTICAL to the float32 sum of the ranks' volumes in rank order (numpy restatement): the order is a function of the key sets;
+      * units two or more ranks touched: weights exact, sdf within 1e-5 of the single volume (TSDFVolume.cpp:93-94 summed in another order) and
+        BIT-IDENTICAL to the float32 sum of the ranks' volumes in rank order (numpy restatement): the order is a function of the key sets;
       * er_comm_merge_stats / _owner equal to the key-set and band arithmetic; what crosses the transport is records, not planes;
       * repeat > 1: the merge is run again from scratch and must give the same bits (bit-reproducibility at N > 1).
     Returns a summary dict."""
-    import os
     import numpy as np
     import torch
     from elasticreconstruction_amd import parallel
@@ -148,8 +147,6 @@ def check_frame_split_merge(make_comms, devices, root, impl="owner", per=100, ma
         full.IntegrateFrames(None, sc["traj"], w, device_ptr=depth.data_ptr())
         full.synchronize()
     full_keys = [int(k) for k in full.unit_keys()]
-    old = os.environ.get("ER_MERGE_IMPL")
-    os.environ["ER_MERGE_IMPL"] = impl
     summary, previous = {}, None
     try:
         for rep in range(repeat):
@@ -185,44 +182,34 @@ def check_frame_split_merge(make_comms, devices, root, impl="owner", per=100, ma
                     W = W + w1
                 with np.errstate(divide="ignore", invalid="ignore"):
                     return np.where(W > 0, SW / W, np.float32(0)).astype(np.float32), W
-            if impl == "owner":
+            for r in range(G):
+                assert st[r]["impl"] == "owner" and st[r]["bytes_reduced"] == 0
+                assert (st[r]["union_units"], st[r]["multi_toucher_units"], st[r]["single_toucher_units"]) == (len(touch), len(multi), len(single))
+                assert st[r]["ring_equivalent_bytes"] == len(multi) * 2 * 64 ** 3 * 4
+            # the owners, read off the distributed result or recomputed: a toucher with the largest band
+            best = {k: max(count[(k, r)] for r in touch[k]) for k in multi}
+            if root == parallel.MERGE_DISTRIBUTED:
+                owner = {}
+                for k in touch:
+                    holders = [r for r in range(G) if k in have[r]]
+                    assert len(holders) == 1, "unit %d lives on ranks %s after a distributed merge" % (k, holders)
+                    owner[k] = holders[0]
+                    assert owner[k] in touch[k] and (len(touch[k]) == 1 or count[(k, owner[k])] == best[k])
+                to_owner = sum(band_record_bytes(count[(k, r)]) for k in multi for r in touch[k] if r != owner[k])
+                assert sum(s["to_owners_bytes_sent"] for s in st) == to_owner == sum(s["to_owners_bytes_received"] for s in st)
+                assert sum(s["to_root_bytes_sent"] for s in st) == 0
                 for r in range(G):
-                    assert st[r]["impl"] == "owner" and st[r]["bytes_reduced"] == 0
-                    assert (st[r]["union_units"], st[r]["multi_toucher_units"], st[r]["single_toucher_units"]) == (len(touch), len(multi), len(single))
-                    assert st[r]["ring_equivalent_bytes"] == len(multi) * 2 * 64 ** 3 * 4
-                # the owners, read off the distributed result or recomputed: a toucher with the largest band
-                best = {k: max(count[(k, r)] for r in touch[k]) for k in multi}
-                if root == parallel.MERGE_DISTRIBUTED:
-                    owner = {}
-                    for k in touch:
-                        holders = [r for r in range(G) if k in have[r]]
-                        assert len(holders) == 1, "unit %d lives on ranks %s after a distributed merge" % (k, holders)
-                        owner[k] = holders[0]
-                        assert owner[k] in touch[k] and (len(touch[k]) == 1 or count[(k, owner[k])] == best[k])
-                    to_owner = sum(band_record_bytes(count[(k, r)]) for k in multi for r in touch[k] if r != owner[k])
-                    assert sum(s["to_owners_bytes_sent"] for s in st) == to_owner == sum(s["to_owners_bytes_received"] for s in st)
-                    assert sum(s["to_root_bytes_sent"] for s in st) == 0
-                    for r in range(G):
-                        assert st[r]["units_owned"] == len(have[r]) and st[r]["units_summed_here"] == len([k for k in multi if owner[k] == r])
-                        assert st[r]["units_handed_over"] == len([k for k in multi if r in touch[k] and owner[k] != r])
-                    summary["to_owners_MB"] = to_owner / 1e6
-                else:
-                    to_owner = sum(s["to_owners_bytes_sent"] for s in st)
-                    lo = sum(band_record_bytes(count[(k, r)]) for k in multi for r in touch[k]) - sum(band_record_bytes(best[k]) for k in multi)
-                    assert to_owner == lo == sum(s["to_owners_bytes_received"] for s in st)
-                    assert sum(s["to_root_bytes_sent"] for s in st) > 0
-                    assert sum(s["to_root_bytes_received"] for s in st) == sum(s["to_root_bytes_sent"] for s in st)      # (sent counts every receiver)
-                summary["ring_equivalent_MB"] = st[0]["ring_equivalent_bytes"] / 1e6
-                summary["moved_MB"] = sum(s["bytes_sent"] for s in st) / 1e6
+                    assert st[r]["units_owned"] == len(have[r]) and st[r]["units_summed_here"] == len([k for k in multi if owner[k] == r])
+                    assert st[r]["units_handed_over"] == len([k for k in multi if r in touch[k] and owner[k] != r])
+                summary["to_owners_MB"] = to_owner / 1e6
             else:
-                unit_bytes = 2 * 64 ** 3 * 4
-                for r in range(G):
-                    assert st[r]["impl"] == "ring" and st[r]["bytes_reduced"] == len(multi) * unit_bytes
-                    mine = [k for k in single if touch[k] == [r]]
-                    travels = (lambda k: True) if root < 0 else (lambda k: touch[k] != [root])
-                    assert st[r]["units_sent"] == len([k for k in mine if travels(k)])
-                    want_recv = len([k for k in single if touch[k] != [r]]) if (root < 0 or r == root) else 0
-                    assert st[r]["units_received"] == want_recv and st[r]["bytes_received"] == want_recv * unit_bytes
+                to_owner = sum(s["to_owners_bytes_sent"] for s in st)
+                lo = sum(band_record_bytes(count[(k, r)]) for k in multi for r in touch[k]) - sum(band_record_bytes(best[k]) for k in multi)
+                assert to_owner == lo == sum(s["to_owners_bytes_received"] for s in st)
+                assert sum(s["to_root_bytes_sent"] for s in st) > 0
+                assert sum(s["to_root_bytes_received"] for s in st) == sum(s["to_root_bytes_sent"] for s in st)      # (sent counts every receiver)
+            summary["ring_equivalent_MB"] = st[0]["ring_equivalent_bytes"] / 1e6
+            summary["moved_MB"] = sum(s["bytes_sent"] for s in st) / 1e6
             receivers = list(range(G)) if root == parallel.MERGE_ALL else ([root] if root >= 0 else [])
             for r in receivers:
                 assert sorted(have[r]) == full_keys, "rank %d misses units after the merge" % r
@@ -230,10 +217,8 @@ def check_frame_split_merge(make_comms, devices, root, impl="owner", per=100, ma
             worst, bits = 0.0, {}
             for r in range(G):
                 for k in sorted(have[r]):
-                    if root >= 0 and r != root and impl == "owner" and k not in before[r]:
+                    if root >= 0 and r != root and k not in before[r]:
                         continue
-                    if root >= 0 and r != root and impl != "owner":
-                        continue                                  # (ring: the other ranks keep their partial volumes)
                     sm, wm = vols[r].read_unit(k)
                     sf, wf = full.read_unit(k)
                     if len(touch[k]) == 1:
@@ -243,9 +228,8 @@ def check_frame_split_merge(make_comms, devices, root, impl="owner", per=100, ma
                     else:
                         assert np.array_equal(wf, wm), "merged weights differ in unit %d" % k
                         worst = max(worst, float(np.abs(sf - sm).max()))
-                        if impl == "owner":
-                            es, ew = rank_sum(k)
-                            assert np.array_equal(ew, wm) and np.array_equal(es.view(np.uint32), sm.view(np.uint32)), "unit %d is not the rank-ordered float32 sum (rank %d)" % (k, r)
+                        es, ew = rank_sum(k)
+                        assert np.array_equal(ew, wm) and np.array_equal(es.view(np.uint32), sm.view(np.uint32)), "unit %d is not the rank-ordered float32 sum (rank %d)" % (k, r)
                     if len(touch[k]) > 1:
                         bits.setdefault(k, sm.view(np.uint32).copy())
                         assert np.array_equal(bits[k], sm.view(np.uint32)), "unit %d differs between ranks" % k
@@ -253,14 +237,10 @@ def check_frame_split_merge(make_comms, devices, root, impl="owner", per=100, ma
             if previous is not None:
                 assert sorted(previous) == sorted(bits) and all(np.array_equal(previous[k], bits[k]) for k in bits), "the merge is not bit-reproducible"
             previous = bits
-            summary.update({"union": len(touch), "multi": len(multi), "single": len(single), "max_abs_dsdf": worst, "root": root, "impl": impl, "ranks": G})
+            summary.update({"union": len(touch), "multi": len(multi), "single": len(single), "max_abs_dsdf": worst, "root": root, "ranks": G})
             comms.close()
             for v in vols:
                 v.close()
     finally:
-        if old is None:
-            os.environ.pop("ER_MERGE_IMPL", None)
-        else:
-            os.environ["ER_MERGE_IMPL"] = old
         full.close()
     return summary

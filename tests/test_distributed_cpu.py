@@ -183,9 +183,9 @@ def test_c_abi_shard_helpers_match_the_python_protocol():
         assert cnt.max() - cnt.min() <= 64
 
 
-def test_c_merge_protocol_world_1_2_3_on_threads(tmp_path):
-    """The protocol of er_tsdf_allreduce (csrc/er_merge_protocol.h -- the very header er_multi.hip runs over RCCL) on host
-    threads with a shared-memory transport, world = 1 / 2 / 3: uneven key counts, empty ranks, root 0 / 1 / 2 / all-reduce, and
+def test_c_owner_merge_protocol_world_1_2_3_on_threads(tmp_path):
+    """The owner merge of er_tsdf_allreduce (csrc/er_merge_protocol.h -- the very header er_multi.hip runs over RCCL) on host
+    threads with a shared-memory transport, world = 1 / 2 / 3: uneven key counts, empty ranks, root 0 / 1 / 2 / all / distributed, and
     the collective-failure rule (a rank whose unit pool overflowed or whose export failed makes EVERY rank return an error after
     the same collective -- no rank is left waiting; the timeout is the hang detector).  Also under ThreadSanitizer when g++ has it."""
     import subprocess

@@ -329,7 +329,7 @@ def integrate_multi_gpu_case(d, gpus_args, same_device):
     tests/test_distributed_gpu.py with real devices):
        * --shard frame (default): frame blocks per worker, er_tsdf_allreduce leaves the merged volume DISTRIBUTED by unit owner (round 6), world.pcd is
          assembled from the owners' extractions in ascending key order: the same points within 1e-5;
-       * --merge_root 0: the same merge gathered on the first GPU before SaveWorld; ER_MERGE_IMPL=ring: round 5's protocol -- all the same points;
+       * --merge_root 0: the same merge gathered on the first GPU before SaveWorld -- the same points;
        * --shard unit: every worker is fed every frame and owns a third of the units, no collective: world.pcd BYTE-identical to the single-GPU one."""
     sc = synth.make_scenario(12, interval=4, warp=True, amplitude=0.004, seed=21)
     depth = synth.to_numpy_u16(sc["depth"])
@@ -338,9 +338,8 @@ def integrate_multi_gpu_case(d, gpus_args, same_device):
             "--length", "3.0", "--interval", "4", "-oni", "frames.raw", "--max_units", "512"]
     sd = ["--same_device"] if same_device else []
 
-    def run(extra, out, env=None):
-        r = subprocess.run([os.path.join(BIN, "Integrate")] + args + extra + ["--save_to", out], cwd=d, capture_output=True, text=True, timeout=300,
-                           env=dict(os.environ, **(env or {})))
+    def run(extra, out):
+        r = subprocess.run([os.path.join(BIN, "Integrate")] + args + extra + ["--save_to", out], cwd=d, capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stdout + r.stderr
         p = formats.load_pcd(os.path.join(d, out))
         return np.stack([p["x"], p["y"], p["z"], p["intensity"]], 1), r
@@ -359,8 +358,6 @@ def integrate_multi_gpu_case(d, gpus_args, same_device):
     assert "gathered on GPU 0" in r.stderr, r.stderr
     _same_world(a, sorted_points(rooted))
     assert np.array_equal(sorted_points(rooted).view(np.uint32), sorted_points(looped).view(np.uint32)), "gathered and distributed results differ"
-    ring, r = run(gpus_args + sd + ["--merge_root", "0"], "wg.pcd", env={"ER_MERGE_IMPL": "ring"})
-    _same_world(a, sorted_points(ring))
     sharded, _ = run(gpus_args + ["--shard", "unit"] + sd, "wu.pcd")
     assert np.array_equal(one.view(np.uint32), sharded.view(np.uint32)), "unit-shard world.pcd differs from the single-GPU one"
     with open(os.path.join(d, "w1.pcd"), "rb") as f1, open(os.path.join(d, "wu.pcd"), "rb") as f2:
@@ -398,7 +395,7 @@ def build_correspondence_multi_gpu_case(d, gpus):
 def test_abi_allreduce_on_a_one_rank_communicator_is_the_identity(gpu):
     """er_tsdf_allreduce through RCCL with ONE rank (RCCL refuses two ranks on one GPU, and this box has one): export ->
     all-reduce -> import must be the identity up to re-rounding, and er_frame_block must tile.  The protocol with world = 2 / 3
-    runs on the CPU: tests/test_distributed_cpu.py::test_c_merge_protocol_world_1_2_3_on_threads (the same header)."""
+    runs on the CPU: tests/test_distributed_cpu.py::test_c_owner_merge_protocol_world_1_2_3_on_threads (the same header)."""
     import ctypes as C
     from elasticreconstruction_amd import _ffi, parallel
     from elasticreconstruction_amd.tsdf import TSDFVolume

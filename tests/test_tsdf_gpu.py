@@ -262,7 +262,7 @@ def test_frame_split_merge_two_virtual_ranks(gpu):
         assert np.array_equal(wf, wm), "merged weights differ in unit %d" % k
         worst = max(worst, float(np.abs(sf - sm).max()))
     assert worst <= 1e-5, "merged tsdf differs by %.3g" % worst
-    # Round 5, the sparse merge (csrc/er_merge_protocol.h) with rank 0 as the root: only the units BOTH blocks touched go through the sum; a unit only
+    # Round 5's sparse merge with rank 0 as the root: only the units BOTH blocks touched go through the sum; a unit only
     # rank 1 touched travels raw (er_tsdf_export_raw -> er_tsdf_import_raw) and must arrive BIT FOR BIT -- and equal the single-volume result exactly,
     # since no frame of rank 0 ever reached it; the root's own single-toucher units do not move at all.
     k0, k1 = parts[0].unit_keys(), parts[1].unit_keys()
@@ -295,18 +295,17 @@ def test_frame_split_merge_two_virtual_ranks(gpu):
         v.close()
 
 
-@pytest.mark.parametrize("impl, root", [("owner", -2), ("owner", 0), ("owner", -1), ("ring", 0), ("ring", -1)])
-def test_frame_split_merge_with_four_loopback_ranks_on_one_gpu(gpu, impl, root):
+@pytest.mark.parametrize("root", [-2, 0, -1], ids=["owner--2", "owner-0", "owner--1"])
+def test_frame_split_merge_with_four_loopback_ranks_on_one_gpu(gpu, root):
     """The product's merge -- er_tsdf_allreduce: csrc/er_merge_protocol.h over the DEVICE volumes and their kernels -- with FOUR ranks on this one GPU
-    (er_comm_create_loopback: host threads, device-to-device copies for the wire; RCCL refuses two ranks on one device).  Round 6: the OWNER merge
+    (er_comm_create_loopback: host threads, device-to-device copies for the wire; RCCL refuses two ranks on one device).  The OWNER merge
     (reduce-scatter by unit over band records, sums in rank order in the owner's kernel) with the result left distributed (-2), gathered on rank 0, or
-    on every rank (-1); and round 5's ring protocol (ER_MERGE_IMPL=ring: whole planes through one sum, raw units point to point) for comparison.
-    tests/helpers.py::check_frame_split_merge holds the assertions; tests/test_distributed_gpu.py runs the same checker over RCCL when the box has
-    two or more GPUs."""
+    on every rank (-1).  tests/helpers.py::check_frame_split_merge holds the assertions; tests/test_distributed_gpu.py runs the same checker over
+    RCCL when the box has two or more GPUs."""
     from elasticreconstruction_amd import parallel
-    out = helpers.check_frame_split_merge(lambda: parallel.LoopbackComms(4), [0, 0, 0, 0], root, impl, repeat=2 if (impl, root) == ("owner", -2) else 1)
+    out = helpers.check_frame_split_merge(lambda: parallel.LoopbackComms(4), [0, 0, 0, 0], root, repeat=2 if root == -2 else 1)
     print("loopback merge:", out)
-    if impl == "owner" and root == -2:
+    if root == -2:
         assert out["moved_MB"] < 0.45 * out["ring_equivalent_MB"], out        # records, not planes
 
 
