@@ -17,13 +17,13 @@ SYMBOLS = [
     "er_tsdf_wait_event", "er_tsdf_reset", "er_tsdf_status", "er_tsdf_set_unit_shard", "er_unit_owner",
     "er_tsdf_scale_depth", "er_tsdf_reproject", "er_tsdf_integrate", "er_tsdf_integrate_frames",
     "er_tsdf_unit_count", "er_tsdf_unit_keys", "er_tsdf_read_unit", "er_tsdf_sum_weight",
-    "er_tsdf_extract_world", "er_tsdf_extract_surface", "er_tsdf_extract_mesh", "er_mc_table", "er_tsdf_export_weighted", "er_tsdf_import_weighted",
+    "er_tsdf_extract_world", "er_tsdf_extract_surface", "er_tsdf_extract_oriented", "er_tsdf_extract_mesh", "er_mc_table", "er_tsdf_export_weighted", "er_tsdf_import_weighted",
     "er_tsdf_export_raw", "er_tsdf_import_raw",
     "er_tsdf_band_sizes", "er_tsdf_export_band", "er_tsdf_merge_band", "er_tsdf_import_band", "er_tsdf_drop_units",
     "er_tsdf_set_profiling", "er_tsdf_get_profile",
     "er_comm_unique_id", "er_comm_create", "er_comm_create_local", "er_comm_create_loopback", "er_comm_destroy", "er_comm_rank", "er_comm_world",
     "er_tsdf_allreduce", "er_comm_merge_stats", "er_comm_merge_stats_owner", "er_frame_block",
-    "er_cloud_create", "er_cloud_create_batch", "er_cloud_destroy", "er_cloud_size",
+    "er_cloud_create", "er_cloud_create_batch", "er_cloud_create_from_tsdf", "er_cloud_destroy", "er_cloud_size",
     "er_icp_count_inliers", "er_icp_align", "er_find_correspondence",
     "er_icp_count_inliers_batch", "er_icp_align_batch", "er_find_correspondence_batch", "er_icp_release_workspaces", "er_registration_batch", "er_ransac_fitness_batch", "er_ransac_inliers",
     "er_fopt_create", "er_fopt_destroy", "er_fopt_set_cloud", "er_fopt_cloud_size", "er_fopt_get_points", "er_fopt_update_pose",
@@ -95,6 +95,8 @@ def lib():
     L.er_tsdf_sum_weight.argtypes = [vp, dp]
     L.er_tsdf_extract_world.argtypes = [vp, vp, C.c_long, C.POINTER(C.c_long)]
     L.er_tsdf_extract_surface.argtypes = [vp, vp, C.c_long, C.POINTER(C.c_long)]
+    if hasattr(L, "er_tsdf_extract_oriented"):                  # (absent from an older build selected with ER_HIP_LIB)
+        L.er_tsdf_extract_oriented.argtypes = [vp, vp, vp, C.c_long, C.POINTER(C.c_long)]
     L.er_tsdf_extract_mesh.argtypes = [vp, vp, C.c_long, C.POINTER(C.c_long)]
     L.er_mc_table.argtypes = [vp]
     L.er_request_hw_queues.argtypes = [C.c_int]
@@ -124,6 +126,8 @@ def lib():
     if hasattr(L, "er_cloud_create"):
         L.er_cloud_create.argtypes = [vp, vp, C.c_int, C.c_float, C.c_int, C.POINTER(vp)]
         L.er_cloud_create_batch.argtypes = [C.c_int, vp, vp, vp, C.c_float, C.c_int, vp]
+        if hasattr(L, "er_cloud_create_from_tsdf"):
+            L.er_cloud_create_from_tsdf.argtypes = [vp, C.c_float, C.c_float, C.POINTER(vp), ip]
         L.er_cloud_destroy.argtypes = [vp]
         L.er_cloud_size.argtypes = [vp]
         L.er_icp_count_inliers.argtypes = [vp, vp, vp, C.c_double, ip]

@@ -1540,8 +1540,6 @@ constexpr int kIcpChunk = 4;
 
 }  // namespace
 
-extern "C" {
-
 // Clouds of a LIST of fragments (BuildCorrespondence's LoadData loop, CorresApp.cpp:82-110, builds them one after the other), in chunks of up to
 // kCloudChunk clouds that share two device allocations and ONE set of grid launches:
 //   stage A, for every chunk up front: the chunk's allocation, its uploads -- coordinates and normals on two copy streams, truly asynchronous
@@ -1549,8 +1547,10 @@ extern "C" {
 //   stage B, chunk by chunk: ONE host wait for the boxes (the host sizes the grids from them), then cell ids + histogram + interleave, one
 //            radix sort, one prefix sum, one gather for the whole chunk, while the later chunks are still uploading.
 // The list is PCIe-bound; before round 4's last step it was bound by the host's launch rate (23 launches per cloud).
-int er_cloud_create_batch(int n_clouds, const float* const* xyz_host, const float* const* normal_host, const int* counts, float grid_cell, int device,
-                          er_cloud_t* out) {
+// `kind`: where the rows come from -- hipMemcpyHostToDevice (er_cloud_create / er_cloud_create_batch) or hipMemcpyDeviceToDevice (rows that a
+// kernel on this device has left complete, er::cloud_create_device); everything behind the copy is the same.
+static int cloud_create_impl(int n_clouds, const float* const* xyz_host, const float* const* normal_host, const int* counts, float grid_cell, int device,
+                             er_cloud_t* out, hipMemcpyKind kind) {
   if (n_clouds < 0 || (n_clouds > 0 && (!xyz_host || !normal_host || !counts || !out))) return er::fail("er_cloud_create: bad arguments");
   for (int i = 0; i < n_clouds; i++) out[i] = nullptr;
   for (int i = 0; i < n_clouds; i++)
@@ -1728,8 +1728,8 @@ int er_cloud_create_batch(int n_clouds, const float* const* xyz_host, const floa
     for (int k = 0; k < m; k++) {
       const int i = C.i0 + k, n = counts[i];
       if (n > 0) {
-        ER_HIP_TRY(hipMemcpyAsync(out[i]->xyz, xyz_host[i], (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, gs.up[0]));
-        ER_HIP_TRY(hipMemcpyAsync(out[i]->nrm, normal_host[i], (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, gs.up[1]));
+        ER_HIP_TRY(hipMemcpyAsync(out[i]->xyz, xyz_host[i], (size_t)n * 3 * sizeof(float), kind, gs.up[0]));
+        ER_HIP_TRY(hipMemcpyAsync(out[i]->nrm, normal_host[i], (size_t)n * 3 * sizeof(float), kind, gs.up[1]));
       }
     }
     // Stage A runs on a stream of its own (round 5): on the two grid lanes the upload waits of chunk 2, 4, ... were queued IN FRONT of
@@ -1846,6 +1846,17 @@ int er_cloud_create_batch(int n_clouds, const float* const* xyz_host, const floa
     return er::fail("%s", why.c_str());
   }
   return 0;
+}
+
+int er::cloud_create_device(const float* xyz_dev, const float* normal_dev, int n, float grid_cell, int device, er_cloud_s** out) {
+  return cloud_create_impl(1, &xyz_dev, &normal_dev, &n, grid_cell, device, out, hipMemcpyDeviceToDevice);
+}
+
+extern "C" {
+
+int er_cloud_create_batch(int n_clouds, const float* const* xyz_host, const float* const* normal_host, const int* counts, float grid_cell, int device,
+                          er_cloud_t* out) {
+  return cloud_create_impl(n_clouds, xyz_host, normal_host, counts, grid_cell, device, out, hipMemcpyHostToDevice);
 }
 
 int er_cloud_create(const float* xyz_host, const float* normal_host, int n, float grid_cell, int device, er_cloud_t* out) {

@@ -875,6 +875,86 @@ __global__ __launch_bounds__(64) void k_surface(const float2* __restrict__ pool,
   if (!pass && lane == 0) slab_count[blockIdx.x] = total;
 }
 
+// Oriented extraction (what the kinfu fragment step leaves in cloud_bin_<i>.pcd and CorresApp.cpp:82-99 reads back: the zero crossings WITH
+// normals): a float4 {nx, ny, nz, 0} for every point of k_surface's list, at the same index.  The normal is the normalised central difference
+// of the sdf at the point's NEAREST voxel v = rint((double)p / unit length) per component -- along the point's axis the crossed edge's lower
+// voxel or the one above it, on the other two axes the lattice index itself -- and exists only if v and its six neighbours are all observed
+// (weight != 0; a voxel of a unit that does not exist or lies outside the 512-unit lattice is unobserved) and the gradient is not zero;
+// otherwise it is NaN in all three components.  g = S[v + e] - S[v - e], n2 = (gx gx + gy gy) + gz gz, n = g / sqrt(n2): float32, every
+// operation rounded on its own (-ffp-contract=off, correctly rounded '/' and sqrtf), so a numpy restatement matches bit for bit
+// (tests/test_oriented_gpu.py).
+// One THREAD per point, behind k_surface's own write pass.  A first version did the seven fetches inside the slab loop of a copy of k_surface
+// (one wave per slab, 64 serial rows): the rows with a crossing -- most rows of a slab the surface passes through -- each waited for three
+// more dependent round trips to memory, 523 us against k_surface's 160 us on a 147-unit fragment (profiles/oriented_extraction.txt).  Here
+// every point is independent: one hash-map lookup for the unit of v, direct addresses for the neighbours that stay in it, a lookup of their
+// own for those across a unit border.  g = voxel index on the whole lattice, 0 .. 512 * 64 - 1 per axis.
+__device__ __forceinline__ float2 fetch_voxel(const float2* __restrict__ pool, const float2* __restrict__ unit, int key, const int* __restrict__ ht_key,
+                                              const int* __restrict__ ht_slot, int cap_mask, int shift, int gx, int gy, int gz) {
+  if ((unsigned)gx >= 512u * 64u || (unsigned)gy >= 512u * 64u || (unsigned)gz >= 512u * 64u) return make_float2(0.0f, 0.0f);
+  const int k = (gx >> 6) << 18 | (gy >> 6) << 9 | (gz >> 6);
+  const size_t l = (size_t)(gx & 63) * 4096 + (size_t)(gy & 63) * 64 + (size_t)(gz & 63);
+  if (k == key) return unit[l];
+  const int s = ht_lookup_slot(ht_key, ht_slot, cap_mask, shift, k);
+  return s >= 0 ? pool[(size_t)s * kUnitVox + l] : make_float2(0.0f, 0.0f);
+}
+
+// the nearest voxel's index: rint((double)p / unit length), round half to even, on the 0-based lattice
+__device__ __forceinline__ int nearest_index(float p) { return (int)rint((double)p / kUnitLength) + 256 * 64; }
+
+__global__ __launch_bounds__(256) void k_surface_normals(const float2* __restrict__ pool, const int* __restrict__ ht_key, const int* __restrict__ ht_slot,
+                                                         int cap_mask, int shift, const float4* __restrict__ pts, long n, float4* __restrict__ out_n) {
+  const long r = (long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= n) return;
+  const float4 p = pts[r];
+  const int gx = nearest_index(p.x), gy = nearest_index(p.y), gz = nearest_index(p.z);
+  // the unit of v: key -1 (matches no voxel) if v is outside the lattice or its unit does not exist -- the fetches then find that out themselves
+  const bool in = (unsigned)gx < 512u * 64u && (unsigned)gy < 512u * 64u && (unsigned)gz < 512u * 64u;
+  int key = in ? ((gx >> 6) << 18 | (gy >> 6) << 9 | (gz >> 6)) : -1;
+  const int slot = in ? ht_lookup_slot(ht_key, ht_slot, cap_mask, shift, key) : -1;
+  if (slot < 0) key = -1;
+  const float2* unit = pool + (size_t)(slot < 0 ? 0 : slot) * kUnitVox;
+#define ER_F(dx, dy, dz) fetch_voxel(pool, unit, key, ht_key, ht_slot, cap_mask, shift, gx + (dx), gy + (dy), gz + (dz))
+  const float2 c = ER_F(0, 0, 0);
+  const float2 xl = ER_F(-1, 0, 0), xh = ER_F(1, 0, 0), yl = ER_F(0, -1, 0), yh = ER_F(0, 1, 0), zl = ER_F(0, 0, -1), zh = ER_F(0, 0, 1);
+#undef ER_F
+  const bool seen = c.y != 0.0f && xl.y != 0.0f && xh.y != 0.0f && yl.y != 0.0f && yh.y != 0.0f && zl.y != 0.0f && zh.y != 0.0f;
+  const float ax = xh.x - xl.x, ay = yh.x - yl.x, az = zh.x - zl.x;
+  const float nrm = sqrtf((ax * ax + ay * ay) + az * az);
+  const float nan = __int_as_float(0x7fc00000);
+  out_n[r] = seen && nrm > 0.0f ? make_float4(ax / nrm, ay / nrm, az / nrm, 0.0f) : make_float4(nan, nan, nan, 0.0f);
+}
+
+// The rows CCorresApp::LoadData keeps (CorresApp.cpp:93-98: normal_x is not NaN) that also lie in the fragment's cube 0 <= x, y, z < cube
+// (PointCloud::GetCoordinate; cube <= 0: no cube test), compacted in order into packed xyz / normal rows -- er_cloud_create's input layout.
+// One wave per 64 rows, two passes (count, then write at the block's offset) like the extraction kernels.
+__global__ __launch_bounds__(64) void k_oriented_keep(const float4* __restrict__ pts, const float4* __restrict__ nrm, long n, float cube,
+                                                      long* __restrict__ blk_count, const long* __restrict__ blk_offset,
+                                                      float* __restrict__ xyz_out, float* __restrict__ nrm_out, int pass) {
+  const int lane = threadIdx.x;
+  const long r = (long)blockIdx.x * 64 + lane;
+  bool keep = false;
+  float4 p = make_float4(0.f, 0.f, 0.f, 0.f), q = p;
+  if (r < n) {
+    p = pts[r];
+    q = nrm[r];
+    keep = !(q.x != q.x) && (!(cube > 0.0f) || (p.x >= 0.0f && p.y >= 0.0f && p.z >= 0.0f && p.x < cube && p.y < cube && p.z < cube));
+  }
+  const unsigned long long b = __ballot(keep);
+  if (!pass) {
+    if (lane == 0) blk_count[blockIdx.x] = __popcll(b);
+    return;
+  }
+  if (keep) {
+    const size_t o = (size_t)(blk_offset[blockIdx.x] + __popcll(b & ((1ull << lane) - 1ull))) * 3;
+    xyz_out[o] = p.x;
+    xyz_out[o + 1] = p.y;
+    xyz_out[o + 2] = p.z;
+    nrm_out[o] = q.x;
+    nrm_out[o + 1] = q.y;
+    nrm_out[o + 2] = q.z;
+  }
+}
+
 
 // Marching cubes on the resident volume (the triangle connectivity the out-of-repo kinfu "mesh_output" step builds
 // from world.pcd, done where the volume lives).  Cell (i, j, k) of a unit = the eight voxels (i..i+1, j..j+1, k..k+1) -- the last
@@ -2042,6 +2122,155 @@ done:
   if (d_cnt) (void)hipFree(d_cnt);
   if (d_off) (void)hipFree(d_off);
   if (d_out) (void)hipFree(d_out);
+  return rc;
+}
+
+// The oriented list on the device: *d_pts / *d_nrm are hipMalloc'ed arrays of *total float4 (the caller frees them; both NULL when the list is
+// empty or want == false, which only counts).  k_surface's two passes, then k_surface_normals.  Synchronises h->stream.
+static int oriented_on_device(er_tsdf_t h, const char* who, bool want, float4** d_pts, float4** d_nrm, long* total_out) {
+  *d_pts = *d_nrm = nullptr;
+  *total_out = 0;
+  std::vector<int> keys, slots;
+  if (sorted_units(h, keys, slots)) return 1;
+  const int n = (int)keys.size();
+  if (n == 0) return 0;
+  const int nslab = n * 64;
+  int *d_keys = nullptr, *d_slots = nullptr;
+  long *d_cnt = nullptr, *d_off = nullptr;
+  int rc = 0;
+  std::vector<long> cnt((size_t)nslab), off((size_t)nslab);
+  long total = 0;
+#define ER_W(expr)                                                                              \
+  do {                                                                                          \
+    hipError_t e_ = (expr);                                                                     \
+    if (e_ != hipSuccess) {                                                                     \
+      rc = er::fail("%s: %s failed: %s", who, #expr, hipGetErrorString(e_));                    \
+      goto done;                                                                                \
+    }                                                                                           \
+  } while (0)
+  ER_W(hipMalloc((void**)&d_keys, (size_t)n * sizeof(int)));
+  ER_W(hipMalloc((void**)&d_slots, (size_t)n * sizeof(int)));
+  ER_W(hipMalloc((void**)&d_cnt, (size_t)nslab * sizeof(long)));
+  ER_W(hipMalloc((void**)&d_off, (size_t)nslab * sizeof(long)));
+  ER_W(hipMemcpyAsync(d_keys, keys.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  ER_W(hipMemcpyAsync(d_slots, slots.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(k_surface, dim3(nslab), dim3(64), 0, h->stream, h->pool, d_slots, d_keys, h->ht_key, h->ht_slot, h->ht_cap - 1, h->ht_shift,
+                     d_cnt, d_off, (float4*)nullptr, 0);
+  ER_W(hipGetLastError());
+  ER_W(hipMemcpyAsync(cnt.data(), d_cnt, (size_t)nslab * sizeof(long), hipMemcpyDeviceToHost, h->stream));
+  ER_W(hipStreamSynchronize(h->stream));
+  for (int s = 0; s < nslab; s++) {
+    off[(size_t)s] = total;
+    total += cnt[(size_t)s];
+  }
+  *total_out = total;
+  if (want && total > 0) {
+    ER_W(hipMalloc((void**)d_pts, (size_t)total * sizeof(float4)));
+    ER_W(hipMalloc((void**)d_nrm, (size_t)total * sizeof(float4)));
+    ER_W(hipMemcpyAsync(d_off, off.data(), (size_t)nslab * sizeof(long), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_surface, dim3(nslab), dim3(64), 0, h->stream, h->pool, d_slots, d_keys, h->ht_key, h->ht_slot, h->ht_cap - 1,
+                       h->ht_shift, d_cnt, d_off, *d_pts, 1);
+    ER_W(hipGetLastError());
+    hipLaunchKernelGGL(k_surface_normals, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->pool, h->ht_key, h->ht_slot, h->ht_cap - 1,
+                       h->ht_shift, *d_pts, total, *d_nrm);
+    ER_W(hipGetLastError());
+    ER_W(hipStreamSynchronize(h->stream));
+  }
+#undef ER_W
+done:
+  if (d_keys) (void)hipFree(d_keys);
+  if (d_slots) (void)hipFree(d_slots);
+  if (d_cnt) (void)hipFree(d_cnt);
+  if (d_off) (void)hipFree(d_off);
+  if (rc) {
+    if (*d_pts) (void)hipFree(*d_pts);
+    if (*d_nrm) (void)hipFree(*d_nrm);
+    *d_pts = *d_nrm = nullptr;
+  }
+  return rc;
+}
+
+int er_tsdf_extract_oriented(er_tsdf_t h, float* points_host, float* normals_host, long capacity, long* count) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return er::fail("er_tsdf_extract_oriented: no HIP device available (liber_hip has no CPU fallback)");
+  if (!h || !count) return er::fail("er_tsdf_extract_oriented: NULL argument");
+  ER_HIP_TRY(hipSetDevice(h->device));
+  const bool want = points_host && normals_host;
+  float4 *d_pts = nullptr, *d_nrm = nullptr;
+  *count = 0;
+  if (oriented_on_device(h, "er_tsdf_extract_oriented", want, &d_pts, &d_nrm, count)) return 1;
+  int rc = 0;
+  if (want && capacity < *count) {
+    rc = er::fail("er_tsdf_extract_oriented: capacity %ld < %ld points", capacity, *count);   // (nothing has been written to the host)
+  } else if (want && *count > 0) {
+    hipError_t e = hipMemcpyAsync(points_host, d_pts, (size_t)*count * sizeof(float4), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(normals_host, d_nrm, (size_t)*count * sizeof(float4), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) rc = er::fail("er_tsdf_extract_oriented: copy back failed: %s", hipGetErrorString(e));
+  }
+  if (d_pts) (void)hipFree(d_pts);
+  if (d_nrm) (void)hipFree(d_nrm);
+  return rc;
+}
+
+int er_cloud_create_from_tsdf(er_tsdf_t h, float cube_length, float grid_cell, er_cloud_t* out, int* n_points) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return er::fail("er_cloud_create_from_tsdf: no HIP device available (liber_hip has no CPU fallback)");
+  if (!h || !out) return er::fail("er_cloud_create_from_tsdf: NULL argument");
+  *out = nullptr;
+  if (n_points) *n_points = 0;
+  if (!(grid_cell > 0.f)) return er::fail("er_cloud_create_from_tsdf: grid_cell must be positive");
+  ER_HIP_TRY(hipSetDevice(h->device));
+  float4 *d_pts = nullptr, *d_nrm = nullptr;
+  long total = 0, kept = 0;
+  if (oriented_on_device(h, "er_cloud_create_from_tsdf", true, &d_pts, &d_nrm, &total)) return 1;
+  long* d_blk = nullptr;          // [2 nblk]: counts, then offsets
+  float* d_rows = nullptr;        // [kept][3] coordinates, then [kept][3] normals
+  int rc = 0;
+  const long nblk = (total + 63) / 64;
+  std::vector<long> blk((size_t)nblk * 2);
+#define ER_W(expr)                                                                              \
+  do {                                                                                          \
+    hipError_t e_ = (expr);                                                                     \
+    if (e_ != hipSuccess) {                                                                     \
+      rc = er::fail("er_cloud_create_from_tsdf: %s failed: %s", #expr, hipGetErrorString(e_));  \
+      goto done;                                                                                \
+    }                                                                                           \
+  } while (0)
+  if (total > 0) {
+    ER_W(hipMalloc((void**)&d_blk, (size_t)nblk * 2 * sizeof(long)));
+    hipLaunchKernelGGL(k_oriented_keep, dim3((unsigned)nblk), dim3(64), 0, h->stream, d_pts, d_nrm, total, cube_length, d_blk, d_blk + nblk,
+                       (float*)nullptr, (float*)nullptr, 0);
+    ER_W(hipGetLastError());
+    ER_W(hipMemcpyAsync(blk.data(), d_blk, (size_t)nblk * sizeof(long), hipMemcpyDeviceToHost, h->stream));
+    ER_W(hipStreamSynchronize(h->stream));
+    for (long b = 0; b < nblk; b++) {
+      blk[(size_t)(nblk + b)] = kept;
+      kept += blk[(size_t)b];
+    }
+    if (kept >= (1L << 27)) {
+      rc = er::fail("er_cloud_create_from_tsdf: %ld points; the limit is 2^27 - 1 (32-bit byte offsets in the search kernels)", kept);
+      goto done;
+    }
+    if (kept > 0) {
+      ER_W(hipMalloc((void**)&d_rows, (size_t)kept * 6 * sizeof(float)));
+      ER_W(hipMemcpyAsync(d_blk + nblk, blk.data() + nblk, (size_t)nblk * sizeof(long), hipMemcpyHostToDevice, h->stream));
+      hipLaunchKernelGGL(k_oriented_keep, dim3((unsigned)nblk), dim3(64), 0, h->stream, d_pts, d_nrm, total, cube_length, d_blk, d_blk + nblk,
+                         d_rows, d_rows + (size_t)kept * 3, 1);
+      ER_W(hipGetLastError());
+      ER_W(hipStreamSynchronize(h->stream));     // the cloud builder works on streams of its own: the rows are complete before it starts
+    }
+  }
+#undef ER_W
+  rc = er::cloud_create_device(d_rows, d_rows ? d_rows + (size_t)kept * 3 : nullptr, (int)kept, grid_cell, h->device, out);
+  if (rc == 0 && n_points) *n_points = (int)kept;
+done:
+  if (d_pts) (void)hipFree(d_pts);
+  if (d_nrm) (void)hipFree(d_nrm);
+  if (d_blk) (void)hipFree(d_blk);
+  if (d_rows) (void)hipFree(d_rows);
   return rc;
 }
 

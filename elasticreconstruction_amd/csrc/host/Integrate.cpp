@@ -20,6 +20,8 @@
 //                         extractions in ascending key order -- unless --merge_root <g> gathers it on GPU g first;
 //                         unit: every GPU is fed all frames and owns the units with er_unit_owner(key, N) == its rank
 //                         (er_tsdf_set_unit_shard): no collective, world.pcd BIT-identical to the single-GPU run
+//   --save_fragment <file.pcd> [--fragment_length <m>, 3.0]   after the run also write cloud_bin_<i>.pcd-style points with normals
+//                         (er_tsdf_extract_oriented, inside the cube [0, length)); single-GPU runs only
 //   --force_merge         with --gpus 1: run the frame-split merge anyway (exercises the RCCL path on a 1-GPU box)
 //
 // Control flow = CIntegrateApp::StartMainLoop/Execute: 1-based frame ids, frame_ == -1 skips a frame,
@@ -68,6 +70,7 @@ int print_help() {
   std::cout << "    -oni <raw_file> | --depth_raw <raw_file> : 640x480 uint16 frames; --depth_list <txt> : 16-bit PNG per line" << std::endl;
   std::cout << "MI355X options:" << std::endl;
   std::cout << "    --device <gpu> (0)  --max_units <n> (2048)  --batch <frames> (64)" << std::endl;
+  std::cout << "    --save_fragment <pcd_file> [--fragment_length <m> (3.0)] : also write the volume's surface points with normals, cloud_bin-style (single GPU only)" << std::endl;
   std::cout << "    --gpus <N> (1)  --shard frame|unit (frame: frame blocks + the merge by unit owner over RCCL; unit: bit-exact, no collective)  --merge_root <g>  --force_merge" << std::endl;
   return 0;
 }
@@ -343,6 +346,25 @@ struct App {
     printf("%ld voxel points have been written.\n", (long)(pts.size() / 4));
     return true;
   }
+
+  // --save_fragment: cloud_bin_<i>.pcd of the resident volume -- er_tsdf_extract_oriented's points inside the cube 0 <= x, y, z < length with their
+  // normals, NaN-normal rows kept (CCorresApp::LoadData filters them, CorresApp.cpp:93-98)
+  bool SaveFragment(const std::string& filename, float length) {
+    long n = 0;
+    if (er_tsdf_extract_oriented(volume_, nullptr, nullptr, 0, &n) != 0) { fprintf(stderr, "Integrate: %s\n", er_last_error()); return false; }
+    std::vector<float> pts((size_t)n * 4), nrm((size_t)n * 4), rows;
+    if (n > 0 && er_tsdf_extract_oriented(volume_, pts.data(), nrm.data(), n, &n) != 0) { fprintf(stderr, "Integrate: %s\n", er_last_error()); return false; }
+    rows.reserve((size_t)n * 6);
+    for (long i = 0; i < n; i++) {
+      const float* p = &pts[(size_t)i * 4];
+      if (!(p[0] >= 0.f && p[1] >= 0.f && p[2] >= 0.f && p[0] < length && p[1] < length && p[2] < length)) continue;
+      rows.insert(rows.end(), p, p + 3);
+      rows.insert(rows.end(), &nrm[(size_t)i * 4], &nrm[(size_t)i * 4] + 3);
+    }
+    if (!erfmt::save_pcd_xyzn(filename, rows.data(), rows.size() / 6)) { fprintf(stderr, "Integrate: cannot write %s\n", filename.c_str()); return false; }
+    printf("%ld fragment points have been written.\n", (long)(rows.size() / 6));
+    return true;
+  }
 };
 
 // hash_key of the unit a SaveWorld point (voxel index coordinates, TSDFVolume.cpp:119-121) belongs to.
@@ -437,6 +459,10 @@ int main(int argc, char* argv[]) {
   parse_argument(argc, argv, "--batch", app.batch_);
   parse_argument(argc, argv, "--gpus", gpus);
   parse_argument(argc, argv, "--shard", shard);
+  std::string fragment_file;                                            // --save_fragment <file.pcd>: the oriented surface points of the volume
+  double fragment_length = 3.0;
+  parse_argument(argc, argv, "--save_fragment", fragment_file);
+  parse_argument(argc, argv, "--fragment_length", fragment_length);
   const bool force_merge = find_switch(argc, argv, "--force_merge");
   int merge_root = ER_MERGE_DISTRIBUTED;                                // --merge_root <g>: gather the merged volume on worker g before SaveWorld
   parse_argument(argc, argv, "--merge_root", merge_root);
@@ -449,6 +475,10 @@ int main(int argc, char* argv[]) {
   if (gpus < 1) gpus = 1;
   if (shard != "frame" && shard != "unit") { fprintf(stderr, "Integrate: --shard must be frame or unit\n"); return 1; }
   if (merge_root != ER_MERGE_DISTRIBUTED && (merge_root < 0 || merge_root >= gpus)) { fprintf(stderr, "Integrate: --merge_root must name one of the %d workers\n", gpus); return 1; }
+  if (!fragment_file.empty() && gpus > 1) {
+    fprintf(stderr, "Integrate: --save_fragment needs the whole volume on one GPU; it is not available with --gpus %d\n", gpus);
+    return 1;
+  }
   const bool unit_shard = shard == "unit";
   if (same_device && !unit_shard && gpus > 16) { fprintf(stderr, "Integrate: --same_device --shard frame takes at most 16 workers\n"); return 1; }
   if (!same_device && gpus > 1 && er_device_count() > 0 && app.device_ + gpus > er_device_count()) {
@@ -541,6 +571,10 @@ int main(int argc, char* argv[]) {
     else if (!apps[(size_t)(merge && merge_root >= 0 ? merge_root : 0)].SaveWorld()) rc = 1;
   }
   stage_done("SaveWorld");
+  if (rc == 0 && !fragment_file.empty()) {
+    if (!apps[0].SaveFragment(fragment_file, (float)fragment_length)) rc = 1;
+    stage_done("SaveFragment");
+  }
   std::cout << "Total " << last_id << " frames processed." << std::endl;
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   std::cerr << "Integrate All took " << ms << "ms." << std::endl;

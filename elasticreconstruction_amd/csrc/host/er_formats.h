@@ -286,6 +286,19 @@ inline bool save_pcd_xyzi(const std::string& path, const float* xyzi, size_t n) 
   return true;
 }
 
+// cloud_bin_<i>.pcd-style fragment (FIELDS x y z normal_x normal_y normal_z, DATA binary): rows[6 n] = x y z nx ny nz per point.
+inline bool save_pcd_xyzn(const std::string& path, const float* rows, size_t n) {
+  FILE* f = fopen(path.c_str(), "wb");
+  if (!f) return false;
+  fprintf(f,
+          "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z normal_x normal_y normal_z\nSIZE 4 4 4 4 4 4\nTYPE F F F F F F\n"
+          "COUNT 1 1 1 1 1 1\nWIDTH %zu\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %zu\nDATA binary\n",
+          n, n);
+  if (n) fwrite(rows, sizeof(float) * 6, n, f);
+  fclose(f);
+  return true;
+}
+
 // LZF stream writer (the format lzf_decompress above reads; liblzf's published container-less format as PCL's
 // "DATA binary_compressed" uses it): greedy matcher over a hash of 3-byte strings, back references of 3..264 bytes
 // up to 8192 bytes back, literal runs of up to 32 bytes.

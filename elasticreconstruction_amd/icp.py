@@ -48,6 +48,19 @@ class Cloud:
         return self.n
 
     @classmethod
+    def from_volume(cls, vol, length=3.0, grid_cell=0.03):
+        """er_cloud_create_from_tsdf: the cloud of a resident TSDFVolume -- its oriented zero crossings minus the NaN-normal rows
+        (CorresApp.cpp:93-98) and, for length > 0, minus the points outside the cube 0 <= x, y, z < length -- built on the volume's device
+        without the points leaving HBM."""
+        lib = _ffi.lib()
+        h, n = C.c_void_p(), C.c_int(0)
+        _ffi.check(lib.er_cloud_create_from_tsdf(vol._h, C.c_float(length), C.c_float(grid_cell), C.byref(h), C.byref(n)),
+                   "er_cloud_create_from_tsdf")
+        c = cls.__new__(cls)
+        c._lib, c.n, c.grid_cell, c._h = lib, int(n.value), float(grid_cell), h
+        return c
+
+    @classmethod
     def create_batch(cls, arrays, grid_cell=0.03, device=0):
         """er_cloud_create_batch: [Cloud] for a list of (xyz, normals) in one call.  Arrays that live in page-locked memory
         (_ffi.PinnedArena) are uploaded asynchronously -- the list is then PCIe-bound."""

@@ -178,6 +178,27 @@ class TSDFVolume:
             _ffi.check(self._lib.er_tsdf_extract_surface(self._h, _ffi.ptr(out), n.value, C.byref(n)), "er_tsdf_extract_surface")
         return out
 
+    def extract_oriented(self):
+        """extract_surface's list with a normal per point (er_tsdf_extract_oriented): (points float32[n, 4] = x y z axis, normals float32[n, 3]).
+        The normal is the normalised central difference of the sdf at the point's nearest voxel; a row is NaN where that voxel or one of its
+        six neighbours was never observed (what the kinfu fragment step leaves in cloud_bin_<i>.pcd, CorresApp.cpp:93-98 filters)."""
+        n = C.c_long(0)
+        _ffi.check(self._lib.er_tsdf_extract_oriented(self._h, None, None, 0, C.byref(n)), "er_tsdf_extract_oriented")
+        pts = np.empty((n.value, 4), dtype=np.float32)
+        nrm = np.empty((n.value, 4), dtype=np.float32)
+        if n.value:
+            _ffi.check(self._lib.er_tsdf_extract_oriented(self._h, _ffi.ptr(pts), _ffi.ptr(nrm), n.value, C.byref(n)), "er_tsdf_extract_oriented")
+        return pts, np.ascontiguousarray(nrm[:, :3])
+
+    def SaveFragment(self, filename, length=3.0):
+        """cloud_bin_<i>.pcd of the resident volume: the oriented points inside the cube 0 <= x, y, z < length (PointCloud::GetCoordinate's cube),
+        NaN-normal rows KEPT -- CCorresApp::LoadData filters them (CorresApp.cpp:93-98).  Returns the number of points written."""
+        pts, nrm = self.extract_oriented()
+        x = pts[:, :3]
+        inside = ((x >= np.float32(0.0)) & (x < np.float32(length))).all(axis=1)
+        formats.save_pcd_xyzn(filename, np.ascontiguousarray(x[inside]), np.ascontiguousarray(nrm[inside]))
+        return int(inside.sum())
+
     def extract_mesh(self):
         """Marching-cubes triangles of the volume (er_tsdf_extract_mesh) as float32[n, 3, 3] = triangle, vertex, xyz in metres."""
         n = C.c_long(0)

@@ -142,6 +142,16 @@ int er_tsdf_extract_world(er_tsdf_t h, float* out_host, long capacity, long* cou
  * out_host may be NULL to query the count; capacity is in points. */
 int er_tsdf_extract_surface(er_tsdf_t h, float* out_host, long capacity, long* count);
 
+/* er_tsdf_extract_surface's list with a normal per point: what the kinfu fragment step writes into cloud_bin_<i>.pcd and CCorresApp::LoadData
+ * (CorresApp.cpp:82-99) and FragmentOptimizer read back -- replaces a host pass over the whole volume (read every unit back, rebuild a dense
+ * grid, take differences there).  The normal is the normalised central difference of the sdf at the point's nearest voxel
+ * v = rint((double)p / (3/512)): g_a = S[v + e_a] - S[v - e_a], n = g / sqrt((gx gx + gy gy) + gz gz), float32, every operation rounded on its own.
+ * It exists iff v and its six neighbours are observed (weight != 0; voxels of absent or dropped units and outside the 512-unit lattice are not)
+ * and the gradient is not zero; it points towards positive sdf = free space.
+ * points_host: 4 floats per point (x y z axis), bit-identical to er_tsdf_extract_surface; normals_host: 4 floats per point (nx ny nz 0;
+ * NaN NaN NaN 0 where the rule gives none).  Either may be NULL to query the count; capacity is in points. */
+int er_tsdf_extract_oriented(er_tsdf_t h, float* points_host, float* normals_host, long capacity, long* count);
+
 /* Marching cubes on the resident volume (the triangle connectivity the pipeline's next step -- kinfu's mesh output,
  * outside the reference repository -- builds from world.pcd).  A cell of 2 x 2 x 2 voxels yields triangles only if all eight are
  * observed (weight != 0); a corner is inside iff sdf < 0; vertices are the linear zero crossings on the lattice edges, in metres.
@@ -257,6 +267,12 @@ int er_cloud_create(const float* xyz_host, const float* normal_host, int n, floa
  * allocations go with its last cloud). */
 int er_cloud_create_batch(int n_clouds, const float* const* xyz_host, const float* const* normal_host, const int* counts, float grid_cell,
                           int device, er_cloud_t* out);
+/* pointclouds_[i] (CorresApp.cpp:82-99) made from the resident volume without leaving the device: er_tsdf_extract_oriented's list, minus the
+ * rows with a NaN normal (CorresApp.cpp:93-98), and, if cube_length > 0, minus the points outside 0 <= x, y, z < cube_length (float32
+ * compares; PointCloud::GetCoordinate's cube, far face excluded).  Order kept (a stable compaction on the device).  The cloud lives on the
+ * volume's device and equals, in every later result, the one er_cloud_create builds from the same rows taken through host memory.
+ * n_points may be NULL.  The call waits for the volume's stream (er_tsdf_set_stream) before the cloud builder's streams read the rows. */
+int er_cloud_create_from_tsdf(er_tsdf_t h, float cube_length, float grid_cell, er_cloud_t* out, int* n_points);
 int er_cloud_destroy(er_cloud_t c);
 int er_cloud_size(er_cloud_t c);
 
