@@ -26,6 +26,7 @@ SYMBOLS = [
     "er_cloud_create", "er_cloud_create_batch", "er_cloud_create_from_tsdf", "er_cloud_destroy", "er_cloud_size",
     "er_icp_count_inliers", "er_icp_align", "er_find_correspondence",
     "er_icp_count_inliers_batch", "er_icp_align_batch", "er_find_correspondence_batch", "er_icp_release_workspaces", "er_registration_batch", "er_ransac_fitness_batch", "er_ransac_inliers",
+    "er_features_create", "er_features_destroy", "er_features_size", "er_feature_knn", "er_ransac_hypotheses", "er_ransac_params_default", "er_ransac_align",
     "er_fopt_create", "er_fopt_destroy", "er_fopt_set_cloud", "er_fopt_cloud_size", "er_fopt_get_points", "er_fopt_update_pose",
     "er_fopt_update_point_pn", "er_fopt_set_correspondences", "er_fopt_set_correspondences_dev", "er_fopt_group_count", "er_fopt_group_info", "er_fopt_update_normals", "er_fopt_assemble_rigid", "er_fopt_assemble_slac",
     "er_fopt_assemble_nonrigid", "er_fopt_factor_slac", "er_fopt_factor_nonrigid", "er_fopt_solve", "er_fopt_debug_shift_diagonal",
@@ -43,6 +44,18 @@ class ErWarp(C.Structure):
         ("seg", C.POINTER(C.c_double)),
         ("madj", C.POINTER(C.c_double)),
     ]
+
+
+class ErRansacParams(C.Structure):
+    """struct er_ransac_params (include/er_hip.h)."""
+    _fields_ = [("max_iterations", C.c_int), ("nr_samples", C.c_int), ("k_correspondences", C.c_int), ("similarity", C.c_float),
+                ("max_corr_dist", C.c_float), ("inlier_fraction", C.c_float), ("inlier_number", C.c_int), ("angle_diff", C.c_float),
+                ("seed", C.c_uint), ("chunk_iterations", C.c_int)]
+
+
+class ErRansacStats(C.Structure):
+    """struct er_ransac_stats (include/er_hip.h)."""
+    _fields_ = [("iterations", C.c_longlong), ("polygon_rejections", C.c_longlong), ("normal_rejections", C.c_longlong), ("scored", C.c_longlong)]
 
 
 class ErError(RuntimeError):
@@ -141,6 +154,14 @@ def lib():
                                             vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.er_ransac_fitness_batch.argtypes = [vp, vp, C.c_int, vp, C.c_float, vp, vp]
         L.er_ransac_inliers.argtypes = [vp, vp, vp, C.c_float, vp, C.c_int, ip, vp, vp, vp]
+        if hasattr(L, "er_ransac_align"):
+            L.er_features_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+            L.er_features_destroy.argtypes = [vp]
+            L.er_features_size.argtypes = [vp]
+            L.er_feature_knn.argtypes = [vp, vp, C.c_int, vp, vp]
+            L.er_ransac_hypotheses.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, C.c_float, C.c_float, vp, vp]
+            L.er_ransac_params_default.argtypes = [C.POINTER(ErRansacParams)]
+            L.er_ransac_align.argtypes = [vp, vp, vp, vp, C.POINTER(ErRansacParams), vp, ip, ip, dp, C.POINTER(ErRansacStats), vp, C.c_int, ip]
     if hasattr(L, "er_fopt_create"):
         L.er_fopt_create.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(vp)]
         L.er_fopt_destroy.argtypes = [vp]

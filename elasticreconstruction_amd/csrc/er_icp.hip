@@ -2355,3 +2355,5 @@ int er_registration_batch(int n, const er_cloud_t* src, const er_cloud_t* tgt, c
 }
 
 }  // extern "C"
+
+#include "er_ransac_search.h"   // GlobalRegistration's RANSAC pose search: shares the cloud types, nn_block and the workspace pool above

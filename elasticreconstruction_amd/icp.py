@@ -167,6 +167,107 @@ def ransac_inliers(src, tgt, M, corr_dist_threshold):
     return pairs[:, 1].copy(), pairs[:, 0].copy(), fit.value, info_s, info_t      # pairs are (target, source) like corres_*.txt
 
 
+class Features:
+    """The descriptors of a cloud's points in HBM (RansacCurvature::setSourceFeatures / setTargetFeatures): float32 [n, dim], row i
+    belongs to point i of the cloud in file order."""
+
+    def __init__(self, array, device=0):
+        self._lib = _ffi.lib()
+        f = np.ascontiguousarray(array, dtype=np.float32)
+        assert f.ndim == 2
+        self.n, self.dim = f.shape
+        h = C.c_void_p()
+        _ffi.check(self._lib.er_features_create(_ffi.ptr(f), self.n, self.dim, int(device), C.byref(h)), "er_features_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.er_features_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self.n
+
+
+def feature_knn(src_f, tgt_f, k):
+    """findSimilarFeatures' nearestKSearch (RansacCurvature.h:373-387) for every source descriptor: (indices int32 [n_src, k],
+    squared distances float32 [n_src, k]), ascending distance, ties to the lower index."""
+    idx = np.zeros((src_f.n, max(int(k), 0)), np.int32)
+    d = np.zeros((src_f.n, max(int(k), 0)), np.float32)
+    _ffi.check(src_f._lib.er_feature_knn(src_f._h, tgt_f._h, int(k), _ffi.ptr(idx), _ffi.ptr(d)), "er_feature_knn")
+    return idx, d
+
+
+def ransac_hypotheses(src, tgt, sample_idx, corr_idx, similarity=0.9, angle_diff=0.52359878):
+    """Polygon pre-rejection, rigid estimate and normal test (RansacCurvature.h:524-613) of explicit sample sets: sample_idx / corr_idx
+    int [n, nr_samples].  Returns (status int32 [n]: 0 accepted, 1 polygon, 2 normal / NaN; M float32 [n, 4, 4])."""
+    s = np.ascontiguousarray(sample_idx, np.int32)
+    c = np.ascontiguousarray(corr_idx, np.int32)
+    assert s.ndim == 2 and s.shape == c.shape
+    n, ns = s.shape
+    status, M = np.zeros(n, np.int32), np.zeros((n, 16), np.float32)
+    _ffi.check(src._lib.er_ransac_hypotheses(src._h, tgt._h, n, ns, _ffi.ptr(s), _ffi.ptr(c), C.c_float(similarity), C.c_float(angle_diff),
+                                             _ffi.ptr(status), _ffi.ptr(M)), "er_ransac_hypotheses")
+    return status, M.reshape(n, 4, 4)
+
+
+RANSAC_AUX = np.dtype([("iteration", np.int32), ("count", np.int32), ("error", np.float64), ("M", np.float32, (4, 4))])   # struct er_ransac_aux
+
+
+class RansacResult:
+    """ransac_align's result: T float32 4x4, converged, n_inliers, error, stats dict, aux (structured array RANSAC_AUX or None)."""
+    __slots__ = ("T", "converged", "n_inliers", "error", "stats", "aux")
+
+    def __init__(self, T, converged, n_inliers, error, stats, aux):
+        self.T, self.converged, self.n_inliers, self.error, self.stats, self.aux = T, converged, n_inliers, error, stats, aux
+
+
+def ransac_align(src, tgt, src_f, tgt_f, max_iterations=4000000, nr_samples=4, k_correspondences=2, similarity=0.9, max_corr_dist=0.075,
+                 inlier_fraction=0.33, inlier_number=30000, angle_diff=0.52359878, seed=0, chunk_iterations=0, aux_capacity=0):
+    """RansacCurvature::computeTransformation (RansacCurvature.h:411-657) on the device; defaults = the reference's alignment.config.
+    aux_capacity > 0 returns the first that many scored hypotheses (iteration, count, error, M)."""
+    assert RANSAC_AUX.itemsize == 80
+    p = _ffi.ErRansacParams(int(max_iterations), int(nr_samples), int(k_correspondences), float(similarity), float(max_corr_dist),
+                            float(inlier_fraction), int(inlier_number), float(angle_diff), int(seed) & 0xffffffff, int(chunk_iterations))
+    T = np.zeros(16, np.float32)
+    conv, cnt, na, err = C.c_int(0), C.c_int(0), C.c_int(0), C.c_double(0)
+    st = _ffi.ErRansacStats()
+    aux = np.zeros(int(aux_capacity), RANSAC_AUX)
+    _ffi.check(src._lib.er_ransac_align(src._h, tgt._h, src_f._h, tgt_f._h, C.byref(p), _ffi.ptr(T), C.byref(conv), C.byref(cnt), C.byref(err),
+                                        C.byref(st), _ffi.ptr(aux) if aux_capacity > 0 else None, int(aux_capacity), C.byref(na)), "er_ransac_align")
+    stats = dict(iterations=st.iterations, polygon_rejections=st.polygon_rejections, normal_rejections=st.normal_rejections, scored=st.scored)
+    return RansacResult(T.reshape(4, 4), bool(conv.value), cnt.value, err.value, stats, aux[:min(na.value, int(aux_capacity))] if aux_capacity > 0 else None)
+
+
+def global_registration(clouds, features, smart_swap=True, **params):
+    """do_all's loop (GlobalRegistration.cpp:32-188) without its file loading, downsampling and feature estimation: every pair i < j,
+    scene = i, object = j; with smart_swap the smaller cloud becomes the source and the pair stores the inverse transform and
+    information_target_ (:160-166).  Converged pairs only.  Returns (traj, info) ready for formats.save_log / save_info
+    (result.txt, result.info)."""
+    num = len(clouds)
+    traj, info = [], []
+    thr = params.get("max_corr_dist", 0.075)
+    for i in range(num):
+        for j in range(i + 1, num):
+            scene, obj, swapped = i, j, False
+            if smart_swap and clouds[obj].n > clouds[scene].n:
+                scene, obj, swapped = j, i, True
+            r = ransac_align(clouds[obj], clouds[scene], features[obj], features[scene], **params)
+            if not r.converged:
+                continue
+            _, _, _, info_s, info_t = ransac_inliers(clouds[obj], clouds[scene], r.T, thr)
+            T = np.linalg.inv(r.T) if swapped else r.T                      # (Matrix4f::inverse, then the cast to double, :161,178)
+            traj.append(formats.FramedTransformation(i, j, num, np.asarray(T, np.float32).astype(np.float64)))
+            info.append(formats.FramedInformation(i, j, num, info_t if swapped else info_s))
+    return traj, info
+
+
 _arena = None
 
 

@@ -241,6 +241,24 @@ def fragment_set(num, target_points=250000, seed=SEED, length=3.0, radius=0.0, d
     return out
 
 
+def landmark_features(world_xyz, seed=11, noise=0.15, outlier_frac=0.7, rng=None):
+    """A seeded 33-float descriptor per point for the RANSAC tests and probes, in the place of FPFH: sin(world_xyz . W + phi) with W a
+    3 x 33 Gaussian matrix scaled to a 0.6 m wavelength and phi uniform (both from RandomState(seed)), plus Gaussian noise of the given
+    standard deviation, and a fraction outlier_frac of the rows replaced by uniform noise in [-1, 1] (both from `rng`: a numpy
+    Generator, or a seed for one).  It takes the WORLD position, so two fragments agree where they see the same surface and the
+    outlier rate is a parameter.  Returns float32 [n, 33]."""
+    rs = np.random.RandomState(seed)
+    W = rs.normal(size=(3, 33)) * (2.0 * math.pi / 0.6)
+    phi = rs.uniform(0.0, 2.0 * math.pi, size=33)
+    g = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+    x = np.asarray(world_xyz, np.float64).reshape(-1, 3)
+    f = np.sin(x @ W + phi)
+    f += g.normal(scale=noise, size=f.shape)
+    out = g.random(x.shape[0]) < outlier_frac
+    f[out] = g.uniform(-1.0, 1.0, size=(int(out.sum()), 33))
+    return f.astype(np.float32)
+
+
 def perturbation(seed, max_rot_deg=2.0, max_trans=0.02):
     """Small seeded rigid perturbation (4x4 float64)."""
     rng = np.random.RandomState(seed)

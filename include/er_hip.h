@@ -330,6 +330,68 @@ int er_ransac_fitness_batch(er_cloud_t src, er_cloud_t tgt, int n_hyp, const flo
 int er_ransac_inliers(er_cloud_t src, er_cloud_t tgt, const float* M16, float corr_dist_threshold, int* pairs_host, int capacity,
                       int* n_inliers, double* fitness, double* info_source36, double* info_target36);
 
+/* ---- GlobalRegistration: the RANSAC pose search (RansacCurvature::computeTransformation, RansacCurvature.h:411-657, with
+ * PolyRejector.h), the per-point features as an input (setSourceFeatures / setTargetFeatures, GlobalRegistration.cpp:131-147). ---- */
+typedef struct er_features_s* er_features_t;
+
+/* n descriptors of dim floats (33 for FPFH; 1 <= dim <= 64), row i belongs to point i of a cloud in file order.  Values must be
+ * finite and at most 1e15 in magnitude (squared distances then stay finite). */
+int er_features_create(const float* feat_host, int n, int dim, int device, er_features_t* out);
+int er_features_destroy(er_features_t f);
+int er_features_size(er_features_t f);
+
+/* findSimilarFeatures' nearestKSearch (RansacCurvature.h:373-387) for EVERY source descriptor at once: its k nearest target
+ * descriptors by brute force, 1 <= k <= 8 <= n_tgt.  Distance = float32 sum of squared differences in ascending dimension; ascending
+ * distance, ties to the lower target index.  idx_host / sqdist_host (either may be NULL): [n_src][k]. */
+int er_feature_knn(er_features_t src, er_features_t tgt, int k, int* idx_host, float* sqdist_host);
+
+/* The unit under the loop, for explicit samples: n_hyp hypotheses of nr_samples (3 .. 6) pairs (source point sample_idx[h][i], target
+ * point corr_idx[h][i]).  Per hypothesis, in the reference's order (:524-613): thresholdPolygon over ALL pairs of edges (float32 squared
+ * lengths, min/max ratio against similarity^2), the rigid estimate of the pairs (least squares, float64, rounded to float32 once),
+ * NaN check, thresholdNormal (every n_t . (R n_s) >= cos(angle_diff), float32).  status[h]: 0 accepted, 1 polygon, 2 normal / NaN.
+ * M: n_hyp row-major float 4x4 (all zero for status 1; the estimate for status 0 and 2). */
+int er_ransac_hypotheses(er_cloud_t src, er_cloud_t tgt, int n_hyp, int nr_samples, const int* sample_idx, const int* corr_idx,
+                         float similarity, float angle_diff, int* status, float* M);
+
+typedef struct er_ransac_params {
+  int max_iterations;        /* 4000000   (alignment.config)        1 .. 2^28 */
+  int nr_samples;            /* 4         3 .. 6; 2 is refused: the reference's two-point branch builds the target's virtual points
+                                          from the SOURCE's normal and midpoint (:575-580), matching it would mean copying a slip */
+  int k_correspondences;     /* 2         1 .. 8 */
+  float similarity;          /* 0.9       [0, 1) */
+  float max_corr_dist;       /* 0.075     <= the target cloud's grid cell */
+  float inlier_fraction;     /* 0.33      [0, 1] */
+  int inlier_number;         /* 30000 */
+  float angle_diff;          /* 0.52359878 */
+  unsigned int seed;
+  int chunk_iterations;      /* iterations per round of launches; 0 = 1048576.  NOT part of the result. */
+} er_ransac_params;
+typedef struct er_ransac_stats {   /* the reference's debug line (:655) */
+  long long iterations, polygon_rejections, normal_rejections, scored;
+} er_ransac_stats;
+typedef struct er_ransac_aux {     /* one scored hypothesis (writeAuxData's list, :737-747, plus its score) */
+  int iteration, count;
+  double error;
+  float M[16];
+} er_ransac_aux;
+int er_ransac_params_default(er_ransac_params* p);
+
+/* computeTransformation with an identity guess, all on the device.  Iteration i draws its random numbers from (seed, i, draw) only:
+ *   z = (seed << 32) + 16 i + draw;  z += 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *   z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z ^= z >> 31;  r = z >> 32;  index(m) = (m * r) >> 32        (64-bit unsigned)
+ * draws 0 .. nr_samples-1 feed selectSamples (:319-359, index(n - i)), draw 8 + i picks index(k) among the k feature matches of the
+ * i-th (ascending) sample when k > 1 (:383-386).  Survivors of the polygon test are estimated, normal-tested and scored like
+ * er_ransac_fitness_batch (count exact; the sum of the inlier distances in 64-bit fixed point, so that error = sum / count is a
+ * function of the inlier set alone).  Acceptable: (float)count / n_src >= inlier_fraction or count > inlier_number, and count > 0;
+ * the acceptable hypothesis of lowest error wins, the earliest iteration on equal error (:627-643).
+ * None acceptable: *converged = 0 and T_out = identity (the reference leaves final_transformation_ = guess).
+ * aux (nullable): the first aux_capacity scored hypotheses in iteration order; *aux_count (nullable) = how many were scored.
+ * The result -- T_out, n_inliers, error, stats, aux -- is a function of the clouds, the features and the parameters other than
+ * chunk_iterations: not of the chunking, the grid sizes or the run. */
+int er_ransac_align(er_cloud_t src, er_cloud_t tgt, er_features_t src_feat, er_features_t tgt_feat, const er_ransac_params* p,
+                    float T_out[16], int* converged, int* n_inliers, double* error, er_ransac_stats* stats, er_ransac_aux* aux,
+                    int aux_capacity, int* aux_count);
+
 /* Frees the pooled ICP workspaces (streams, scratch, pinned blocks).  Optional; call when no ICP call is running. */
 int er_icp_release_workspaces(void);
 
