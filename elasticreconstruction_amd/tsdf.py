@@ -255,7 +255,7 @@ class TSDFVolume:
         sp = np.ascontiguousarray(self_pos, dtype=np.int32)
         r = (C.c_void_p * (16 * k.size))()
         for u, x in enumerate(srcs):
-            for q, ptr in enumerate(x):
+            for q, ptr in enumerate(x[:16]):                       # (more than 16: the library refuses the call by the count)
                 r[16 * u + q] = int(ptr)
         _ffi.check(self._lib.er_tsdf_merge_band(self._h, _ffi.ptr(k), k.size, _ffi.ptr(ns), _ffi.ptr(sp), r), "er_tsdf_merge_band")
 

@@ -181,8 +181,10 @@ int er_tsdf_import_raw(er_tsdf_t h, const int* keys_host, int n_keys, const floa
  * keys[u] becomes the sum of its own voxels and nsrc[u] <= 16 records (recs[16 u + k], the other GPUs' in rank order; self_pos[u] of them come before
  * its own voxels in that order): SW = sum fl(sdf_r w_r), W = sum w_r, sdf = SW / W, TSDFVolume.cpp:93-94 as a sum in an order fixed by the arguments.
  * import_band: create / overwrite units from records.  drop_units: this GPU hands the units over -- they are zeroed and disappear from
- * er_tsdf_unit_count / unit_keys / read_unit / the extractions until the next integrated frame or import touches them.  All of them run on the handle's
- * stream and return when the device work is done. */
+ * er_tsdf_unit_count / unit_keys / read_unit / band_sizes / the extractions.  An import (raw, weighted or band) brings back the units it names.  The
+ * next er_tsdf_integrate_frames call with at least one frame brings back ALL of them, whichever units its frames touch: the touched ones hold those
+ * frames alone, the others are allocated, never-updated units (all voxels (+0, 0), as far units are after any integration), and the next merge counts
+ * this GPU among their holders with an empty record.  All of them run on the handle's stream and return when the device work is done. */
 int er_tsdf_band_sizes(er_tsdf_t h, const int* keys_host, int n_keys, int* words_host);
 int er_tsdf_export_band(er_tsdf_t h, const int* keys_host, const int* words_host, int n_keys, void* dev_block);
 int er_tsdf_merge_band(er_tsdf_t h, const int* keys_host, int n_keys, const int* nsrc, const int* self_pos, const void* const* recs);
