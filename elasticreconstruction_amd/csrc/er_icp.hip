@@ -2357,3 +2357,4 @@ int er_registration_batch(int n, const er_cloud_t* src, const er_cloud_t* tgt, c
 }  // extern "C"
 
 #include "er_ransac_search.h"   // GlobalRegistration's RANSAC pose search: shares the cloud types, nn_block and the workspace pool above
+#include "er_fpfh.h"            // GlobalRegistration's voxel grid, normal and FPFH estimation: shares the cloud types, the grid builder and er_features_s above

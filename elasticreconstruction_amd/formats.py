@@ -347,3 +347,35 @@ def save_pcd_xyzn(path, xyz, normals, binary=True):
             s = io.StringIO()
             np.savetxt(s, a, fmt="%.9g")
             f.write(s.getvalue().encode("ascii"))
+
+
+# GlobalRegistration's alignment.config (helper.h's Configuration): key=value lines.  The defaults are the values of the file the reference ships.
+ALIGNMENT_DEFAULTS = dict(visualization=False, estimate_normal=True, aux_data=False, smart_swap=True, pcl_verbose=3, normal_radius=0.1,
+                          feature_radius=0.25, max_iteration=4000000, num_of_samples=4, correspondence_randomness=2, edge_similarity=0.9,
+                          resample_leaf=0.05, max_correspondence_distance=0.075, inlier_fraction=0.33, inlier_number=30000,
+                          angle_difference=0.52359878)
+
+
+def load_alignment_config(path):
+    """alignment.config -> dict.  Known keys are converted to the type of their default (booleans: "true" is True, anything else False,
+    as the reference compares); unknown keys are kept as strings; path None or a missing file gives the defaults."""
+    cfg = dict(ALIGNMENT_DEFAULTS)
+    if path is None or not os.path.exists(path):
+        return cfg
+    with open(path) as f:
+        for line in f:
+            line = line.strip()
+            if not line or "=" not in line:
+                continue
+            key, val = line.split("=", 1)
+            key, val = key.strip(), val.strip()
+            d = ALIGNMENT_DEFAULTS.get(key)
+            if isinstance(d, bool):
+                cfg[key] = val == "true"
+            elif isinstance(d, int):
+                cfg[key] = int(val)
+            elif isinstance(d, float):
+                cfg[key] = float(val)
+            else:
+                cfg[key] = val
+    return cfg

@@ -81,6 +81,36 @@ class Cloud:
             out.append(c)
         return out
 
+    @classmethod
+    def _wrap(cls, lib, handle, grid_cell):
+        c = cls.__new__(cls)
+        c._lib, c.n, c.grid_cell, c._h = lib, int(lib.er_cloud_size(handle)), float(grid_cell), handle
+        return c
+
+    def read(self):
+        """er_cloud_read: (xyz float32 [n, 3], normals float32 [n, 3]) in file order."""
+        xyz, nrm = np.empty((self.n, 3), np.float32), np.empty((self.n, 3), np.float32)
+        _ffi.check(self._lib.er_cloud_read(self._h, _ffi.ptr(xyz), _ffi.ptr(nrm)), "er_cloud_read")
+        return xyz, nrm
+
+    def voxel_grid(self, leaf, grid_cell=None):
+        """er_cloud_voxel_grid: pcl::VoxelGrid at `leaf` (GlobalRegistration.cpp:59-68) as a new Cloud, one point per occupied cell in
+        ascending cell order, searchable up to grid_cell (default: this cloud's)."""
+        gc = self.grid_cell if grid_cell is None else float(grid_cell)
+        h, n = C.c_void_p(), C.c_int(0)
+        _ffi.check(self._lib.er_cloud_voxel_grid(self._h, C.c_float(leaf), C.c_float(gc), C.byref(h), C.byref(n)), "er_cloud_voxel_grid")
+        return Cloud._wrap(self._lib, h, gc)
+
+    def estimate_normals(self, radius, want_counts=False):
+        """er_cloud_estimate_normals: pcl::NormalEstimation at `radius` and the flip against this cloud's normals
+        (GlobalRegistration.cpp:81-117) as a new Cloud over the same points.  want_counts: (Cloud, neighbourhood sizes int32 [n])."""
+        h = C.c_void_p()
+        cnt = np.zeros(self.n, np.int32) if want_counts else None
+        _ffi.check(self._lib.er_cloud_estimate_normals(self._h, C.c_float(radius), C.byref(h), _ffi.ptr(cnt) if want_counts else None),
+                   "er_cloud_estimate_normals")
+        out = Cloud._wrap(self._lib, h, self.grid_cell)
+        return (out, cnt) if want_counts else out
+
 
 def count_inliers(src, tgt, T, max_dist):
     """Registration pre-check (CorresApp.cpp:249-264)."""
@@ -194,6 +224,40 @@ class Features:
     def __len__(self):
         return self.n
 
+    def read(self):
+        """er_features_read: float32 [n, dim]."""
+        out = np.empty((self.n, self.dim), np.float32)
+        if self.n:
+            _ffi.check(self._lib.er_features_read(self._h, _ffi.ptr(out)), "er_features_read")
+        return out
+
+
+def fpfh(cloud, radius, want_counts=False):
+    """er_fpfh_estimate: pcl::FPFHEstimation at `radius` (GlobalRegistration.cpp:121-128) over the cloud's points and normals -> Features
+    (33 per point) that never leave the device.  want_counts: (Features, SPFH bin counts int32 [n, 33], neighbourhood sizes int32 [n])."""
+    lib = cloud._lib
+    h = C.c_void_p()
+    cnt = np.zeros((cloud.n, 33), np.int32) if want_counts else None
+    nn = np.zeros(cloud.n, np.int32) if want_counts else None
+    _ffi.check(lib.er_fpfh_estimate(cloud._h, C.c_float(radius), C.byref(h), _ffi.ptr(cnt) if want_counts else None,
+                                    _ffi.ptr(nn) if want_counts else None), "er_fpfh_estimate")
+    f = Features.__new__(Features)
+    f._lib, f._h = lib, h
+    f.n, f.dim = int(lib.er_features_size(h)), int(lib.er_features_dim(h))
+    return (f, cnt, nn) if want_counts else f
+
+
+def preprocess_fragment(cloud, leaf=0.05, normal_radius=0.1, feature_radius=0.25, estimate_normal=True, grid_cell=0.075):
+    """The per-fragment half of do_all (GlobalRegistration.cpp:59-128): downsample, re-estimate the normals (signs from the downsampled
+    input normals), FPFH.  Defaults = alignment.config; grid_cell = the search radius the result has to support as a target
+    (max_correspondence_distance).  Returns (Cloud, Features)."""
+    down = cloud.voxel_grid(leaf, grid_cell)
+    if estimate_normal:
+        est = down.estimate_normals(normal_radius)
+        down.close()
+        down = est
+    return down, fpfh(down, feature_radius)
+
 
 def feature_knn(src_f, tgt_f, k):
     """findSimilarFeatures' nearestKSearch (RansacCurvature.h:373-387) for every source descriptor: (indices int32 [n_src, k],
@@ -266,6 +330,24 @@ def global_registration(clouds, features, smart_swap=True, **params):
             traj.append(formats.FramedTransformation(i, j, num, np.asarray(T, np.float32).astype(np.float64)))
             info.append(formats.FramedInformation(i, j, num, info_t if swapped else info_s))
     return traj, info
+
+
+def global_registration_fragments(clouds, config=None, **params):
+    """do_all (GlobalRegistration.cpp:32-188) from the fragments' full clouds: every fragment is preprocessed ONCE (the reference redoes
+    it for both clouds of every pair), then global_registration runs unchanged -- its smart_swap compares the downsampled sizes, as
+    :70-79 does.  config: a dict as formats.load_alignment_config returns it (default: alignment.config's values); **params override
+    ransac_align's arguments (seed, max_iterations, ...).  Returns (traj, info, downsampled clouds, features)."""
+    cfg = formats.load_alignment_config(None)
+    cfg.update(config or {})
+    pre = [preprocess_fragment(c, cfg["resample_leaf"], cfg["normal_radius"], cfg["feature_radius"], cfg["estimate_normal"],
+                               cfg["max_correspondence_distance"]) for c in clouds]
+    kw = dict(max_iterations=cfg["max_iteration"], nr_samples=cfg["num_of_samples"], k_correspondences=cfg["correspondence_randomness"],
+              similarity=cfg["edge_similarity"], max_corr_dist=cfg["max_correspondence_distance"], inlier_fraction=cfg["inlier_fraction"],
+              inlier_number=cfg["inlier_number"], angle_diff=cfg["angle_difference"])
+    kw.update(params)
+    down, feats = [p[0] for p in pre], [p[1] for p in pre]
+    traj, info = global_registration(down, feats, smart_swap=cfg["smart_swap"], **kw)
+    return traj, info, down, feats
 
 
 _arena = None

@@ -259,6 +259,47 @@ def landmark_features(world_xyz, seed=11, noise=0.15, outlier_frac=0.7, rng=None
     return f.astype(np.float32)
 
 
+def relief_height(xy, bumps):
+    """z and the unit upward normal of the relief z = 1.5 + sum a_k exp(-|xy - c_k|^2 / (2 s_k^2)) at xy [n, 2] (float64)."""
+    c, a, s = bumps
+    d = xy[:, None, :] - c[None, :, :]
+    g = a[None, :] * np.exp(-(d * d).sum(axis=2) / (2.0 * s[None, :] ** 2))
+    z = 1.5 + g.sum(axis=1)
+    gx = (g * (-d[:, :, 0] / s[None, :] ** 2)).sum(axis=1)
+    gy = (g * (-d[:, :, 1] / s[None, :] ** 2)).sum(axis=1)
+    nrm = np.stack([-gx, -gy, np.ones_like(gx)], axis=1)
+    return z, nrm / np.linalg.norm(nrm, axis=1, keepdims=True)
+
+
+def relief_fragments(num=3, n_points=100000, seed=1234, n_bumps=60, angles_deg=(0.0, 25.0, 60.0), shifts=(0.0, 0.2, 0.3)):
+    """The end-to-end scene of the FPFH tests: `num` independently sampled views of ONE smooth height field with 60 Gaussian bumps
+    (RandomState(seed): centres uniform in [0.2, 2.8]^2, amplitudes uniform in +-0.12, widths uniform in [0.08, 0.25]), so that -- unlike the
+    box room of fragment_set, whose walls all look alike -- a local shape descriptor tells places apart.  Every fragment draws n_points
+    samples with xy uniform in [0.1, 2.9]^2 and the analytic normals; fragment k is expressed in a frame turned by angles_deg[k] about a
+    seeded axis through (1.5, 1.5, 1.5) and shifted by up to shifts[k] metres per axis.
+    Returns [(xyz float32 [n, 3], normals float32 [n, 3], world_T_frag float64 4x4)], as fragment_set does."""
+    rs = np.random.RandomState(seed)
+    bumps = (rs.uniform(0.2, 2.8, size=(n_bumps, 2)), rs.uniform(-0.12, 0.12, size=n_bumps), rs.uniform(0.08, 0.25, size=n_bumps))
+    out = []
+    for k in range(num):
+        rk = np.random.RandomState(seed + 1 + k)
+        xy = rk.uniform(0.1, 2.9, size=(n_points, 2))
+        z, nrm = relief_height(xy, bumps)
+        world = np.concatenate([xy, z[:, None]], axis=1)
+        ax = rk.normal(size=3)
+        ax /= np.linalg.norm(ax)
+        ang = math.radians(angles_deg[k % len(angles_deg)])
+        K = np.array([[0, -ax[2], ax[1]], [ax[2], 0, -ax[0]], [-ax[1], ax[0], 0]])
+        R = np.eye(3) + math.sin(ang) * K + (1 - math.cos(ang)) * (K @ K)
+        ctr = np.array([1.5, 1.5, 1.5])
+        F = np.eye(4)                                                            # world_T_frag: a fragment point p is the world point R p + t
+        F[:3, :3] = R
+        F[:3, 3] = ctr - R @ ctr + rk.uniform(-1.0, 1.0, size=3) * shifts[k % len(shifts)]
+        Fi = np.linalg.inv(F)
+        out.append(((world @ Fi[:3, :3].T + Fi[:3, 3]).astype(np.float32), (nrm @ Fi[:3, :3].T).astype(np.float32), F))
+    return out
+
+
 def perturbation(seed, max_rot_deg=2.0, max_trans=0.02):
     """Small seeded rigid perturbation (4x4 float64)."""
     rng = np.random.RandomState(seed)

@@ -394,6 +394,42 @@ int er_ransac_align(er_cloud_t src, er_cloud_t tgt, er_features_t src_feat, er_f
                     float T_out[16], int* converged, int* n_inliers, double* error, er_ransac_stats* stats, er_ransac_aux* aux,
                     int aux_capacity, int* aux_count);
 
+/* ---- GlobalRegistration: the first half of do_all (GlobalRegistration.cpp:59-128) -- voxel-grid downsampling, normal and FPFH
+ * estimation -- once per fragment, from a cloud that is already on the device.  The PCL calls are pinned to the float64 restatement of
+ * tests/fpfh_restatement.py (PCL itself is not vendored).  A radius neighbourhood of point i: every point j of the same cloud whose
+ * float32 squared distance ((dx*dx) + dy*dy) + dz*dz is < fl32(r * r), i itself included.  Every result is a function of the cloud and
+ * the parameters alone: the same bits from run to run.  All entry points return an error -- never fault -- for NULL handles, an empty
+ * cloud and a leaf or radius that is not positive and finite; the two radius queries also refuse a cloud that spans more than 4000 cells
+ * of that radius along one axis (beyond it the float32 cell coordinates no longer guarantee exact membership). ---- */
+
+/* The cloud's rows back on the host, in file order (either pointer may be NULL): [n][3] floats each. */
+int er_cloud_read(er_cloud_t c, float* xyz_host, float* normal_host);
+
+/* pcl::VoxelGrid<PointNT> at leaf (:59-68; all fields averaged, min_points_per_voxel 0): inv = fl32(1 / leaf), ijk = floor(fl32(x * inv)),
+ * key = (i - min_i) + (j - min_j) div_x + (k - min_k) div_x div_y; one output point per occupied key in ascending key order, each of
+ * x, y, z, nx, ny, nz the mean of the cell's members (float64 sum in file order / count, rounded to float32 once; normals are not
+ * renormalised).  *out is a new cloud with a search grid for grid_cell; *n_out (nullable) its size.  Refused: a grid of more than
+ * INT_MAX cells, where PCL warns and returns the cloud unfiltered. */
+int er_cloud_voxel_grid(er_cloud_t in, float leaf, float grid_cell, er_cloud_t* out, int* n_out);
+
+/* pcl::NormalEstimation at radius followed by the flip of :93-116: per point the float64 centroid and scatter matrix of its
+ * neighbourhood, the unit eigenvector of the smallest eigenvalue, negated if its float64 dot product with the point's input normal is
+ * < 0, rounded to float32.  Fewer than 3 neighbours: NaN (PCL leaves what its solver returns for a rank-deficient matrix).  *out: the same
+ * points with the new normals and the input's grid cell; the input is not changed.  n_neighbours_host (nullable): [n] neighbourhood sizes. */
+int er_cloud_estimate_normals(er_cloud_t in, float radius, er_cloud_t* out, int* n_neighbours_host);
+
+/* pcl::FPFHEstimation at radius (:121-128) over the cloud's own points and normals, pair features and sums in float64.
+ * SPFH of point i: integer counts [3][11] of the bins of (f1, f2, f3) = computePairFeatures(i, j) over its neighbours j != i, failed pairs
+ * skipped; m_i = neighbours - 1; row = count * 100 / m_i.  FPFH of i: per bin the sum over neighbours j with d^2 != 0 of
+ * spfh_j[bin] * (1 / d^2), every block of 11 scaled to sum 100, rounded to float32; a zero row for a point whose own normal is not finite.
+ * *out: 33-dimensional features, row i for point i.  spfh_counts_host (nullable): int [n][33]; n_neighbours_host (nullable): int [n],
+ * the point itself included. */
+int er_fpfh_estimate(er_cloud_t c, float radius, er_features_t* out, int* spfh_counts_host, int* n_neighbours_host);
+
+/* The descriptors back on the host: [n][er_features_dim] floats. */
+int er_features_dim(er_features_t f);
+int er_features_read(er_features_t f, float* feat_host);
+
 /* Frees the pooled ICP workspaces (streams, scratch, pinned blocks).  Optional; call when no ICP call is running. */
 int er_icp_release_workspaces(void);
 
