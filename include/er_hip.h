@@ -343,7 +343,7 @@ int er_features_destroy(er_features_t f);
 int er_features_size(er_features_t f);
 
 /* findSimilarFeatures' nearestKSearch (RansacCurvature.h:373-387) for EVERY source descriptor at once: its k nearest target
- * descriptors by brute force, 1 <= k <= 8 <= n_tgt.  Distance = float32 sum of squared differences in ascending dimension; ascending
+ * descriptors by brute force, 1 <= k <= 8 and k <= n_tgt.  Distance = float32 sum of squared differences in ascending dimension; ascending
  * distance, ties to the lower target index.  idx_host / sqdist_host (either may be NULL): [n_src][k]. */
 int er_feature_knn(er_features_t src, er_features_t tgt, int k, int* idx_host, float* sqdist_host);
 

@@ -58,6 +58,15 @@ def _sqdist32(a, b):
     return (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
 
 
+def edge_ok(ds, dt, simsq):
+    """thresholdEdgeLength on float32 squared lengths: the shorter over the longer >= simsq.  0 / 0 is NaN and fails."""
+    ds, dt = np.asarray(ds, np.float32), np.asarray(dt, np.float32)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        sim = np.where(ds < dt, ds / dt, dt / ds)
+    assert sim.dtype == np.float32
+    return sim >= np.float32(simsq)
+
+
 def polygon_ok(src_xyz, tgt_xyz, s, c, similarity):
     """thresholdPolygon over all pairs of edges, float32."""
     sx, tx = np.asarray(src_xyz, np.float32), np.asarray(tgt_xyz, np.float32)
@@ -69,9 +78,7 @@ def polygon_ok(src_xyz, tgt_xyz, s, c, similarity):
             for j in range(i + 1, ns):
                 ds = _sqdist32(sx[s[:, i]], sx[s[:, j]])
                 dt = _sqdist32(tx[c[:, i]], tx[c[:, j]])
-                sim = np.where(ds < dt, ds / dt, dt / ds)
-                assert sim.dtype == np.float32
-                ok &= sim >= simsq
+                ok &= edge_ok(ds, dt, simsq)
     return ok
 
 
@@ -100,18 +107,36 @@ def estimate(src_xyz, tgt_xyz, s, c):
     return M.astype(np.float32), sv
 
 
-def normal_min_dot(M32, src_nrm, tgt_nrm, s, c):
-    """The smallest n_t . (R n_s) of each hypothesis, float32 arithmetic in the library's order."""
+def normal_dots(M32, src_nrm, tgt_nrm, s, c):
+    """n_t . (R n_s) of every sample of every hypothesis: float32 [m, ns], float32 arithmetic in the library's order."""
     sn, tn = np.asarray(src_nrm, np.float32)[s], np.asarray(tgt_nrm, np.float32)[c]          # [m, ns, 3]
     M = np.asarray(M32, np.float32)
+    out = np.zeros(s.shape, np.float32)
+    with np.errstate(invalid="ignore"):
+        for i in range(s.shape[1]):
+            a = sn[:, i]
+            nn = [(M[:, r, 0] * a[:, 0] + M[:, r, 1] * a[:, 1]) + M[:, r, 2] * a[:, 2] for r in range(3)]
+            d = (tn[:, i, 0] * nn[0] + tn[:, i, 1] * nn[1]) + tn[:, i, 2] * nn[2]
+            assert d.dtype == np.float32
+            out[:, i] = d
+    return out
+
+
+def normal_min_dot(M32, src_nrm, tgt_nrm, s, c):
+    """The smallest n_t . (R n_s) of each hypothesis (for printing margins; NaN as soon as one sample's is -- normal_ok is the test)."""
+    d = normal_dots(M32, src_nrm, tgt_nrm, s, c)
     out = np.full(s.shape[0], np.inf, np.float32)
     for i in range(s.shape[1]):
-        a = sn[:, i]
-        nn = [(M[:, r, 0] * a[:, 0] + M[:, r, 1] * a[:, 1]) + M[:, r, 2] * a[:, 2] for r in range(3)]
-        d = (tn[:, i, 0] * nn[0] + tn[:, i, 1] * nn[1]) + tn[:, i, 2] * nn[2]
-        assert d.dtype == np.float32
-        out = np.minimum(out, d)
+        out = np.minimum(out, d[:, i])
     return out
+
+
+def normal_ok(M32, src_nrm, tgt_nrm, s, c, cos_a):
+    """thresholdNormal sample by sample: a hypothesis is rejected if and only if some sample has n_t . (R n_s) < cos_a, compared in
+    float64.  A NaN dot product is not below anything, so a sample with a NaN normal never rejects -- and never hides another that does."""
+    d = normal_dots(M32, src_nrm, tgt_nrm, s, c).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        return ~(d < cos_a).any(axis=1)
 
 
 def propose(seed, it0, it1, n_src, ns, knn, src_xyz, tgt_xyz, similarity, block=250000):
@@ -156,7 +181,7 @@ def align(src_xyz, src_nrm, tgt_xyz, tgt_nrm, knn, scorer, max_iterations, nr_sa
         if not len(its):
             continue
         M32, _ = estimate(src_xyz, tgt_xyz, s, c)
-        keep = ~(normal_min_dot(M32, src_nrm, tgt_nrm, s, c).astype(np.float64) < cos_a) & ~np.isnan(M32[:, :3, :]).any(axis=(1, 2))
+        keep = normal_ok(M32, src_nrm, tgt_nrm, s, c, cos_a) & ~np.isnan(M32[:, :3, :]).any(axis=(1, 2))
         its, M32 = its[keep], M32[keep]
         sc = [scorer(M) for M in M32]
         cnt = np.array([x[0] for x in sc], np.int64)
@@ -172,7 +197,8 @@ def align(src_xyz, src_nrm, tgt_xyz, tgt_nrm, knn, scorer, max_iterations, nr_sa
 
 
 def feature_knn(src_f, tgt_f, k, block=512):
-    """float64 brute force: (indices [n, k], squared distances [n, k]); candidates from the expanded form, ranked by the difference form."""
+    """float64 brute force: (indices [n, k], squared distances [n, k]); candidates from the expanded form, ranked by the difference form;
+    equal distances go to the lower index, also where more targets tie than a row has places."""
     a, b = np.asarray(src_f, np.float64), np.asarray(tgt_f, np.float64)
     kk = min(b.shape[0], k + 8)
     bb = (b * b).sum(axis=1)
@@ -181,7 +207,10 @@ def feature_knn(src_f, tgt_f, k, block=512):
     for r0 in range(0, a.shape[0], block):
         x = a[r0:r0 + block]
         d2 = (x * x).sum(axis=1)[:, None] + bb[None] - 2.0 * (x @ b.T)
-        cand = np.sort(np.argpartition(d2, kk - 1, axis=1)[:, :kk], axis=1)               # ascending index: a stable sort then breaks ties downwards
+        thr = np.partition(d2, kk - 1, axis=1)[:, kk - 1:kk]                                # every target as close as the kk-th, however many tie with it
+        far = d2 > thr + 1e-9 * (np.abs(thr) + (x * x).sum(axis=1)[:, None] + bb.max())
+        m = int((~far).sum(axis=1).max())
+        cand = np.sort(np.argsort(far, axis=1, kind="stable")[:, :m], axis=1)             # ascending index: a stable sort then breaks ties downwards
         dd = ((x[:, None, :] - b[cand]) ** 2).sum(axis=2)
         o = np.argsort(dd, axis=1, kind="stable")[:, :k]
         idx[r0:r0 + block] = np.take_along_axis(cand, o, axis=1)

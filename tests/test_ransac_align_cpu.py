@@ -74,6 +74,36 @@ def test_generator_and_select_samples_restatement():
     assert abs(u.mean() - 0.5) < 0.01 and abs(np.corrcoef(u[:-1], u[1:])[0, 1]) < 0.03
 
 
+def test_normal_test_is_per_sample_and_a_nan_normal_never_rejects():
+    """thresholdNormal (RansacCurvature.h:192-202) tests each sample on its own: `nt.dot(nn) < cos` is false for a NaN, so a NaN normal
+    neither rejects nor shields a bad sample next to it.  Folding the dot products with a NaN-propagating minimum first, as the
+    restatement once did, keeps the first case below."""
+    nan = np.float32(np.nan)
+    c30 = np.cos(np.float64(np.float32(0.52359878)))
+    good, bad = [0.0, 0.0, 1.0], [0.0, np.sin(1.0), np.cos(1.0)]                             # against a target normal z: dot 1 and cos(1 rad) = 0.54
+    for ns in (3, 4, 6):
+        src = np.array([[nan] * 3, bad, good, [nan, 0.0, 1.0]] + [good] * 4, np.float32)
+        tgt = np.zeros((8, 3), np.float32)
+        tgt[:, 2] = 1.0
+        tgt_nan = tgt.copy()
+        tgt_nan[:] = nan
+        M = np.broadcast_to(np.eye(4, dtype=np.float32), (5, 4, 4))
+        rest = [2, 4, 5, 6, 7]
+        s = np.array([[0, 1] + rest[:ns - 2],                                                # one NaN sample and one below the cosine
+                      [1, 0] + rest[:ns - 2],                                                # the same, the bad one first
+                      [0] + rest[:ns - 1],                                                   # one NaN sample, the others above
+                      [3] + rest[:ns - 1],                                                   # (one NaN component is a NaN sample)
+                      rest[:ns - 1] + [1]])                                                  # no NaN, one below
+        c = np.broadcast_to(np.arange(ns), s.shape)
+        new = rr.normal_ok(M, src, tgt, s, c, c30)
+        with np.errstate(invalid="ignore"):
+            old = ~(rr.normal_min_dot(M, src, tgt, s, c).astype(np.float64) < c30)
+        assert list(new) == [False, False, True, True, False]
+        assert list(old) == [True, True, True, True, False]                                  # what the folded minimum gave: it differs in the first kind
+        assert rr.normal_ok(M, np.full_like(src, nan), tgt, s, c, c30).all()                 # all samples NaN: kept
+        assert rr.normal_ok(M, src, tgt_nan, s, c, c30).all()
+
+
 def test_restatement_alone_registers_the_common_scene():
     from oracle.pyoracle import IcpOracle
     sc = rr.common_scene(2)
