@@ -1,8 +1,8 @@
-// er_fpfh.h -- the first half of GlobalRegistration's do_all on the device (included at the end of er_icp.hip: it shares er_cloud_s, the
-// chunk grid builder, the workspace pool and er_features_s): pcl::VoxelGrid at resample_leaf (GlobalRegistration.cpp:59-68),
+// er_fpfh.hip -- the first half of GlobalRegistration's do_all on the device (it shares er_cloud_s, er_features_s and the chunk grid builder
+// through er_cloud.h and, through er::StreamLease, the workspace pool of er_icp.hip): pcl::VoxelGrid at resample_leaf (GlobalRegistration.cpp:59-68),
 // pcl::NormalEstimationOMP with the sign flip against the input normals (:81-117) and pcl::FPFHEstimationOMP (:121-128), once per
 // fragment and from the cloud that is already in HBM.  The PCL calls are pinned to the restatement of tests/fpfh_restatement.py.
-//   k_vox_keys / hipcub sort / k_vox_heads / hipcub scan / k_vox_starts / k_vox_mean
+//   k_vox_keys / hipcub sort / k_vox_heads / hipcub scan / k_vox_starts / k_vox_mean      (hipcub through er::sort_pairs_u32 / er::inclusive_sum_i32)
 //                     one key per point, a stable sort, the segment of every occupied cell, one float64 mean per cell and component
 //   k_fp_normals      one wave per point: neighbour centroid, float64 covariance, smallest eigenvector, sign from the input normal
 //   k_fp_spfh         one wave per point: the three pair features against every neighbour -> 3 x 11 INTEGER counts in LDS
@@ -15,9 +15,14 @@
 // Every result is a function of the cloud and the radius alone: a wave walks the nine ranges in a fixed order, candidate s of a range goes to
 // lane (s - first) % 64, cross-lane sums are xor butterflies (the same bits in every lane), the histogram is integer, and k_fp_fpfh adds
 // its neighbours one after the other in candidate order.  No float atomics.
+#include "er_cloud.h"
 #include "er_fpfh_math.h"
 
+#include <algorithm>
 #include <climits>
+#include <cmath>
+
+using namespace er;
 
 namespace {
 
@@ -293,30 +298,18 @@ int er_cloud_voxel_grid(er_cloud_t in, float leaf, float grid_cell, er_cloud_t* 
   if (fp_bad_length(leaf)) return er::fail("er_cloud_voxel_grid: leaf %g must be positive and finite", (double)leaf);
   if (fp_bad_length(grid_cell)) return er::fail("er_cloud_voxel_grid: grid_cell %g must be positive and finite", (double)grid_cell);
   const int n = in->n;
-  GroupLease L;
+  StreamLease L;
   if (L.acquire(in->device)) return 1;
-  hipStream_t st = L.g->stream;
+  hipStream_t st = L.stream;
   DevBufs B;
   // the cloud's bounding box (k_chunk_bounds of the grid builder), then min_b / max_b = the cell of its corners: x -> floor(fl32(x * inv)) is monotonic
-  int* d_box;
-  ER_HIP_TRY(B.alloc(&d_box, 8 * sizeof(int)));
-  int box[8] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN, 0, 0};
-  ER_HIP_TRY(hipMemcpyAsync(d_box, box, sizeof box, hipMemcpyHostToDevice, st));
-  ChunkDesc D{};
-  D.m = 1;
-  D.n[0] = n;
-  D.pt_off[1] = n;
-  D.xyz[0] = in->xyz;
-  D.nrm[0] = in->nrm;
-  hipLaunchKernelGGL(k_chunk_bounds, dim3(std::min(nblocks_of(n), 128), 1), dim3(kBlock), 0, st, D, d_box);
-  ER_HIP_TRY(hipGetLastError());
-  ER_HIP_TRY(hipMemcpyAsync(box, d_box, sizeof box, hipMemcpyDeviceToHost, st));
-  ER_HIP_TRY(hipStreamSynchronize(st));
+  float box_lo[3], box_hi[3];
+  if (er::cloud_bounds(in, st, box_lo, box_hi)) return 1;
   VoxDims V;
   V.inv = 1.0f / leaf;
   double cells = 1.0;
   for (int a = 0; a < 3; a++) {
-    const float lo = ordered_float(box[a]), hi = ordered_float(box[3 + a]);
+    const float lo = box_lo[a], hi = box_hi[a];
     if (!(std::fabs((double)(lo * V.inv)) < 2.0e9) || !(std::fabs((double)(hi * V.inv)) < 2.0e9))
       return er::fail("er_cloud_voxel_grid: leaf %g is too small for this cloud: the cell indices overflow an int (PCL returns the cloud unfiltered)", (double)leaf);
     V.min_b[a] = er_fp::voxel_index(lo, V.inv);
@@ -337,17 +330,17 @@ int er_cloud_voxel_grid(er_cloud_t in, float leaf, float grid_cell, er_cloud_t* 
   ER_HIP_TRY(B.alloc(&head, (size_t)n * sizeof(int)));
   ER_HIP_TRY(B.alloc(&seg, (size_t)n * sizeof(int)));
   size_t need_sort = 0, need_scan = 0;
-  ER_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need_sort, k0, k1, x0, x1, n, 0, bits, st));
-  ER_HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, need_scan, head, seg, n, st));
+  ER_HIP_TRY(er::sort_pairs_u32(nullptr, need_sort, k0, k1, x0, x1, n, 0, bits, st));
+  ER_HIP_TRY(er::inclusive_sum_i32(nullptr, need_scan, head, seg, n, st));
   size_t tmp_bytes = std::max(need_sort, need_scan);
   char* tmp;
   ER_HIP_TRY(B.alloc(&tmp, tmp_bytes));
   hipLaunchKernelGGL(k_vox_keys, dim3(nblocks_of(n)), dim3(kBlock), 0, st, in->xyz, n, V, k0, x0);
   size_t t = tmp_bytes;
-  ER_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, t, k0, k1, x0, x1, n, 0, bits, st));       // stable: a cell's members stay in file order
+  ER_HIP_TRY(er::sort_pairs_u32(tmp, t, k0, k1, x0, x1, n, 0, bits, st));       // stable: a cell's members stay in file order
   hipLaunchKernelGGL(k_vox_heads, dim3(nblocks_of(n)), dim3(kBlock), 0, st, k1, n, head);
   t = tmp_bytes;
-  ER_HIP_TRY(hipcub::DeviceScan::InclusiveSum(tmp, t, head, seg, n, st));
+  ER_HIP_TRY(er::inclusive_sum_i32(tmp, t, head, seg, n, st));
   ER_HIP_TRY(hipGetLastError());
   int m = 0;
   ER_HIP_TRY(hipMemcpyAsync(&m, seg + (n - 1), sizeof(int), hipMemcpyDeviceToHost, st));
@@ -376,9 +369,9 @@ int er_cloud_estimate_normals(er_cloud_t in, float radius, er_cloud_t* out, int*
   const int n = in->n;
   CloudHolder T;
   if (fp_radius_grid(in, radius, &T, "er_cloud_estimate_normals")) return 1;
-  GroupLease L;
+  StreamLease L;
   if (L.acquire(in->device)) return 1;
-  hipStream_t st = L.g->stream;
+  hipStream_t st = L.stream;
   DevBufs B;
   float* nrm;
   int* nn;
@@ -400,9 +393,9 @@ int er_fpfh_estimate(er_cloud_t c, float radius, er_features_t* out, int* spfh_c
   const int n = c->n;
   CloudHolder T;
   if (fp_radius_grid(c, radius, &T, "er_fpfh_estimate")) return 1;
-  GroupLease L;
+  StreamLease L;
   if (L.acquire(c->device)) return 1;
-  hipStream_t st = L.g->stream;
+  hipStream_t st = L.stream;
   DevBufs B;
   int *counts, *nn;
   ER_HIP_TRY(B.alloc(&counts, (size_t)n * er_fp::kDim * sizeof(int)));

@@ -1,5 +1,5 @@
 // er_fpfh_math.h -- the per-point and per-pair arithmetic of the voxel grid, the normal estimation and the FPFH descriptor
-// (er_fpfh.h), free of HIP types so that the same text compiles for the device and, for checking, for the host:
+// (er_fpfh.hip), free of HIP types so that the same text compiles for the device and, for checking, for the host:
 //   voxel_index      pcl::VoxelGrid's cell coordinate of one axis (GlobalRegistration.cpp:63-68)
 //   smallest_eigvec  pcl::NormalEstimation's plane fit: the eigenvector of the smallest eigenvalue of a symmetric 3x3 (:89-92)
 //   pair_bins        pcl::computePairFeatures and the three histogram bins of FPFHEstimation (:121-128)

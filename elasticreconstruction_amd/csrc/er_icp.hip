@@ -5,17 +5,12 @@
 // PCL semantics follow SURVEY.md Appendix B (PCL 1.7; the library itself is not vendored -- see
 // oracle/icp_oracle.cpp's header for what is assumed and DESIGN.md "parity unpinned").
 //
-// Data layout in HBM (one er_cloud_s per fragment, uploaded once, reused by every pair):
-//   xyz, nrm     float[3n] in file order (the cloud as SOURCE; NaN-normal points already dropped)
-//   sorted       float4[n] = {x, y, z, bit_cast(original index)} ordered by grid cell
-//   cell_start   int[cells+1]   uniform grid, cell edge >= the largest search radius, so an exact
-//                               nearest neighbour inside the radius lies in the 3x3x3 neighbourhood;
-//                               cell id = (z*ny + y)*nx + x, so each (z,y) row is ONE contiguous range
-// plus GROUP workspaces (streams, per-pair descriptors and ICP states, scratch slabs cut into one slice per pair) borrowed from a
-// per-device pool, so clouds are immutable and any number of pair lists can be in flight.
+// The clouds (one er_cloud_s per fragment, uploaded once, reused by every pair: layout and grid build in er_cloud.hip) are immutable; what a list of
+// pairs needs while it is processed are GROUP workspaces (streams, per-pair descriptors and ICP states, scratch slabs cut into one slice per pair) borrowed
+// from a per-device pool, so any number of pair lists can be in flight.  er_ransac.hip and er_fpfh.hip borrow their stream from the same pool (er::StreamLease).
 // Queries run in the SOURCE cloud's own cell-sorted order (thread t takes sorted[t]), so the lanes of a wave
 // walk the same few target cells together (coalesced / broadcast candidate loads); results are written back
-// by original index.  The NN search is block-cooperative (see nn_block); candidates stream from L2 as 16-byte loads.
+// by original index.  The NN search is block-cooperative (nn_block, er_nn.h); candidates stream from L2 as 16-byte loads.
 // Every stage processes a whole GROUP of pairs per launch (blockIdx.y = pair; "pair groups" below):
 //   k_count_inliers   transform (float64 -> float32) + NN + count           (Registration pre-check)
 //   k_icp_iter        one ICP iteration: [apply guess / last increment] + NN + point-to-plane rows -> 27+2 float64 sums
@@ -24,14 +19,10 @@
 //   k_find_corr       transform points+normals + NN + distance/normal tests -> match[orig index];
 //                     k_count_blocks (+ information-matrix sums) + k_scan_blocks + k_compact = stable compaction in file order
 // Reductions and scans, not contractions: no MFMA.
-#include "er_common.h"
-
-#include "../../include/er_hip.h"
-
-#include <hipcub/hipcub.hpp>   // device radix sort / prefix sum of the grid build (library primitives; everything else is hand-written)
+#include "er_cloud.h"
+#include "er_nn.h"
 
 #include <algorithm>
-#include <atomic>
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
@@ -40,239 +31,16 @@
 #include <thread>
 #include <vector>
 
+using namespace er;
+
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kAcc = 32;   // 21 ATA + 6 ATb + sum d^2 + count (+ padding)
-
-// PairDev carries its pointers through memory, so the compiler emits FLAT loads for them (64-bit VALU address arithmetic, both wait counters).
-// The hot accesses go through explicitly GLOBAL pointer types: global_load with a scalar base and a 32-bit offset, vmcnt only.
-typedef float f4v __attribute__((ext_vector_type(4)));
-#define ER_GLOBAL __attribute__((address_space(1)))
-typedef const ER_GLOBAL f4v* gp_f4;
-typedef const ER_GLOBAL float* gp_f;
-typedef const ER_GLOBAL int* gp_i;
-typedef ER_GLOBAL float* gp_fw;
-typedef ER_GLOBAL int* gp_iw;
-#define ER_GP(type, ptr) ((type)(ptr))
-
-// The grid carries TWO RINGS OF EMPTY CELLS around the cloud's bounding box (cell (x, y, z) of the box is cell (x + 2, y + 2, z + 2) of the array).  A query is
-// searched only if its home cell lies within one cell of the box, so every cell of its 27-neighbourhood EXISTS -- no flags, range tests or clamps -- and
-// the four bounds L, O, R, E of a row's three cells x-1, x, x+1 are four consecutive ints of cell_start: one 16-byte load per row.
-// (What was tried on this search and dropped, with numbers: profiles/HISTORY.md "Path B: the search, rounds 3-6".)
-constexpr int kPadBatch = 4;   // rows whose four bounds are in flight at a time (4 registers per row; 8 = all rows: +11 VGPRs, within the noise)
-typedef int i4v __attribute__((ext_vector_type(4), aligned(4)));   // (the four bounds of a row start at an arbitrary cell: 4-byte alignment only)
-struct Grid {
-  const float4* pts;
-  const int* cell_start;
-  float org[3];
-  float cell;
-  int dim[3];      // cells of the bounding box per axis (the array has dim + 4 per axis: two rings of empty cells)
-  float slack;     // absolute part of nn_block's pruning margin (square metres), from the grid's extent: grid_slack()
-  int pnx, pny;    // dim[0] + 4, dim[1] + 4: strides of the padded array
-  const unsigned char* occ;   // [cells] 1 = some cell of this cell's 27-neighbourhood holds a point (round 6; see nn_block)
-};
-
-// The pruning margin of nn_block.  A cell (or row of cells) is skipped when the squared distance f'^2 from the query to its nearest face, as the
-// kernel computes it, exceeds  B * (1 + 1e-4) + slack,  B = the best float32 squared distance so far (or the squared search radius).  For that to
-// be exact -- no point p of a skipped cell may have a float32 distance below B -- the margin has to cover what the float32 cell arithmetic can be
-// off by:  u = fl(fl(q - org) / cell) carries a relative error of 2 x 2^-24, i.e. up to 1.2e-7 x |q - org| metres in the face distance, and the
-// target points were assigned to their cells by the same expression, so the face itself is that fuzzy once more:  f' <= f + D  per axis with
-// D = 2.5e-7 x (largest extent + 2 cells) + 4e-9, and sqrt(3) D for the rows and corners that combine two or three axes.  With S^2 = B (1 + r) + A,
-// a skipped point has a true distance >= S - sqrt(3) D, its float32 squared distance is >= (S - sqrt(3) D)^2 (1 - 3e-7), and
-// 2 S sqrt(3) D <= (r / 4) S^2 + 12 D^2 / r  gives  (S - sqrt(3) D)^2 (1 - 3e-7) >= B  as soon as  A >= 1.2001e5 D^2  (r = 1e-4); the code takes 1.3e5.
-// (A constant absolute part would cover D only for best distances below a micrometre or above several millimetres; tests/test_icp_gpu.py builds the
-// queries in between on purpose.)
-inline float grid_slack(const int dim[3], float cell) {
-  const int big = std::max(dim[0], std::max(dim[1], dim[2]));
-  const double D = 2.5e-7 * (double)(big + 2) * (double)cell + 4e-9;
-  return (float)(1.3e5 * D * D);
-}
 
 struct Mat12d { double m[12]; };
 struct Mat12f { float m[12]; };
 
-// Exact 1-NN of q among the target points of the 27 neighbouring cells: float32 squared distance ((dx*dx) + dy*dy) + dz*dz (FLANN L2_Simple), ties ->
-// lower original index.  limit2 = squared search radius: callers discard anything farther, so cells lying entirely beyond it are skipped (margin: 1e-4
-// relative plus an absolute part sized from the grid's extent, see grid_slack).
-// Block-cooperative, two phases (one query per thread, kBlock queries per workgroup):
-//   phase 0  the thread scans its query's own cell, then the left / right cell of the home row if its face is closer than the best so far; the eight
-//            neighbour rows are trimmed by the same face tests and their NON-EMPTY ranges go to an LDS task list as (first candidate, count, query);
-//   phase 1  the workgroup shares the list -- one range per thread and trip -- folding results into the query's packed (distance bits, index) key with a
-//            64-bit LDS atomicMin, which IS the lexicographic (distance, index) minimum.
-// Why: ~1.7 of the 8 neighbour rows survive for an average query, but a SIMT loop runs every row ANY lane needs; compacting the survivors across the
-// workgroup removes that waste.  Candidates are scanned kUnroll at a time (the 16-byte loads are issued together).  What bounds it (counters,
-// profiles/r04w_*, r05f_*): VALU issue in the straight-line part every query runs (~360 of ~735 instructions per slice of 64 queries) and LDS traffic per task.
-constexpr int kUnroll = 4;
-constexpr unsigned long long kNoHit = ((unsigned long long)0x7f7fffffu << 32) | 0xffffffffull;   // (FLT_MAX, -1)
-
-constexpr int kTaskCap = kBlock * 4;   // (query, row) tasks of phase 1 held in LDS; a task beyond that is scanned by the thread that found it
-
-struct NnShared {
-  unsigned long long best[kBlock];
-  float q[3][kBlock];
-  int task_s0[kTaskCap];          // first candidate of the task's range in the cell-sorted target
-  int task_nq[kTaskCap];          // candidates << 8 | query
-  int ntask;
-};
-
-// Candidates [s0, s1) of the cell-sorted target against the query: the packed (distance bits, index) minimum -- every candidate against the key, exact by
-// construction; ~54 VALU instructions per trip of four, 20 of them the selection.
-// The kU loads of a trip are NOT clamped to the range: a trip that starts inside [s0, s1) may read up to kU - 1 entries past s1.  Those are points of the
-// cells that follow in the cell-sorted array -- REAL points of the same cloud, so the minimum over the wider set is still the exact nearest neighbour --
-// or, behind the cloud's last point, the kSentinel entries of +inf er_cloud_create appends (distance inf / NaN: a bit pattern that never wins).
-constexpr int kSentinel = 8;            // float4 entries of +inf behind every cloud's sorted array (>= the largest kU - 1)
-template <int kU = kUnroll>
-__device__ __forceinline__ unsigned long long scan_range(const Grid& g, int s0, int s1, float qx, float qy, float qz, unsigned long long key) {
-  // candidates are addressed by UNSIGNED 32-bit byte offsets from the (wave-uniform) base: a scalar-base global load and one 32-bit
-  // add per candidate instead of a sign extension and a 64-bit multiply-add each
-  const ER_GLOBAL char* base = (const ER_GLOBAL char*)g.pts;
-  const unsigned last = (unsigned)(s1 - 1) * 16u;
-  for (unsigned o = (unsigned)s0 * 16u; o <= last && s0 < s1; o += 16u * kU) {
-    f4v p[kU];
-#pragma unroll
-    for (int u = 0; u < kU; u++) p[u] = *(const ER_GLOBAL f4v*)(base + o + 16u * (unsigned)u);
-#pragma unroll
-    for (int u = 0; u < kU; u++) {
-      const float dx = qx - p[u].x, dy = qy - p[u].y, dz = qz - p[u].z;
-      const float d = ((dx * dx) + dy * dy) + dz * dz;
-      // d >= 0, so its bit pattern orders like its value; NaN / inf patterns exceed FLT_MAX's and never win
-      const unsigned long long k = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)__float_as_int(p[u].w);
-      key = k < key ? k : key;
-    }
-  }
-  return key;
-}
-
-// Every thread of the workgroup must call this (it synchronises); `active` = this thread carries a query.
-// Returns the index (or -1) and the squared distance of the nearest target point.  A cell is skipped only when every point in it is provably
-// farther than the best so far: its nearest face already is, with the 1e-4 relative margin of grid_slack; ties cannot hide there.
-// hit2 >= 0 (the Registration pre-check): the caller only needs to know whether ANY target point lies closer than sqrt(hit2) -- "count the points
-// whose nearest neighbour is within reg_dist" is "count the points that have a neighbour within reg_dist" -- so a query stops as soon as it holds a
-// candidate below hit2; the returned distance is then that candidate's, not the minimum.  Queries without one run the full exact search.
-// kU = candidates per trip: 4 where the nearest neighbour is needed, 3 in the any-hit pre-check (profiles/r04t_ab_scan_unroll.txt).
-template <int kU = kUnroll>
-__device__ __forceinline__ int nn_block(NnShared& sh, const Grid& g, bool active, float qx, float qy, float qz, float limit2,
-                                        float& best_d, float hit2 = -1.f) {
-  const int tid = threadIdx.x;
-  __syncthreads();                                            // the previous call's readers are done with `sh`
-  if (tid == 0) sh.ntask = 0;
-  // the query's cell (float32 expressions shared with the grid build)
-  const float ux = (qx - g.org[0]) / g.cell, uy = (qy - g.org[1]) / g.cell, uz = (qz - g.org[2]) / g.cell;
-  const float cx = floorf(ux), cy = floorf(uy), cz = floorf(uz);
-  const bool inside = active && cx >= -1.f && cx <= (float)g.dim[0] && cy >= -1.f && cy <= (float)g.dim[1] && cz >= -1.f && cz <= (float)g.dim[2];
-  const int ix = inside ? (int)cx : 0, iy = inside ? (int)cy : 0, iz = inside ? (int)cz : 0;
-  __syncthreads();                                            // (sh.ntask is zero)
-  unsigned long long key = kNoHit;
-  // A query whose whole 27-neighbourhood is empty (55-63 % of the queries of a fragment pair: the part of the source that does not overlap the target)
-  // has no neighbour within the radius; one byte per cell (k_chunk_occ) says so before the row tests.  Queries come in the source's cell order: whole
-  // waves leave here (9-10 % of the ICP phase, profiles/r06c_*).
-  const bool live = inside && ER_GP(const ER_GLOBAL unsigned char*, g.occ)[(unsigned)(((iz + 2) * g.pny + (iy + 2)) * g.pnx + (ix + 2))] != 0;
-  if (live) {
-    // distance from q to the lower / upper face of its own cell along x, y and z (metres), squared
-    const float xlo = (ux - cx) * g.cell, xhi = g.cell - xlo, ylo = (uy - cy) * g.cell, yhi = g.cell - ylo, zlo = (uz - cz) * g.cell,
-                zhi = g.cell - zlo;
-    const float xl2 = xlo * xlo, xr2 = xhi * xhi;
-    float bound = limit2 * 1.0001f + g.slack;
-    const ER_GLOBAL char* csb = (const ER_GLOBAL char*)g.cell_start;
-    const int pnx = g.pnx, pny = g.pny;
-    int home = ((iz + 2) * pny + (iy + 2)) * pnx + (ix + 1);   // the cell LEFT of the query's own cell: where the four bounds of a row's three cells begin
-    {
-      const i4v h = *(const ER_GLOBAL i4v*)(csb + (unsigned)home * 4u);   // L, O, R, E of the home row
-      key = scan_range<kU>(g, h.y, h.z, qx, qy, qz, key);                  // the query's own cell first
-      bound = fminf(bound, __uint_as_float((unsigned)(key >> 32)) * 1.0001f + g.slack);   // the other cells must beat this one
-      if (__uint_as_float((unsigned)(key >> 32)) < hit2) bound = -1.f;                   // (any-hit mode: done)
-      if (xl2 <= bound) {
-        key = scan_range<kU>(g, h.x, h.y, qx, qy, qz, key);
-        bound = fminf(bound, __uint_as_float((unsigned)(key >> 32)) * 1.0001f + g.slack);
-        if (__uint_as_float((unsigned)(key >> 32)) < hit2) bound = -1.f;
-      }
-      if (xr2 <= bound) {
-        key = scan_range<kU>(g, h.z, h.w, qx, qy, qz, key);
-        bound = fminf(bound, __uint_as_float((unsigned)(key >> 32)) * 1.0001f + g.slack);
-        if (__uint_as_float((unsigned)(key >> 32)) < hit2) bound = -1.f;
-      }
-    }
-    sh.q[0][tid] = qx;
-    sh.q[1][tid] = qy;
-    sh.q[2][tid] = qz;
-    // the eight neighbour rows: wave-uniform steps away from the home row, every one of them inside the array -- all eight 16-byte loads are issued
-    // up front behind one wait (a row that does not survive the test below is loaded anyway: no address select)
-    asm volatile("" : "+v"(home));                            // (opaque, or the compiler folds the steps back into y and z)
-    const float yl2 = ylo * ylo, yh2 = yhi * yhi, zl2 = zlo * zlo, zh2 = zhi * zhi;
-    int r_s0[8], r_n[8];
-#pragma unroll
-    for (int j0 = 0; j0 < 8; j0 += kPadBatch) {                 // (kPadBatch rows' bounds in flight at a time: 4 registers per row)
-      i4v rb[kPadBatch];
-#pragma unroll
-      for (int jj = 0; jj < kPadBatch; jj++) {
-        const int j = j0 + jj, pass = j < 4 ? j : j + 1;
-        const int dy = pass % 3 - 1, dz = pass / 3 - 1;
-        rb[jj] = *(const ER_GLOBAL i4v*)(csb + (unsigned)(home + (dz * pny + dy) * pnx) * 4u);
-      }
-#pragma unroll
-      for (int jj = 0; jj < kPadBatch; jj++) {
-        const int j = j0 + jj, pass = j < 4 ? j : j + 1;
-        const int dy = pass % 3 - 1, dz = pass / 3 - 1;
-        const float e2 = (dy < 0 ? yl2 : (dy > 0 ? yh2 : 0.f)) + (dz < 0 ? zl2 : (dz > 0 ? zh2 : 0.f));
-        const bool wl = xl2 + e2 <= bound, wr = xr2 + e2 <= bound;
-        const int s0 = wl ? rb[jj].x : rb[jj].y, s1 = wr ? rb[jj].w : rb[jj].z;
-        r_s0[j] = s0;
-        r_n[j] = e2 <= bound ? s1 - s0 : 0;
-        asm volatile("" : "+v"(r_s0[j]), "+v"(r_n[j]));         // materialised HERE: the four bounds die now (left alone, the compiler sinks the selects
-      }                                                        // to each row's push and keeps all 32 bound registers alive across the fallback scans)
-      __builtin_amdgcn_sched_barrier(0);                       // (... and the scheduler hoists all eight loads above the first batch's selects)
-    }
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      const int n = r_n[j];
-      if (n > 0) {
-        const int t = n < (1 << 23) ? atomicAdd(&sh.ntask, 1) : kTaskCap;
-        if (t < kTaskCap) {
-          sh.task_s0[t] = r_s0[j];
-          sh.task_nq[t] = (n << 8) | tid;
-        } else {                                              // the task list is full (or the range does not fit the packing): scan it here
-          key = scan_range<kU>(g, r_s0[j], r_s0[j] + n, qx, qy, qz, key);
-        }
-      }
-    }
-  }
-  sh.best[tid] = key;
-  __syncthreads();
-  const int nt = min(sh.ntask, kTaskCap);
-  for (int t = tid; t < nt; t += kBlock) {
-    const int s0 = sh.task_s0[t], nq = sh.task_nq[t], q = nq & 255;
-    const unsigned long long k = scan_range<kU>(g, s0, s0 + (nq >> 8), sh.q[0][q], sh.q[1][q], sh.q[2][q], kNoHit);
-    atomicMin(&sh.best[q], k);
-  }
-  __syncthreads();
-  key = sh.best[tid];
-  best_d = __uint_as_float((unsigned)(key >> 32));
-  return (int)(unsigned)(key & 0xffffffffull);              // 0xffffffff -> -1
-}
-
-using NnSh = NnShared;
 constexpr int kPrecheckUnroll = 3;   // candidates per trip of the any-hit pre-check (see nn_block)
-
-// Block reduction of NV float64 values per thread: wave shuffle (64 lanes) -> LDS -> lane 0 atomics.
-template <int NV>
-__device__ __forceinline__ void block_reduce_atomic(double (&v)[NV], double* __restrict__ out) {
-  __shared__ double part[kBlock / 64][NV];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < NV; i++) {
-    double s = v[i];
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
-    if (lane == 0) part[wave][i] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < NV) {
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; w++) s += part[w][threadIdx.x];
-    if (s != 0.0) atomicAdd(&out[threadIdx.x], s);
-  }
-}
 
 // pcl::transformPointCloudWithNormals with a Matrix4d: float64 evaluation, float32 storage.
 __device__ __forceinline__ void xform_d(const Mat12d& T, float x, float y, float z, float& ox, float& oy, float& oz) {
@@ -995,216 +763,6 @@ __global__ __launch_bounds__(kBlock) void k_compact(const PairDev* __restrict__ 
   }
 }
 
-// ---- uniform grids of a CHUNK of clouds, built on the device ---------------------------------------------------------------
-// (the reference builds a kd-tree per pair and per function, CorresApp.cpp:129,238; here once per fragment)
-// Up to kCloudChunk clouds go through ONE set of launches (round 4; before, every cloud had its own ~23 launches and a list of fragments was bound by
-// the host's launch rate, not by PCIe: profiles/r04y_cloud_build_timeline.txt):
-//   k_chunk_bounds  per cloud (blockIdx.y): min / max of the coordinates (float bits mapped to ordered ints, block reduce, 7 atomics per
-//                   workgroup) + a non-finite flag;
-//   k_chunk_cells   cell id of every point (the same float32 expression nn_block evaluates for a query) -> key = cloud << shift | cell, the
-//                   histogram of every cloud's cells in one concatenated array [ncell_0 + 1 | ncell_1 + 1 | ...], and the interleaved
-//                   {point, normal} records;
-//   hipcub          ONE stable radix sort of (key, position in the chunk) and ONE prefix sum over the concatenated histograms: element 0 of
-//                   cloud k's segment holds -n_(k-1), which cancels the running total at the segment's start, so every segment comes out as that
-//                   cloud's own cell_start (0 ... n_k);
-//   k_chunk_gather  sorted[s] = {x, y, z, original index within its cloud}; the clouds' sorted arrays are consecutive pieces of one array.
-// A stable sort keeps the points of a cell in file order, like a counting sort on the host would: the layout -- and with it the
-// order of every float64 reduction that walks the cloud -- is reproducible from run to run, and the same for a cloud built alone or in a list.
-__device__ __forceinline__ int ordered_int(float f) {
-  const int i = __float_as_int(f);
-  return i >= 0 ? i : i ^ 0x7fffffff;
-}
-__host__ __device__ __forceinline__ float ordered_float(int i) {
-  const int b = i >= 0 ? i : i ^ 0x7fffffff;
-  float f;
-  memcpy(&f, &b, sizeof f);
-  return f;
-}
-
-constexpr int kCloudChunk = 8;          // clouds per chunk (3 key bits above the cell id)
-struct GridDims {
-  float org[3];
-  float cell;
-  int dim[3];
-};
-struct ChunkDesc {                      // passed by value (kernel argument)
-  int m;                                // clouds in the chunk
-  int shift;                            // key = cloud << shift | cell
-  int n[kCloudChunk];
-  int pt_off[kCloudChunk + 1];          // prefix sum of n: a point's position in the chunk
-  long cs_off[kCloudChunk + 1];         // prefix sum of (cells + 1): where a cloud's cell_start begins in the chunk's array
-  const float* xyz[kCloudChunk];
-  const float* nrm[kCloudChunk];
-  float4* xn[kCloudChunk];
-  GridDims G[kCloudChunk];
-};
-
-__global__ __launch_bounds__(kBlock) void k_chunk_bounds(ChunkDesc D, int* __restrict__ out8) {
-  const int y = blockIdx.y, n = D.n[y];
-  const float* __restrict__ xyz = D.xyz[y];
-  int* out7 = out8 + 8 * y;
-  int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {INT_MIN, INT_MIN, INT_MIN};
-  int bad = 0, nmax = 0;                                        // nmax: bits of the largest finite |normal component| (both uploads are in: stage A)
-  const float* __restrict__ nrm = D.nrm[y];
-  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      const float v = xyz[3 * (size_t)i + a];
-      bad |= !isfinite(v);
-      const int o = ordered_int(v);
-      lo[a] = min(lo[a], o);
-      hi[a] = max(hi[a], o);
-      const float nv = fabsf(nrm[3 * (size_t)i + a]);
-      if (isfinite(nv)) nmax = max(nmax, __float_as_int(nv));
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1) nmax = max(nmax, __shfl_down(nmax, off));
-  if ((threadIdx.x & 63) == 0 && nmax > 0) atomicMax(&out8[8 * y + 7], nmax);
-#pragma unroll
-  for (int a = 0; a < 3; a++)
-    for (int off = 32; off > 0; off >>= 1) {
-      lo[a] = min(lo[a], __shfl_down(lo[a], off));
-      hi[a] = max(hi[a], __shfl_down(hi[a], off));
-    }
-  bad = __any(bad) ? 1 : 0;
-  __shared__ int part[kBlock / 64][7];
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      part[wave][a] = lo[a];
-      part[wave][3 + a] = hi[a];
-    }
-    part[wave][6] = bad;
-  }
-  __syncthreads();
-  if (threadIdx.x < 7 && (int)blockIdx.x * kBlock < n) {       // 7 atomics per workgroup that saw points
-    int v = part[0][threadIdx.x];
-    for (int w = 1; w < kBlock / 64; w++)
-      v = threadIdx.x < 3 ? min(v, part[w][threadIdx.x]) : (threadIdx.x < 6 ? max(v, part[w][threadIdx.x]) : (v | part[w][threadIdx.x]));
-    if (threadIdx.x < 3) atomicMin(&out7[threadIdx.x], v);
-    else if (threadIdx.x < 6) atomicMax(&out7[threadIdx.x], v);
-    else if (v) atomicOr(&out7[6], 1);
-  }
-}
-
-// xn[2 i] = {x, y, z, 0}, xn[2 i + 1] = {nx, ny, nz, 0} in file order: the matched target point of k_icp_iter is one aligned
-// 32-byte record = one cache line instead of two 12-byte gathers from two arrays (those were ~30 % of an ICP iteration).
-__global__ __launch_bounds__(kBlock) void k_chunk_cells(ChunkDesc D, unsigned* __restrict__ key, unsigned* __restrict__ idx, int* __restrict__ count) {
-  const int y = blockIdx.y, n = D.n[y];
-  int* __restrict__ cnt = count + D.cs_off[y];
-  if (blockIdx.x == 0 && threadIdx.x == 0) cnt[0] = y > 0 ? -D.n[y - 1] : 0;   // (see the prefix sum above; nothing else touches element 0)
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  const float* __restrict__ xyz = D.xyz[y];
-  const float* __restrict__ nrm = D.nrm[y];
-  const GridDims G = D.G[y];
-  const float p[3] = {xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2]};
-  int q[3];
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    q[a] = (int)floorf((p[a] - G.org[a]) / G.cell);
-    q[a] = min(max(q[a], 0), G.dim[a] - 1);
-  }
-  const int c = ((q[2] + 2) * (G.dim[1] + 4) + (q[1] + 2)) * (G.dim[0] + 4) + (q[0] + 2);   // two rings of empty cells around the box (struct Grid)
-  const unsigned g = (unsigned)(D.pt_off[y] + i);
-  key[g] = ((unsigned)y << D.shift) | (unsigned)c;
-  idx[g] = g;
-  atomicAdd(&cnt[c + 1], 1);                                 // integer histogram: the result does not depend on the order
-  float4* __restrict__ xn = D.xn[y];
-  xn[2 * (size_t)i] = make_float4(p[0], p[1], p[2], 0.f);
-  xn[2 * (size_t)i + 1] = make_float4(nrm[3 * (size_t)i], nrm[3 * (size_t)i + 1], nrm[3 * (size_t)i + 2], 0.f);
-}
-
-__global__ __launch_bounds__(kBlock) void k_chunk_gather(ChunkDesc D, const unsigned* __restrict__ key, const unsigned* __restrict__ idx, int total,
-                                                         float4* __restrict__ sorted) {
-  const int s = blockIdx.x * kBlock + threadIdx.x;
-  if (s >= total) return;
-  const int y = (int)(key[s] >> D.shift);
-  const int i = (int)idx[s] - D.pt_off[y];
-  const float* __restrict__ xyz = D.xyz[y];
-  float4* __restrict__ out = sorted + (size_t)s + (size_t)kSentinel * (size_t)y;       // kSentinel entries of +inf behind every cloud (scan_range)
-  *out = make_float4(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], __int_as_float(i));
-  if (s + 1 == D.pt_off[y + 1]) {                                // the cloud's last point in sorted order also writes the sentinels
-    const float inf = __int_as_float(0x7f800000);
-    for (int k = 1; k <= kSentinel; k++) out[k] = make_float4(inf, inf, inf, __int_as_float(-1));
-  }
-}
-
-// occ[c] = 1 iff some cell of c's 3 x 3 x 3 neighbourhood holds a point (c over the padded array; cells of the outermost ring get 0: no query is searched
-// from there).  One thread per cell, nine row sums of three cells each from the finished cell_start.
-__global__ __launch_bounds__(kBlock) void k_chunk_occ(ChunkDesc D, const int* __restrict__ cell_start, unsigned char* __restrict__ occ) {
-  const int y = blockIdx.y;
-  const GridDims G = D.G[y];
-  const int pnx = G.dim[0] + 4, pny = G.dim[1] + 4, pnz = G.dim[2] + 4;
-  const long ncell = (long)pnx * pny * pnz;
-  const long c = (long)blockIdx.x * kBlock + threadIdx.x;
-  if (c >= ncell) return;
-  const int* __restrict__ cs = cell_start + D.cs_off[y];
-  const int x = (int)(c % pnx), yy = (int)((c / pnx) % pny), z = (int)(c / ((long)pnx * pny));
-  int any = 0;
-  if (x >= 1 && x <= pnx - 2 && yy >= 1 && yy <= pny - 2 && z >= 1 && z <= pnz - 2) {
-#pragma unroll
-    for (int dz = -1; dz <= 1; dz++)
-#pragma unroll
-      for (int dy = -1; dy <= 1; dy++) {
-        const long row = ((long)(z + dz) * pny + (yy + dy)) * pnx + x;
-        any |= cs[row + 2] - cs[row - 1];                       // points in cells x-1 .. x+1 of that row
-      }
-  }
-  occ[D.cs_off[y] + c] = any ? 1 : 0;
-}
-
-
-// Grow-only scratch of the grid build, one per device, handed out under a mutex (er_cloud_create may be called from
-// several host threads; builds on one device then take turns).
-struct GridScratch {
-  std::mutex mu;
-  int device = -1;
-  unsigned *key[4] = {nullptr, nullptr, nullptr, nullptr}, *idx[4] = {nullptr, nullptr, nullptr, nullptr};   // two sets: [2 lane], [2 lane + 1]
-  void* cub[2] = {nullptr, nullptr};
-  int *bounds = nullptr, *h_bounds = nullptr;                   // 8 ints per cloud of a batch: device and its page-locked mirror (+ the initial pattern)
-  size_t n_cap = 0, cub_cap = 0, bounds_cap = 0;
-  hipStream_t up[2] = {nullptr, nullptr};                       // uploads: coordinates on one, normals on the other (two DMA engines keep the link busy)
-  hipStream_t cs2[2] = {nullptr, nullptr};                      // grid kernels: consecutive chunks alternate between two lanes
-  hipStream_t bs = nullptr;                                     // the bounding boxes of EVERY chunk (stage A): waits for uploads never sit in front of a grid
-  hipEvent_t lane_ev = nullptr;
-  std::vector<hipEvent_t> ev;                                   // three per chunk of a batch: uploads done (two streams), bounds back
-};
-GridScratch& grid_scratch(int device) {
-  static GridScratch* tab = new GridScratch[64];             // intentionally leaked (see WsPool)
-  return tab[device & 63];
-}
-
-// One device allocation shared by the clouds of a chunk (freed with the last of them).
-struct CloudSlab {
-  void* p = nullptr;
-  std::atomic<int> refs{0};
-};
-void slab_release(CloudSlab* sl) {
-  if (sl && sl->refs.fetch_sub(1) == 1) {
-    if (sl->p) (void)hipFree(sl->p);
-    delete sl;
-  }
-}
-
-}  // namespace
-
-struct er_cloud_s {
-  int device = 0, n = 0;
-  float *xyz = nullptr, *nrm = nullptr;
-  float4* sorted = nullptr;
-  float4* xn = nullptr;         // [2n] file order: {x, y, z, 0}, {nx, ny, nz, 0} -- ONE 32-byte gather per matched point in k_icp_iter
-  int* cell_start = nullptr;
-  Grid grid{};
-  float radius_cap = 0.f;       // largest search radius the grid supports
-  float nmax = 1.f;             // largest finite |normal component| (k_chunk_bounds): bounds the ICP sums (PairDev::fx_scale)
-  CloudSlab *pts_slab = nullptr, *cell_slab = nullptr;   // the chunk's allocations these pointers live in
-};
-
-namespace {
-Grid grid_of(const er_cloud_s* c) { return c->grid; }
-
 // ---- group workspaces ----------------------------------------------------------------------------
 // Everything a GROUP of pairs needs while it is being processed (clouds are immutable and shared): one compute stream and one
 // copy stream, the per-pair descriptors and ICP states (device + pinned host mirrors), small per-pair result arrays, and slabs of
@@ -1278,7 +836,6 @@ void group_destroy(Group* g) {
   delete g;
 }
 
-int nblocks_of(int n) { return (std::max(n, 1) + kBlock - 1) / kBlock; }
 constexpr int kPrecheckWgs = 16384;    // workgroups of one k_count_inliers launch (each strides over its pair's slices; 8192: +3 % time, 32768: the same)
 // Slices of 256 points per workgroup of k_icp_iter when `blocks` slices are to be searched in one launch (the 29 cross-lane sums are paid
 // once per workgroup, so more slices per workgroup are cheaper as long as the launch still fills the chip).
@@ -1373,15 +930,18 @@ Group* group_acquire(int device) {
   return g;
 }
 
+void group_release(Group* g) {
+  if (g->stream) (void)hipStreamSynchronize(g->stream);
+  if (g->copy_stream) (void)hipStreamSynchronize(g->copy_stream);
+  if (g->copy_stream2) (void)hipStreamSynchronize(g->copy_stream2);
+  std::lock_guard<std::mutex> lock(pool().mu);
+  pool().idle.push_back(g);
+}
+
 struct GroupLease {             // RAII: the group of one API call
   Group* g = nullptr;
   ~GroupLease() {
-    if (!g) return;
-    if (g->stream) (void)hipStreamSynchronize(g->stream);
-    if (g->copy_stream) (void)hipStreamSynchronize(g->copy_stream);
-    if (g->copy_stream2) (void)hipStreamSynchronize(g->copy_stream2);
-    std::lock_guard<std::mutex> lock(pool().mu);
-    pool().idle.push_back(g);
+    if (g) group_release(g);
   }
   int acquire(int device) {
     g = group_acquire(device);
@@ -1391,14 +951,6 @@ struct GroupLease {             // RAII: the group of one API call
 
 // Pairs per group: bounded by the per-point scratch (32 bytes per source point and pair).  ER_ICP_GROUP overrides (tests use small groups).
 static int group_cfg() { const char* e = getenv("ER_ICP_GROUP"); int v = e ? atoi(e) : 64; return v < 1 ? 1 : (v > 1024 ? 1024 : v); }
-
-int check_pair(er_cloud_t src, er_cloud_t tgt, double radius, const char* who) {
-  if (!src || !tgt) return er::fail("%s: NULL cloud", who);
-  if (src->device != tgt->device) return er::fail("%s: source and target live on different devices", who);
-  if (!(radius > 0.0) || radius > (double)tgt->radius_cap * (1.0 + 1e-6))
-    return er::fail("%s: search radius %g exceeds the target's grid cell %g (er_cloud_create grid_cell)", who, radius, (double)tgt->radius_cap);
-  return 0;
-}
 
 int batch_prologue(int n, const er_cloud_t* src, const er_cloud_t* tgt, double radius, const char* who, int* device) {
   if (n < 0 || (n > 0 && (!src || !tgt))) return er::fail("%s: bad arguments", who);
@@ -1456,7 +1008,7 @@ int group_describe(Group* g, int i0, int m, const er_cloud_t* src, const er_clou
     memset(&P, 0, sizeof P);
     P.src_sorted = s->sorted; P.src_xyz = s->xyz; P.src_nrm = s->nrm;
     P.tgt_xyz = t->xyz; P.tgt_nrm = t->nrm; P.tgt_xn = t->xn;
-    P.g = grid_of(t);
+    P.g = t->grid;
     if (T16)
       for (int c = 0; c < 12; c++) P.T.m[c] = T16[(size_t)(i0 + q) * 16 + c];
     P.n = s->n; P.nb = nblocks_of(s->n); P.nbi = nparts_of(s->n, pts); P.pts = pts;
@@ -1540,342 +1092,19 @@ constexpr int kIcpChunk = 4;
 
 }  // namespace
 
-// Clouds of a LIST of fragments (BuildCorrespondence's LoadData loop, CorresApp.cpp:82-110, builds them one after the other), in chunks of up to
-// kCloudChunk clouds that share two device allocations and ONE set of grid launches:
-//   stage A, for every chunk up front: the chunk's allocation, its uploads -- coordinates and normals on two copy streams, truly asynchronous
-//            when the caller's arrays are page-locked (er_host_alloc) -- and its bounding boxes on a compute lane as soon as the uploads are in;
-//   stage B, chunk by chunk: ONE host wait for the boxes (the host sizes the grids from them), then cell ids + histogram + interleave, one
-//            radix sort, one prefix sum, one gather for the whole chunk, while the later chunks are still uploading.
-// The list is PCIe-bound; before round 4's last step it was bound by the host's launch rate (23 launches per cloud).
-// `kind`: where the rows come from -- hipMemcpyHostToDevice (er_cloud_create / er_cloud_create_batch) or hipMemcpyDeviceToDevice (rows that a
-// kernel on this device has left complete, er::cloud_create_device); everything behind the copy is the same.
-static int cloud_create_impl(int n_clouds, const float* const* xyz_host, const float* const* normal_host, const int* counts, float grid_cell, int device,
-                             er_cloud_t* out, hipMemcpyKind kind) {
-  if (n_clouds < 0 || (n_clouds > 0 && (!xyz_host || !normal_host || !counts || !out))) return er::fail("er_cloud_create: bad arguments");
-  for (int i = 0; i < n_clouds; i++) out[i] = nullptr;
-  for (int i = 0; i < n_clouds; i++)
-    if (counts[i] < 0 || (counts[i] > 0 && (!xyz_host[i] || !normal_host[i]))) return er::fail("er_cloud_create: bad arguments (cloud %d)", i);
-  // the search kernels address candidates, matched-target records and the ICP loop's X by UNSIGNED 32-bit byte offsets (s * 16, i * 32, k * 12: struct
-  // PairDev's hot accesses): a cloud must stay below 2^27 points, or those offsets wrap and the kernels read other memory
-  for (int i = 0; i < n_clouds; i++)
-    if (counts[i] >= (1 << 27)) return er::fail("er_cloud_create: cloud %d has %d points; the limit is 2^27 - 1 (32-bit byte offsets in the search kernels)", i, counts[i]);
-  if (!(grid_cell > 0.f)) return er::fail("er_cloud_create: grid_cell must be positive");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return er::fail("er_cloud_create: no HIP device available (liber_hip has no CPU fallback)");
-  if (device < 0 || device >= ndev) return er::fail("er_cloud_create: device %d out of range [0,%d)", device, ndev);
-  if (n_clouds == 0) return 0;
-  ER_HIP_TRY(hipSetDevice(device));
-  GridScratch& gs = grid_scratch(device);
-  std::lock_guard<std::mutex> lock(gs.mu);
-  auto sync_all = [&]() -> hipError_t {
-    hipError_t e = hipSuccess;
-    for (hipStream_t st : {gs.up[0], gs.up[1], gs.cs2[0], gs.cs2[1], gs.bs})
-      if (st) {
-        const hipError_t e1 = hipStreamSynchronize(st);
-        if (e == hipSuccess) e = e1;
-      }
-    return e;
-  };
-  auto undo = [&]() {
-    (void)sync_all();
-    for (int i = 0; i < n_clouds; i++) {
-      if (out[i]) er_cloud_destroy(out[i]);
-      out[i] = nullptr;
-    }
-  };
-#define ER_CTRY(expr)                                                                         \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess) {                                                                   \
-      er::fail("er_cloud_create: %s failed: %s", #expr, hipGetErrorString(e_));               \
-      undo();                                                                                 \
-      return 1;                                                                               \
-    }                                                                                         \
-  } while (0)
-  for (int q = 0; q < 2; q++) {
-    if (!gs.up[q]) ER_CTRY(hipStreamCreateWithFlags(&gs.up[q], hipStreamNonBlocking));
-    if (!gs.cs2[q]) ER_CTRY(hipStreamCreateWithFlags(&gs.cs2[q], hipStreamNonBlocking));
-    if (!gs.bs) ER_CTRY(hipStreamCreateWithFlags(&gs.bs, hipStreamNonBlocking));
-  }
-  if (!gs.lane_ev) ER_CTRY(hipEventCreateWithFlags(&gs.lane_ev, hipEventDisableTiming));
-  // ---- the chunks: consecutive clouds, at most kCloudChunk of them and kChunkPoints points (the first cloud of a chunk always fits) ----
-  constexpr long kChunkPoints = 16L << 20;
-  struct Chunk {
-    int i0 = 0, i1 = 0;
-    long total = 0;                     // points
-    CloudSlab *pts = nullptr, *cells = nullptr;
-    float4* sorted = nullptr;           // the chunk's sorted array (the clouds' pieces are consecutive)
-    ChunkDesc D{};
-  };
-  std::vector<Chunk> chunks;
-  {
-    // a chunk takes half of what is left (at most kCloudChunk): the list ends in small chunks, and what remains to be done after the
-    // last upload -- the last chunk's grids -- is short (25 fragments: 8, 8, 5, 2, 1, 1)
-    for (int i = 0; i < n_clouds;) {
-      Chunk c;
-      c.i0 = i;
-      const int per = std::min(kCloudChunk, std::max(1, (n_clouds - i + 1) / 2));
-      while (i < n_clouds && i - c.i0 < per && (i == c.i0 || c.total + counts[i] <= kChunkPoints)) c.total += counts[i++];
-      c.i1 = i;
-      chunks.push_back(c);
-    }
-  }
-  const int n_chunks = (int)chunks.size();
-  while ((int)gs.ev.size() < 3 * n_chunks) {
-    hipEvent_t e = nullptr;
-    ER_CTRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    gs.ev.push_back(e);
-  }
-  if (gs.bounds_cap < (size_t)n_clouds) {
-    ER_CTRY(sync_all());
-    if (gs.bounds) (void)hipFree(gs.bounds);
-    if (gs.h_bounds) (void)hipHostFree(gs.h_bounds);
-    gs.bounds = gs.h_bounds = nullptr;
-    gs.bounds_cap = 0;
-    const size_t cap = (size_t)n_clouds + 16;
-    ER_CTRY(hipMalloc((void**)&gs.bounds, cap * 8 * sizeof(int)));
-    ER_CTRY(hipHostMalloc((void**)&gs.h_bounds, cap * 16 * sizeof(int), hipHostMallocDefault));   // [cap][8] results, then [cap][8] initial pattern
-    gs.bounds_cap = cap;
-  }
-  long t_max = 0;
-  for (const Chunk& c : chunks) t_max = std::max(t_max, c.total);
-  if (t_max >= (1L << 31) - kBlock) return er::fail("er_cloud_create: a cloud of %ld points is beyond the 32-bit point index", t_max);
-  if (t_max > 0) {
-    if (gs.n_cap < (size_t)t_max) {
-      ER_CTRY(sync_all());
-      for (int q = 0; q < 4; q++) {
-        if (gs.key[q]) (void)hipFree(gs.key[q]);
-        if (gs.idx[q]) (void)hipFree(gs.idx[q]);
-        gs.key[q] = gs.idx[q] = nullptr;
-      }
-      gs.n_cap = 0;
-      const size_t cap = (size_t)t_max + (size_t)t_max / 8;
-      for (int q = 0; q < 4; q++) {
-        ER_CTRY(hipMalloc((void**)&gs.key[q], cap * sizeof(unsigned)));
-        ER_CTRY(hipMalloc((void**)&gs.idx[q], cap * sizeof(unsigned)));
-      }
-      gs.n_cap = cap;
-    }
-    // temporary storage of the sort / scan for the largest chunk and the largest grids (2^25 cells and 3 cloud bits: 28 key bits) this call can meet
-    size_t need_sort = 0, need_scan = 0;
-    ER_CTRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need_sort, gs.key[0], gs.key[1], gs.idx[0], gs.idx[1], (int)t_max, 0, 28, gs.cs2[0]));
-    ER_CTRY(hipcub::DeviceScan::InclusiveSum(nullptr, need_scan, (int*)nullptr, (int*)nullptr, kCloudChunk * ((1 << 25) + 1), gs.cs2[0]));
-    const size_t need = std::max(need_sort, need_scan);
-    if (gs.cub_cap < need) {
-      ER_CTRY(sync_all());
-      for (int q = 0; q < 2; q++) {
-        if (gs.cub[q]) (void)hipFree(gs.cub[q]);
-        gs.cub[q] = nullptr;
-      }
-      gs.cub_cap = 0;
-      for (int q = 0; q < 2; q++) ER_CTRY(hipMalloc(&gs.cub[q], need + need / 4));
-      gs.cub_cap = need + need / 4;
-    }
-  }
-  int* h_got = gs.h_bounds;
-  int* h_init = gs.h_bounds + gs.bounds_cap * 8;
-  for (int i = 0; i < n_clouds; i++) {
-    const int init[8] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN, 0, 0};
-    memcpy(h_init + (size_t)i * 8, init, sizeof init);
-  }
-  ER_CTRY(hipMemcpyAsync(gs.bounds, h_init, (size_t)n_clouds * 8 * sizeof(int), hipMemcpyHostToDevice, gs.cs2[0]));
-  ER_CTRY(hipEventRecord(gs.lane_ev, gs.cs2[0]));
-  ER_CTRY(hipStreamWaitEvent(gs.cs2[1], gs.lane_ev, 0));
-  ER_CTRY(hipStreamWaitEvent(gs.bs, gs.lane_ev, 0));            // (the boxes' initial pattern is in place before the first bounds kernel)
-  // ---- stage A of a chunk: allocation, uploads (two copy streams), bounding boxes (the chunk's compute lane) ----
-  auto stage_a = [&](int ch) -> int {
-    Chunk& C = chunks[(size_t)ch];
-    const int m = C.i1 - C.i0;
-    const size_t N = (size_t)C.total;
-    // one allocation: [sorted N float4 + kSentinel entries of +inf behind every cloud (scan_range) | xn 2N float4 (32-byte aligned records) | per cloud: xyz 3n,
-    // normals 3n floats]
-    const size_t xn_base = (N + (size_t)kSentinel * (size_t)m + 1) & ~(size_t)1;
-    const size_t f_base = (xn_base + 2 * N) * 4;
-    const size_t bytes = std::max((f_base + 6 * N) * sizeof(float), (size_t)256);
-    C.pts = new CloudSlab();
-    hipError_t e = hipMalloc(&C.pts->p, bytes);
-    if (e != hipSuccess) {
-      delete C.pts;
-      C.pts = nullptr;
-      return er::fail("er_cloud_create: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-    }
-    C.pts->refs = m;
-    C.sorted = static_cast<float4*>(C.pts->p);
-    float* fbase = static_cast<float*>(C.pts->p) + f_base;
-    C.D.m = m;
-    long off = 0;
-    for (int k = 0; k < m; k++) {                                 // the cloud objects first: from here on undo() releases the allocation through them
-      const int i = C.i0 + k, n = counts[i];
-      er_cloud_t c = new er_cloud_s();
-      out[i] = c;
-      c->device = device;
-      c->n = n;
-      c->radius_cap = grid_cell;
-      c->pts_slab = C.pts;
-      c->sorted = C.sorted + off + (long)kSentinel * k;
-      c->xn = C.sorted + xn_base + 2 * off;
-      c->xyz = fbase + 6 * off;
-      c->nrm = c->xyz + 3 * (size_t)n;
-      C.D.n[k] = n;
-      C.D.pt_off[k] = (int)off;
-      C.D.xyz[k] = c->xyz;
-      C.D.nrm[k] = c->nrm;
-      C.D.xn[k] = c->xn;
-      off += n;
-    }
-    C.D.pt_off[m] = (int)off;
-    for (int k = 0; k < m; k++) {
-      const int i = C.i0 + k, n = counts[i];
-      if (n > 0) {
-        ER_HIP_TRY(hipMemcpyAsync(out[i]->xyz, xyz_host[i], (size_t)n * 3 * sizeof(float), kind, gs.up[0]));
-        ER_HIP_TRY(hipMemcpyAsync(out[i]->nrm, normal_host[i], (size_t)n * 3 * sizeof(float), kind, gs.up[1]));
-      }
-    }
-    // Stage A runs on a stream of its own (round 5): on the two grid lanes the upload waits of chunk 2, 4, ... were queued IN FRONT of
-    // chunk 0's grid (in-order streams; every stage A is enqueued before the first stage B), so "built while the later chunks are still uploading" mostly
-    // did not happen.  Stage B of a chunk starts after the HOST has seen the chunk's boxes (ev[3 ch + 2]), hence after its uploads.
-    hipStream_t L = gs.bs;
-    for (int q = 0; q < 2; q++) {
-      ER_HIP_TRY(hipEventRecord(gs.ev[(size_t)(3 * ch + q)], gs.up[q]));
-      ER_HIP_TRY(hipStreamWaitEvent(L, gs.ev[(size_t)(3 * ch + q)], 0));
-    }
-    int n_big = 0;
-    for (int k = 0; k < m; k++) n_big = std::max(n_big, C.D.n[k]);
-    if (n_big > 0)
-      hipLaunchKernelGGL(k_chunk_bounds, dim3(std::min(nblocks_of(n_big), 128), m), dim3(kBlock), 0, L, C.D, gs.bounds + (size_t)C.i0 * 8);
-    ER_HIP_TRY(hipGetLastError());
-    ER_HIP_TRY(hipMemcpyAsync(h_got + (size_t)C.i0 * 8, gs.bounds + (size_t)C.i0 * 8, (size_t)m * 8 * sizeof(int), hipMemcpyDeviceToHost, L));
-    ER_HIP_TRY(hipEventRecord(gs.ev[(size_t)(3 * ch + 2)], L));
-    return 0;
-  };
-  // ---- stage B: the grids of the chunk (its boxes are back) ----
-  auto stage_b = [&](int ch) -> int {
-    Chunk& C = chunks[(size_t)ch];
-    const int m = C.i1 - C.i0;
-    ER_HIP_TRY(hipEventSynchronize(gs.ev[(size_t)(3 * ch + 2)]));
-    long cs_total = 0;
-    int max_cells = 1;
-    for (int k = 0; k < m; k++) {
-      er_cloud_t c = out[C.i0 + k];
-      const int n = c->n;
-      const int* got = h_got + (size_t)(C.i0 + k) * 8;
-      float cell = grid_cell * 1.001f;                            // strictly larger than any admissible radius
-      float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-      int dim[3] = {1, 1, 1};
-      if (n > 0) {
-        if (got[7] > 0) memcpy(&c->nmax, &got[7], sizeof(float));
-        if (got[6]) return er::fail("er_cloud_create: non-finite coordinates");
-        for (int a = 0; a < 3; a++) {
-          lo[a] = ordered_float(got[a]);
-          hi[a] = ordered_float(got[3 + a]);
-        }
-      }
-      constexpr int kRing = 4;                                    // two rings of empty cells per axis (struct Grid)
-      for (;;) {
-        long total = 1;
-        for (int a = 0; a < 3; a++) {
-          dim[a] = (int)std::floor((hi[a] - lo[a]) / cell) + 1;
-          total *= dim[a] + kRing;
-        }
-        if (total <= (1L << 25)) break;
-        cell *= 2.f;
-      }
-      const int ncell = (dim[0] + kRing) * (dim[1] + kRing) * (dim[2] + kRing);
-      max_cells = std::max(max_cells, ncell);
-      C.D.cs_off[k] = cs_total;
-      cs_total += (long)ncell + 1;
-      c->grid.cell = cell;
-      for (int a = 0; a < 3; a++) {
-        c->grid.org[a] = C.D.G[k].org[a] = lo[a];
-        c->grid.dim[a] = C.D.G[k].dim[a] = dim[a];
-      }
-      C.D.G[k].cell = cell;
-      c->grid.slack = grid_slack(dim, cell);
-      c->grid.pnx = dim[0] + 4;
-      c->grid.pny = dim[1] + 4;
-    }
-    C.D.cs_off[m] = cs_total;
-    C.cells = new CloudSlab();
-    const size_t cells_bytes = (size_t)cs_total * sizeof(int) + (size_t)cs_total;   // cell_start of the chunk's clouds, then one occupancy byte per cell
-    hipError_t e = hipMalloc(&C.cells->p, cells_bytes);
-    if (e != hipSuccess) {
-      delete C.cells;
-      C.cells = nullptr;
-      return er::fail("er_cloud_create: hipMalloc(%zu) failed: %s", cells_bytes, hipGetErrorString(e));
-    }
-    C.cells->refs = m;
-    int* cs = static_cast<int*>(C.cells->p);
-    unsigned char* occ = reinterpret_cast<unsigned char*>(cs + cs_total);
-    for (int k = 0; k < m; k++) {
-      er_cloud_t c = out[C.i0 + k];
-      c->cell_slab = C.cells;
-      c->cell_start = cs + C.D.cs_off[k];
-      c->grid.pts = c->sorted;
-      c->grid.cell_start = c->cell_start;
-      c->grid.occ = occ + C.D.cs_off[k];
-    }
-    int bits = 1;
-    while ((1L << bits) < (long)max_cells) bits++;
-    C.D.shift = bits;
-    const int q = ch & 1;
-    hipStream_t L = gs.cs2[q];
-    unsigned *k0 = gs.key[2 * q], *k1 = gs.key[2 * q + 1], *x0 = gs.idx[2 * q], *x1 = gs.idx[2 * q + 1];
-    ER_HIP_TRY(hipMemsetAsync(cs, 0, (size_t)cs_total * sizeof(int), L));
-    int n_big = 0;
-    for (int k = 0; k < m; k++) n_big = std::max(n_big, C.D.n[k]);
-    hipLaunchKernelGGL(k_chunk_cells, dim3(nblocks_of(n_big), m), dim3(kBlock), 0, L, C.D, k0, x0, cs);
-    size_t tmp = gs.cub_cap;
-    if (C.total > 0) ER_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(gs.cub[q], tmp, k0, k1, x0, x1, (int)C.total, 0, bits + 3, L));
-    tmp = gs.cub_cap;
-    ER_HIP_TRY(hipcub::DeviceScan::InclusiveSum(gs.cub[q], tmp, cs, cs, (int)cs_total, L));
-    hipLaunchKernelGGL(k_chunk_occ, dim3((unsigned)((max_cells + kBlock - 1) / kBlock), m), dim3(kBlock), 0, L, C.D, cs, occ);
-    if (C.total > 0) hipLaunchKernelGGL(k_chunk_gather, dim3(nblocks_of((int)C.total)), dim3(kBlock), 0, L, C.D, k1, x1, (int)C.total, C.sorted);
-    ER_HIP_TRY(hipGetLastError());
-    return 0;
-  };
-  int rc = 0;
-  for (int ch = 0; ch < n_chunks && rc == 0; ch++) rc = stage_a(ch);   // every upload is queued before the first host wait
-  for (int ch = 0; ch < n_chunks && rc == 0; ch++) rc = stage_b(ch);
-  if (rc == 0 && sync_all() != hipSuccess)                              // the caller's arrays and the shared scratch are free again
-    rc = er::fail("er_cloud_create: %s", hipGetErrorString(hipGetLastError()));
-#undef ER_CTRY
-  if (rc) {
-    const std::string why = er_last_error();
-    undo();
-    return er::fail("%s", why.c_str());
-  }
+// er::StreamLease (er_cloud.h): a group of the pool above, of which the borrower sees the compute stream only.
+int er::StreamLease::acquire(int device) {
+  Group* g = group_acquire(device);
+  if (!g) return 1;
+  group_ = g;
+  stream = g->stream;
   return 0;
 }
-
-int er::cloud_create_device(const float* xyz_dev, const float* normal_dev, int n, float grid_cell, int device, er_cloud_s** out) {
-  return cloud_create_impl(1, &xyz_dev, &normal_dev, &n, grid_cell, device, out, hipMemcpyDeviceToDevice);
+er::StreamLease::~StreamLease() {
+  if (group_) group_release(static_cast<Group*>(group_));
 }
 
 extern "C" {
-
-int er_cloud_create_batch(int n_clouds, const float* const* xyz_host, const float* const* normal_host, const int* counts, float grid_cell, int device,
-                          er_cloud_t* out) {
-  return cloud_create_impl(n_clouds, xyz_host, normal_host, counts, grid_cell, device, out, hipMemcpyHostToDevice);
-}
-
-int er_cloud_create(const float* xyz_host, const float* normal_host, int n, float grid_cell, int device, er_cloud_t* out) {
-  if (!out) return er::fail("er_cloud_create: out is NULL");
-  *out = nullptr;
-  if (n < 0 || (n > 0 && (!xyz_host || !normal_host))) return er::fail("er_cloud_create: bad arguments");
-  return er_cloud_create_batch(1, &xyz_host, &normal_host, &n, grid_cell, device, out);
-}
-
-int er_cloud_destroy(er_cloud_t c) {
-  if (!c) return 0;
-  (void)hipSetDevice(c->device);
-  slab_release(c->pts_slab);                    // xyz, normals, sorted and xn live in the chunk's allocation, cell_start in its second one:
-  slab_release(c->cell_slab);                   // both go with the last cloud of the chunk
-  delete c;
-  return 0;
-}
-
-int er_cloud_size(er_cloud_t c) { return c ? c->n : -1; }
 
 int er_icp_release_workspaces(void) {
   std::vector<Group*> v;
@@ -2044,7 +1273,7 @@ int er_ransac_fitness_batch(er_cloud_t src, er_cloud_t tgt, int n_hyp, const flo
       const int bx = std::max(1, std::min(nblocks_of(src->n), 4096 / std::min(n_hyp, 4096)));
       for (int h0 = 0; h0 < n_hyp && rc == 0; h0 += 32768) {
         const int hn = std::min(32768, n_hyp - h0);
-        hipLaunchKernelGGL(k_ransac_fitness, dim3(bx, hn), dim3(kBlock), 0, w->stream, src->sorted, src->n, d_hyp, h0, grid_of(tgt),
+        hipLaunchKernelGGL(k_ransac_fitness, dim3(bx, hn), dim3(kBlock), 0, w->stream, src->sorted, src->n, d_hyp, h0, tgt->grid,
                            corr_dist_threshold, corr_dist_threshold * corr_dist_threshold, d_cnt, d_sum);
         if (hipGetLastError() != hipSuccess) rc = er::fail("er_ransac_fitness_batch: launch failed");
       }
@@ -2355,6 +1584,3 @@ int er_registration_batch(int n, const er_cloud_t* src, const er_cloud_t* tgt, c
 }
 
 }  // extern "C"
-
-#include "er_ransac_search.h"   // GlobalRegistration's RANSAC pose search: shares the cloud types, nn_block and the workspace pool above
-#include "er_fpfh.h"            // GlobalRegistration's voxel grid, normal and FPFH estimation: shares the cloud types, the grid builder and er_features_s above

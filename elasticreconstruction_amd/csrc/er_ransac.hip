@@ -1,5 +1,5 @@
-// er_ransac_search.h -- GlobalRegistration's RANSAC pose search on the device (included at the end of er_icp.hip: it shares the cloud
-// types, the exact nearest-neighbour search nn_block and the workspace pool).  RansacCurvature::computeTransformation
+// er_ransac.hip -- GlobalRegistration's RANSAC pose search on the device (it shares the cloud types of er_cloud.h, the exact
+// nearest-neighbour search nn_block of er_nn.h and, through er::StreamLease, the workspace pool of er_icp.hip).  RansacCurvature::computeTransformation
 // (GlobalRegistration/RansacCurvature.h:411-657) with PolyRejector.h, the per-point features as an input.
 //   k_feature_knn / k_feature_knn_merge   findSimilarFeatures' nearestKSearch for every source descriptor: brute force, the source
 //                        descriptor of a lane in registers, target descriptors through LDS tiles read as broadcasts, top-k in registers
@@ -11,12 +11,16 @@
 //   k_ransac_score       k_ransac_fitness's search over them, hypotheses read from device memory, 64-bit fixed-point distance sums
 //   k_ransac_select      the reference's acceptance rule and the (error, iteration) minimum, carried across chunks; the aux rows
 // Nothing comes back to the host between the chunks: every kernel reads the counts of its predecessor from device memory.
+#include "er_cloud.h"
+#include "er_nn.h"
 #include "er_ransac_math.h"
 
-struct er_features_s {
-  int device = 0, n = 0, dim = 0, dp = 0;     // dp = dim rounded up to a multiple of 8 (rows padded with zeros: they add +0 to a distance)
-  float* d = nullptr;                         // [n][dp]
-};
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <vector>
+
+using namespace er;
 
 namespace {
 
@@ -471,26 +475,6 @@ __global__ __launch_bounds__(kBlock) void k_ransac_select(const int* __restrict_
   }
 }
 
-struct DevBufs {                                   // frees what a call allocated, whatever way it leaves
-  std::vector<void*> p;
-  template <typename T>
-  hipError_t alloc(T** out, size_t bytes) {
-    *out = nullptr;
-    hipError_t e = hipMalloc((void**)out, std::max<size_t>(bytes, 16));
-    if (e == hipSuccess) p.push_back(*out);
-    return e;
-  }
-  ~DevBufs() {
-    for (void* q : p) (void)hipFree(q);
-  }
-};
-
-int no_device(const char* who) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return er::fail("%s: no HIP device available (liber_hip has no CPU fallback)", who);
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -536,7 +520,7 @@ int er_features_size(er_features_t f) { return f ? f->n : -1; }
 int er_feature_knn(er_features_t src, er_features_t tgt, int k, int* idx_host, float* sqdist_host) {
   if (no_device("er_feature_knn")) return 1;
   if (check_features(src, tgt, k, "er_feature_knn")) return 1;
-  GroupLease L;
+  StreamLease L;
   if (L.acquire(src->device)) return 1;
   DevBufs B;
   int* d_idx;
@@ -545,13 +529,13 @@ int er_feature_knn(er_features_t src, er_features_t tgt, int k, int* idx_host, f
   const size_t m = (size_t)src->n * k;
   ER_HIP_TRY(B.alloc(&d_idx, m * sizeof(int)));
   ER_HIP_TRY(B.alloc(&d_dist, m * sizeof(float)));
-  const int rc = feature_knn_device(src, tgt, k, L.g->stream, d_idx, d_dist, &pd, &pi);
+  const int rc = feature_knn_device(src, tgt, k, L.stream, d_idx, d_dist, &pd, &pi);
   if (pd) B.p.push_back(pd);
   if (pi) B.p.push_back(pi);
   if (rc) return 1;
-  if (idx_host) ER_HIP_TRY(hipMemcpyAsync(idx_host, d_idx, m * sizeof(int), hipMemcpyDeviceToHost, L.g->stream));
-  if (sqdist_host) ER_HIP_TRY(hipMemcpyAsync(sqdist_host, d_dist, m * sizeof(float), hipMemcpyDeviceToHost, L.g->stream));
-  ER_HIP_TRY(hipStreamSynchronize(L.g->stream));
+  if (idx_host) ER_HIP_TRY(hipMemcpyAsync(idx_host, d_idx, m * sizeof(int), hipMemcpyDeviceToHost, L.stream));
+  if (sqdist_host) ER_HIP_TRY(hipMemcpyAsync(sqdist_host, d_dist, m * sizeof(float), hipMemcpyDeviceToHost, L.stream));
+  ER_HIP_TRY(hipStreamSynchronize(L.stream));
   return 0;
 }
 
@@ -568,9 +552,9 @@ int er_ransac_hypotheses(er_cloud_t src, er_cloud_t tgt, int n_hyp, int nr_sampl
     if (sample_idx[e] < 0 || sample_idx[e] >= src->n || corr_idx[e] < 0 || corr_idx[e] >= tgt->n)
       return er::fail("er_ransac_hypotheses: hypothesis %d names a point outside its cloud", (int)(e / nr_samples));
   if (n_hyp == 0) return 0;
-  GroupLease L;
+  StreamLease L;
   if (L.acquire(src->device)) return 1;
-  hipStream_t S = L.g->stream;
+  hipStream_t S = L.stream;
   DevBufs B;
   int *d_s, *d_c, *d_st;
   float* d_M;
@@ -626,9 +610,9 @@ int er_ransac_align(er_cloud_t src, er_cloud_t tgt, er_features_t src_feat, er_f
   if (src->n < p->nr_samples) return er::fail("%s: the number of samples (%d) must not be greater than the number of points (%d)", who, p->nr_samples, src->n);
   const int chunk = std::min(p->max_iterations, p->chunk_iterations > 0 ? p->chunk_iterations : (1 << 20));
   const int n = src->n, k = p->k_correspondences, ns = p->nr_samples;
-  GroupLease L;
+  StreamLease L;
   if (L.acquire(src->device)) return 1;
-  hipStream_t S = L.g->stream;
+  hipStream_t S = L.stream;
   DevBufs B;
   int *d_knn, *d_list, *d_status, *d_acc, *d_count;
   float *d_kd, *d_M, *pd = nullptr;
@@ -677,7 +661,7 @@ int er_ransac_align(er_cloud_t src, er_cloud_t tgt, er_features_t src_feat, er_f
     }
 #undef ER_RS_NS
     hipLaunchKernelGGL(k_ransac_accept, dim3(1), dim3(1024), 0, S, d_status, d_acc, d_st, d_count, d_sum);
-    hipLaunchKernelGGL(k_ransac_score, dim3(score_bx, score_by), dim3(kBlock), 0, S, src->sorted, n, d_M, d_acc, d_st, grid_of(tgt), radius, max_range,
+    hipLaunchKernelGGL(k_ransac_score, dim3(score_bx, score_by), dim3(kBlock), 0, S, src->sorted, n, d_M, d_acc, d_st, tgt->grid, radius, max_range,
                        scale, d_count, d_sum);
     hipLaunchKernelGGL(k_ransac_select, dim3(1), dim3(kBlock), 0, S, d_list, d_acc, d_M, d_count, d_sum, d_st, n, p->inlier_fraction, p->inlier_number,
                        inv_scale, d_aux, (long long)aux_capacity);

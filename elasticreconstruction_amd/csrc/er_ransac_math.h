@@ -1,4 +1,4 @@
-// er_ransac_math.h -- the per-hypothesis arithmetic of the RANSAC pose search (er_ransac_search.h), free of HIP types so that the
+// er_ransac_math.h -- the per-hypothesis arithmetic of the RANSAC pose search (er_ransac.hip), free of HIP types so that the
 // same text compiles for the device and, for checking, for the host: the counter-based generator, selectSamples
 // (GlobalRegistration/RansacCurvature.h:319-359), the polygon edge test (PolyRejector.h:262-295), the float64 rigid estimate and
 // thresholdNormal (RansacCurvature.h:192-202).

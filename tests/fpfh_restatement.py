@@ -1,6 +1,6 @@
 """A numpy restatement of the first half of GlobalRegistration's do_all (GlobalRegistration.cpp:59-128): pcl::VoxelGrid, pcl::NormalEstimation
 with the sign flip against the input normals, and pcl::FPFHEstimation -- written from the definitions, not from the kernels.  The kernels
-of csrc/er_fpfh.h are compared with this file, never the other way round.
+of csrc/er_fpfh.hip are compared with this file, never the other way round.
 
 Neighbourhood of point i at radius r: every j whose float32 value ((dx*dx) + dy*dy) + dz*dz is < fl32(r * r); i itself is a member.
 Everything behind the float32 inputs is float64.

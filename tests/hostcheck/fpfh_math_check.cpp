@@ -1,4 +1,4 @@
-// Host build of csrc/er_fpfh_math.h for tests/test_fpfh_cpu.py: the same text the kernels of er_fpfh.h compile, behind a C interface.
+// Host build of csrc/er_fpfh_math.h for tests/test_fpfh_cpu.py: the same text the kernels of er_fpfh.hip compile, behind a C interface.
 #include "er_fpfh_math.h"
 
 extern "C" {

@@ -1,4 +1,4 @@
-// Host build of csrc/er_ransac_math.h for tests/test_ransac_math_cpu.py: the same text the kernels of er_ransac_search.h compile, behind
+// Host build of csrc/er_ransac_math.h for tests/test_ransac_math_cpu.py: the same text the kernels of er_ransac.hip compile, behind
 // a C interface over arrays.
 #include "er_ransac_math.h"
 

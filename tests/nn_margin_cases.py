@@ -1,4 +1,4 @@
-"""Adversarial queries for the pruning margin of the GPU nearest-neighbour search (csrc/er_icp.hip: nn_block, grid_slack): the true nearest neighbour
+"""Adversarial queries for the pruning margin of the GPU nearest-neighbour search (csrc/er_nn.h: nn_block, csrc/er_grid.h: grid_slack): the true nearest neighbour
 sits just behind a cell face, straight along the x axis, and a competitor in the query's OWN cell is farther by a fraction of a micrometre.
 With the absolute margin of rounds 1-4 (1e-12 m^2) the float32 face distance of such a query exceeds the pruning bound and the neighbour's cell
 is skipped; the margin sized from the grid's extent keeps it.  Everything here is float32 arithmetic restated with numpy."""
@@ -12,7 +12,7 @@ def cell_of(v, org, cell):
 
 
 def grid_slack(dim, cell):
-    """csrc/er_icp.hip: grid_slack."""
+    """csrc/er_grid.h: grid_slack."""
     D = 2.5e-7 * (max(dim) + 2) * float(cell) + 4e-9
     return f32(1.3e5 * D * D)
 

@@ -1,12 +1,49 @@
-"""The pruning margin of the GPU nearest-neighbour search (csrc/er_icp.hip: grid_slack), checked on the CPU: the adversarial queries of
+"""The pruning margin of the GPU nearest-neighbour search (csrc/er_grid.h: grid_slack), checked on the CPU: the adversarial queries of
 tests/nn_margin_cases.py defeat the constant 1e-12 of rounds 1-4 in float32 arithmetic, the margin sized from the grid's extent covers them, and the
 oracle (27 cells, no pruning) names the point behind the face as their nearest neighbour.  tests/test_icp_gpu.py runs the same clouds through the HIP path."""
+import ctypes as C
+import os
+import subprocess
+
 import numpy as np
 
 from nn_margin_cases import build, grid_slack
 from oracle.pyoracle import IcpOracle
 
 f32 = np.float32
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _hostlib():
+    """csrc/er_grid.h compiled for the host (tests/hostcheck/grid_slack_check.cpp)."""
+    src = os.path.join(ROOT, "tests", "hostcheck", "grid_slack_check.cpp")
+    inc = os.path.join(ROOT, "elasticreconstruction_amd", "csrc")
+    out = os.path.join(ROOT, "tests", "hostcheck", "_build", "libgrid_slack_check.so")
+    deps = [src, os.path.join(inc, "er_grid.h")]
+    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-I" + inc, src, "-o", out], check=True)
+    lib = C.CDLL(out)
+    lib.gs_grid_slack.restype = C.c_float
+    lib.gs_grid_slack.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float]
+    return lib
+
+
+def test_the_restated_grid_slack_is_the_compiled_one_bit_for_bit():
+    """The margin proved below is proved about nn_margin_cases.grid_slack; this pins that restatement to the C++ the cloud builder calls: the case
+    file's own grid, then the largest axis at 1, 2, 105 and 4096 cells (in every position) for three cell sizes."""
+    lib = _hostlib()
+    _, _, _, _, (_, cell, dim) = build()
+    assert cell == f32(f32(0.03) * f32(1.001))
+    grids = [(list(dim), cell)]
+    for big in (1, 2, 105, 4096):
+        for c in (f32(0.03003), f32(0.1), f32(1.0)):
+            small = max(1, big // 3)
+            grids += [([big, small, 1], c), ([1, big, small], c), ([small, 1, big], c)]
+    for d, c in grids:
+        got = f32(lib.gs_grid_slack(int(d[0]), int(d[1]), int(d[2]), float(c)))
+        want = grid_slack(d, c)
+        assert want.dtype == np.float32 and got.view(np.uint32) == want.view(np.uint32), (d, float(c), float(got), float(want))
 
 
 def test_adversarial_queries_defeat_the_old_margin_and_not_the_new_one():

@@ -1,6 +1,6 @@
 """csrc/er_ransac_math.h compiled for the host (tests/hostcheck/ransac_math_check.cpp) against the numpy restatement of
 tests/ransac_restatement.py: the generator, selectSamples at every NS and at the smallest clouds, the polygon edge test at its edges,
-the rigid estimate against a float64 Kabsch, and the terms of thresholdNormal.  The kernels of er_ransac_search.h compile this text."""
+the rigid estimate against a float64 Kabsch, and the terms of thresholdNormal.  The kernels of er_ransac.hip compile this text."""
 import ctypes as C
 import os
 import subprocess
