@@ -26,7 +26,7 @@ SYMBOLS = [
     "er_cloud_create", "er_cloud_create_batch", "er_cloud_create_from_tsdf", "er_cloud_destroy", "er_cloud_size",
     "er_icp_count_inliers", "er_icp_align", "er_find_correspondence",
     "er_icp_count_inliers_batch", "er_icp_align_batch", "er_find_correspondence_batch", "er_icp_release_workspaces", "er_registration_batch", "er_ransac_fitness_batch", "er_ransac_inliers",
-    "er_features_create", "er_features_destroy", "er_features_size", "er_feature_knn", "er_ransac_hypotheses", "er_ransac_params_default", "er_ransac_align",
+    "er_features_create", "er_features_destroy", "er_features_size", "er_feature_knn", "er_ransac_hypotheses", "er_ransac_params_default", "er_ransac_align", "er_ransac_align_batch",
     "er_cloud_read", "er_cloud_voxel_grid", "er_cloud_estimate_normals", "er_fpfh_estimate", "er_features_dim", "er_features_read",
     "er_fopt_create", "er_fopt_destroy", "er_fopt_set_cloud", "er_fopt_cloud_size", "er_fopt_get_points", "er_fopt_update_pose",
     "er_fopt_update_point_pn", "er_fopt_set_correspondences", "er_fopt_set_correspondences_dev", "er_fopt_group_count", "er_fopt_group_info", "er_fopt_update_normals", "er_fopt_assemble_rigid", "er_fopt_assemble_slac",
@@ -163,6 +163,8 @@ def lib():
             L.er_ransac_hypotheses.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, C.c_float, C.c_float, vp, vp]
             L.er_ransac_params_default.argtypes = [C.POINTER(ErRansacParams)]
             L.er_ransac_align.argtypes = [vp, vp, vp, vp, C.POINTER(ErRansacParams), vp, ip, ip, dp, C.POINTER(ErRansacStats), vp, C.c_int, ip]
+        if hasattr(L, "er_ransac_align_batch"):
+            L.er_ransac_align_batch.argtypes = [C.c_int, vp, vp, vp, vp, C.POINTER(ErRansacParams), vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
         if hasattr(L, "er_fpfh_estimate"):
             L.er_cloud_read.argtypes = [vp, vp, vp]
             L.er_cloud_voxel_grid.argtypes = [vp, C.c_float, C.c_float, C.POINTER(vp), ip]

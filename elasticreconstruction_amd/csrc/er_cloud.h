@@ -60,6 +60,10 @@ struct StreamLease {
   StreamLease& operator=(const StreamLease&) = delete;
   ~StreamLease();
   int acquire(int device);
+  // getInformation for m pairs at one float 4x4 each (er_ransac_inliers without its lists), through the leased workspace's compaction chain on
+  // `stream`; waits for the result.  info_source36 / info_target36 (either may be NULL): m row-major 6x6 matrices.
+  int ransac_information(int m, const er_cloud_t* src, const er_cloud_t* tgt, const float* M16, float corr_dist_threshold, double* info_source36,
+                         double* info_target36);
 
  private:
   void* group_ = nullptr;

@@ -1584,3 +1584,29 @@ int er_registration_batch(int n, const er_cloud_t* src, const er_cloud_t* tgt, c
 }
 
 }  // extern "C"
+
+// What er_ransac_inliers does for its one pair, for m pairs in one chain: a search per pair (each has its own matrix), then one count / scan / compact
+// over all of them and one wait.  Every sum of the chain belongs to one pair, so the matrices are those of m single calls.
+int er::StreamLease::ransac_information(int m, const er_cloud_t* src, const er_cloud_t* tgt, const float* M16, float corr_dist_threshold,
+                                        double* info_source36, double* info_target36) {
+  Group* g = static_cast<Group*>(group_);
+  if (m <= 0 || !g) return 0;
+  if (group_describe(g, 0, m, src, tgt, nullptr, true)) return 1;
+  ER_HIP_TRY(hipMemsetAsync(g->d_info, 0, (size_t)m * kAcc * sizeof(double), g->stream));
+  int mxb = 1;
+  for (int q = 0; q < m; q++) {
+    const int nb = nblocks_of(src[q]->n);
+    mxb = std::max(mxb, nb);
+    Mat12f M;
+    for (int e = 0; e < 12; e++) M.m[e] = M16[(size_t)q * 16 + e];
+    hipLaunchKernelGGL(k_ransac_match, dim3(nb), dim3(kBlock), 0, g->stream, g->d_pairs + q, M, corr_dist_threshold,
+                       corr_dist_threshold * corr_dist_threshold, g->d_info + (size_t)q * kAcc);
+  }
+  if (corr_chain(g, 0, m, mxb, info_source36 != nullptr, info_target36 != nullptr, g->ev)) return 1;
+  ER_HIP_TRY(hipEventSynchronize(g->ev));
+  for (int q = 0; q < m; q++) {
+    if (info_source36) expand_information(g->h_info + (size_t)q * kAcc, info_source36 + (size_t)q * 36);
+    if (info_target36) expand_information(g->h_info + (size_t)q * kAcc + 10, info_target36 + (size_t)q * 36);
+  }
+  return 0;
+}

@@ -285,11 +285,13 @@ RANSAC_AUX = np.dtype([("iteration", np.int32), ("count", np.int32), ("error", n
 
 
 class RansacResult:
-    """ransac_align's result: T float32 4x4, converged, n_inliers, error, stats dict, aux (structured array RANSAC_AUX or None)."""
-    __slots__ = ("T", "converged", "n_inliers", "error", "stats", "aux")
+    """ransac_align's result: T float32 4x4, converged, n_inliers, error, stats dict, aux (structured array RANSAC_AUX or None);
+    from ransac_align_batch(want_info=True) also info_source / info_target (float64 6x6, zero for a pair that did not converge)."""
+    __slots__ = ("T", "converged", "n_inliers", "error", "stats", "aux", "info_source", "info_target")
 
-    def __init__(self, T, converged, n_inliers, error, stats, aux):
+    def __init__(self, T, converged, n_inliers, error, stats, aux, info_source=None, info_target=None):
         self.T, self.converged, self.n_inliers, self.error, self.stats, self.aux = T, converged, n_inliers, error, stats, aux
+        self.info_source, self.info_target = info_source, info_target
 
 
 def ransac_align(src, tgt, src_f, tgt_f, max_iterations=4000000, nr_samples=4, k_correspondences=2, similarity=0.9, max_corr_dist=0.075,
@@ -309,34 +311,105 @@ def ransac_align(src, tgt, src_f, tgt_f, max_iterations=4000000, nr_samples=4, k
     return RansacResult(T.reshape(4, 4), bool(conv.value), cnt.value, err.value, stats, aux[:min(na.value, int(aux_capacity))] if aux_capacity > 0 else None)
 
 
-def global_registration(clouds, features, smart_swap=True, **params):
+def ransac_align_batch(srcs, tgts, src_fs, tgt_fs, seeds=None, max_concurrent=0, want_info=False, max_iterations=4000000, nr_samples=4,
+                       k_correspondences=2, similarity=0.9, max_corr_dist=0.075, inlier_fraction=0.33, inlier_number=30000, angle_diff=0.52359878,
+                       seed=0, chunk_iterations=0):
+    """er_ransac_align_batch: ransac_align for a list of pairs in one call (do_all's pair loop, GlobalRegistration.cpp:38-41), every
+    result bit-equal to the single call's.  seeds: one per pair instead of `seed`; max_concurrent: pairs in flight at once (0: the
+    library chooses); want_info: every result also carries getInformation's two matrices at its transform, as ransac_inliers returns
+    them.  Returns a list of RansacResult."""
+    n = len(srcs)
+    assert len(tgts) == n and len(src_fs) == n and len(tgt_fs) == n
+    if n == 0:
+        return []
+    p = _ffi.ErRansacParams(int(max_iterations), int(nr_samples), int(k_correspondences), float(similarity), float(max_corr_dist),
+                            float(inlier_fraction), int(inlier_number), float(angle_diff), int(seed) & 0xffffffff, int(chunk_iterations))
+    sd = None
+    if seeds is not None:
+        sd = np.array([int(v) & 0xffffffff for v in seeds], np.uint32)
+        assert sd.shape == (n,)
+    T = np.zeros((n, 16), np.float32)
+    conv, cnt, err = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float64)
+    st = (_ffi.ErRansacStats * n)()
+    info_s = np.zeros((n, 6, 6)) if want_info else None
+    info_t = np.zeros((n, 6, 6)) if want_info else None
+    _ffi.check(srcs[0]._lib.er_ransac_align_batch(n, _handles(srcs), _handles(tgts), _handles(src_fs), _handles(tgt_fs), C.byref(p),
+                                                  _ffi.ptr(sd) if sd is not None else None, int(max_concurrent), _ffi.ptr(T), _ffi.ptr(conv),
+                                                  _ffi.ptr(cnt), _ffi.ptr(err), C.cast(st, C.c_void_p), _ffi.ptr(info_s) if want_info else None,
+                                                  _ffi.ptr(info_t) if want_info else None), "er_ransac_align_batch")
+    return [RansacResult(T[i].reshape(4, 4).copy(), bool(conv[i]), int(cnt[i]), float(err[i]),
+                         dict(iterations=st[i].iterations, polygon_rejections=st[i].polygon_rejections, normal_rejections=st[i].normal_rejections,
+                              scored=st[i].scored), None, info_s[i].copy() if want_info else None, info_t[i].copy() if want_info else None)
+            for i in range(n)]
+
+
+def inverse4f(M):
+    """The float32 inverse of a 4x4 by 2x2 minors, operation for operation what ergr::inverse4<float> of csrc/host/er_globalreg.h computes
+    (every product and sum rounded to float32, in the order written): the inverse bin/GlobalRegistration applies to a swapped pair.
+    np.linalg.inv goes through LAPACK, whose float32 rounding differs from build to build in the last bits."""
+    m = np.ascontiguousarray(M, np.float32).reshape(16)
+    s0, s1, s2 = m[0] * m[5] - m[4] * m[1], m[0] * m[6] - m[4] * m[2], m[0] * m[7] - m[4] * m[3]
+    s3, s4, s5 = m[1] * m[6] - m[5] * m[2], m[1] * m[7] - m[5] * m[3], m[2] * m[7] - m[6] * m[3]
+    c5, c4, c3 = m[10] * m[15] - m[14] * m[11], m[9] * m[15] - m[13] * m[11], m[9] * m[14] - m[13] * m[10]
+    c2, c1, c0 = m[8] * m[15] - m[12] * m[11], m[8] * m[14] - m[12] * m[10], m[8] * m[13] - m[12] * m[9]
+    det = ((((s0 * c5 - s1 * c4) + s2 * c3) + s3 * c2) - s4 * c1) + s5 * c0
+    if det == 0:
+        raise np.linalg.LinAlgError("singular matrix")
+    d = np.float32(1) / det
+    r = [((m[5] * c5 - m[6] * c4) + m[7] * c3) * d, ((-m[1] * c5 + m[2] * c4) - m[3] * c3) * d,
+         ((m[13] * s5 - m[14] * s4) + m[15] * s3) * d, ((-m[9] * s5 + m[10] * s4) - m[11] * s3) * d,
+         ((-m[4] * c5 + m[6] * c2) - m[7] * c1) * d, ((m[0] * c5 - m[2] * c2) + m[3] * c1) * d,
+         ((-m[12] * s5 + m[14] * s2) - m[15] * s1) * d, ((m[8] * s5 - m[10] * s2) + m[11] * s1) * d,
+         ((m[4] * c4 - m[5] * c2) + m[7] * c0) * d, ((-m[0] * c4 + m[1] * c2) - m[3] * c0) * d,
+         ((m[12] * s4 - m[13] * s2) + m[15] * s0) * d, ((-m[8] * s4 + m[9] * s2) - m[11] * s0) * d,
+         ((-m[4] * c3 + m[5] * c1) - m[6] * c0) * d, ((m[0] * c3 - m[1] * c1) + m[2] * c0) * d,
+         ((-m[12] * s3 + m[13] * s1) - m[14] * s0) * d, ((m[8] * s3 - m[9] * s1) + m[10] * s0) * d]
+    return np.array(r, np.float32).reshape(4, 4)
+
+
+def global_registration(clouds, features, smart_swap=True, batch=False, inverse=np.linalg.inv, **params):
     """do_all's loop (GlobalRegistration.cpp:32-188) without its file loading, downsampling and feature estimation: every pair i < j,
     scene = i, object = j; with smart_swap the smaller cloud becomes the source and the pair stores the inverse transform and
     information_target_ (:160-166).  Converged pairs only.  Returns (traj, info) ready for formats.save_log / save_info
-    (result.txt, result.info)."""
+    (result.txt, result.info).  batch: the whole loop as ONE ransac_align_batch call (searches and information matrices) instead of a
+    ransac_align and a ransac_inliers call per pair; the same entries, bit for bit.  inverse: the float32 4x4 inverse of a swapped pair;
+    inverse4f gives the bits bin/GlobalRegistration writes."""
     num = len(clouds)
     traj, info = [], []
     thr = params.get("max_corr_dist", 0.075)
+    order = []
     for i in range(num):
         for j in range(i + 1, num):
             scene, obj, swapped = i, j, False
             if smart_swap and clouds[obj].n > clouds[scene].n:
                 scene, obj, swapped = j, i, True
+            order.append((i, j, scene, obj, swapped))
+    res = None
+    if batch:
+        res = ransac_align_batch([clouds[o] for _, _, _, o, _ in order], [clouds[s] for _, _, s, _, _ in order],
+                                 [features[o] for _, _, _, o, _ in order], [features[s] for _, _, s, _, _ in order], want_info=True, **params)
+    for e, (i, j, scene, obj, swapped) in enumerate(order):
+        if batch:
+            r = res[e]
+            if not r.converged:
+                continue
+            info_s, info_t = r.info_source, r.info_target
+        else:
             r = ransac_align(clouds[obj], clouds[scene], features[obj], features[scene], **params)
             if not r.converged:
                 continue
             _, _, _, info_s, info_t = ransac_inliers(clouds[obj], clouds[scene], r.T, thr)
-            T = np.linalg.inv(r.T) if swapped else r.T                      # (Matrix4f::inverse, then the cast to double, :161,178)
-            traj.append(formats.FramedTransformation(i, j, num, np.asarray(T, np.float32).astype(np.float64)))
-            info.append(formats.FramedInformation(i, j, num, info_t if swapped else info_s))
+        T = inverse(r.T) if swapped else r.T                                # (Matrix4f::inverse, then the cast to double, :161,178)
+        traj.append(formats.FramedTransformation(i, j, num, np.asarray(T, np.float32).astype(np.float64)))
+        info.append(formats.FramedInformation(i, j, num, info_t if swapped else info_s))
     return traj, info
 
 
-def global_registration_fragments(clouds, config=None, **params):
+def global_registration_fragments(clouds, config=None, batch=False, inverse=np.linalg.inv, **params):
     """do_all (GlobalRegistration.cpp:32-188) from the fragments' full clouds: every fragment is preprocessed ONCE (the reference redoes
     it for both clouds of every pair), then global_registration runs unchanged -- its smart_swap compares the downsampled sizes, as
     :70-79 does.  config: a dict as formats.load_alignment_config returns it (default: alignment.config's values); **params override
-    ransac_align's arguments (seed, max_iterations, ...).  Returns (traj, info, downsampled clouds, features)."""
+    ransac_align's arguments (seed, max_iterations, ...); batch and inverse as in global_registration.  Returns (traj, info, downsampled clouds, features)."""
     cfg = formats.load_alignment_config(None)
     cfg.update(config or {})
     pre = [preprocess_fragment(c, cfg["resample_leaf"], cfg["normal_radius"], cfg["feature_radius"], cfg["estimate_normal"],
@@ -346,7 +419,7 @@ def global_registration_fragments(clouds, config=None, **params):
               inlier_number=cfg["inlier_number"], angle_diff=cfg["angle_difference"])
     kw.update(params)
     down, feats = [p[0] for p in pre], [p[1] for p in pre]
-    traj, info = global_registration(down, feats, smart_swap=cfg["smart_swap"], **kw)
+    traj, info = global_registration(down, feats, smart_swap=cfg["smart_swap"], batch=batch, inverse=inverse, **kw)
     return traj, info, down, feats
 
 

@@ -394,6 +394,22 @@ int er_ransac_align(er_cloud_t src, er_cloud_t tgt, er_features_t src_feat, er_f
                     float T_out[16], int* converged, int* n_inliers, double* error, er_ransac_stats* stats, er_ransac_aux* aux,
                     int aux_capacity, int* aux_count);
 
+/* The pair loop of do_all (GlobalRegistration.cpp:38-41) in one call: n_pairs searches (src[i], tgt[i], src_feat[i], tgt_feat[i]) on ONE device
+ * under one parameter set; a cloud may appear in any number of pairs, in either role.  seeds (nullable): one seed per pair instead of p->seed.
+ * Outputs are arrays over the pairs -- T_out n*16 floats, converged n ints, n_inliers / error / stats (nullable) n entries -- and equal, bit for
+ * bit, what er_ransac_align returns for each pair alone (with that pair's seed): every kernel of the search takes the pair from a grid axis, the
+ * pairs share nothing but the launches.  info_source36 / info_target36 (nullable, n row-major 6x6 float64 matrices): getInformation
+ * (RansacCurvature.h:706-733) at the winning transform, bit-equal to er_ransac_inliers called with it; all zero for a pair that did not converge.
+ * The pairs run in waves of max_concurrent; a wave shares one workspace allocation, one stream and one read-back of its states.  A pair in flight
+ * needs 88 bytes and one bit per chunk iteration (92 MB at the default chunk of 1048576) plus its k-NN table.  max_concurrent = 0: as many pairs as
+ * fit into 2 GiB of that workspace, at least 1 and at most 64 (23 at the default chunk).  Neither max_concurrent nor the order or make-up of the
+ * list is part of any pair's result.
+ * Everything er_ransac_align refuses is refused for the whole list before the first launch, the message naming the pair ("pair 3: ..."); also
+ * max_concurrent < 0, n_pairs < 0 and a NULL array for n_pairs > 0.  n_pairs == 0 returns 0 and touches nothing. */
+int er_ransac_align_batch(int n_pairs, const er_cloud_t* src, const er_cloud_t* tgt, const er_features_t* src_feat, const er_features_t* tgt_feat,
+                          const er_ransac_params* p, const unsigned int* seeds, int max_concurrent, float* T_out, int* converged, int* n_inliers,
+                          double* error, er_ransac_stats* stats, double* info_source36, double* info_target36);
+
 /* ---- GlobalRegistration: the first half of do_all (GlobalRegistration.cpp:59-128) -- voxel-grid downsampling, normal and FPFH
  * estimation -- once per fragment, from a cloud that is already on the device.  The PCL calls are pinned to the float64 restatement of
  * tests/fpfh_restatement.py (PCL itself is not vendored).  A radius neighbourhood of point i: every point j of the same cloud whose
