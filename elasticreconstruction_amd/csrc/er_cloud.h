@@ -36,7 +36,7 @@ namespace er {
 inline int nblocks_of(int n) { return (std::max(n, 1) + kBlock - 1) / kBlock; }
 
 // ---- er_cloud.hip ----
-// (er::cloud_create_device, the cloud builder for rows that already live on the device, is declared in er_common.h: er_tsdf.hip calls it too.)
+// (er::cloud_create_device, the cloud builder for rows that already live on the device, is declared in er_common.h: er_tsdf_extract.hip calls it too.)
 
 int no_device(const char* who);
 int check_pair(er_cloud_t src, er_cloud_t tgt, double radius, const char* who);

@@ -35,7 +35,7 @@ int tsdf_device(er_tsdf_s* h);
 
 // er_cloud_create for rows that already live on `device` (er_cloud_create_from_tsdf): xyz_dev / normal_dev are packed [n][3] float arrays in
 // device memory whose contents are complete (their producer's stream has been synchronised); they are free again when the call returns.
-// (Declared here for er_tsdf.hip; the rest of what path B's translation units share is er_cloud.h.)
+// (Declared here for er_tsdf_extract.hip; the rest of what path B's translation units share is er_cloud.h.)
 struct er_cloud_s;
 namespace er {
 int cloud_create_device(const float* xyz_dev, const float* normal_dev, int n, float grid_cell, int device, er_cloud_s** out);

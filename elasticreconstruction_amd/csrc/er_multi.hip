@@ -286,7 +286,7 @@ struct DeviceVolume : er::MergeVolume {
     keys.resize((size_t)n);
     return 0;
   }
-  // ---- band records (er_tsdf.hip) ----
+  // ---- band records (er_tsdf_band.hip) ----
   static int grow_floats(float** b, size_t* have, size_t floats) {
     if (*have >= floats) return 0;
     if (*b) (void)hipFree(*b);

@@ -1,0 +1,191 @@
+// er_tsdf.h -- what the translation units of path A (er_tsdf.hip, er_tsdf_pre.hip, er_tsdf_int.hip, er_tsdf_extract.hip, er_tsdf_band.hip) know about
+// each other: the constants of the volume's tables and of the batch pipeline, the three kernels that live in files of their own, the handle, and
+// the few host functions one file calls in another.  Internal: not part of the C ABI (include/er_hip.h).
+#pragma once
+
+#include "er_common.h"
+#include "er_tsdf_math.h"
+
+#include "../../include/er_hip.h"
+
+#include <algorithm>
+#include <cstdlib>
+#include <utility>
+#include <vector>
+
+// Path A's own namespace: er_grid.h (path B) has a kBlock too, in er::.  The kernels declared here are the ones with external linkage: the compiler
+// flags that are best for the voxel pass are not the ones that are best for the pre-pass kernels (profiles/r04k_ab_compiler_flags.txt: without the
+// SLP vectoriser's packed-math pairs -- which cost k_reproject_scatter 28 register moves per pixel -- and with the max-memory-clause scheduler the job
+// gains 4.5 %; k_integrate alone is fastest with the max-ILP scheduler), and hipcc takes such flags per file.  So k_reproject_scatter and k_prepare
+// are defined in er_tsdf_pre.hip, k_integrate in er_tsdf_int.hip, and er_tsdf.hip launches them.  Every other kernel sits in an anonymous namespace
+// next to its host caller; device helpers have internal linkage and are compiled where they are used (er_tsdf_dev.h).
+namespace er_tsdf_k {
+using namespace er;
+
+constexpr int kBlock = 256;
+constexpr int kEmptyKey = -1;
+constexpr uint32_t kZEmpty = 0xFFFFFFFFu;
+
+// counters[] slots
+enum { C_NUNITS = 0, C_NBATCH = 1 /* and 6, 7: one per pipeline slot */, C_POOL_OVERFLOW = 2, C_TABLE_FULL = 3, C_OUT_OF_RANGE = 4,
+       C_NBATCH1 = 6, C_NBATCH2 = 7, C_ZERO_WRITE = 8 /* 8, 9: frames 0-31 / 32-63 of the batch; 10, 11 for the second pre-pass stream */,
+       C_ZERO_WRITE1 = 10, C_COUNT = 12 };
+constexpr int kDepth = 3;                // batches in flight: voxel pass of n, pre-passes of n+1 and n+2 (depth 2 with one pre-pass
+constexpr int kAux = 2;                  // stream = the round-1 pipeline: profiles/r02n_ab_pipeline_depth_hw_queues.txt); pre-pass streams:
+                                         // batch b runs on stream b mod kAux
+
+// ------------------------------------------------------------------------------------------------
+// Reproject, IntegrateApp.cpp:247-268: every source pixel is warped through its fragment's control
+// grid and scattered into the frame's z-buffer.  The reference's sequential "write if empty or
+// closer" is an order-independent min for dd != 0; a write of dd == 0 RESETS the cell (0 means
+// empty), which is order dependent.  Such a write (a warped depth below 0.5 mm: practically never) records its source index
+// in lastzero (max) and raises the FRAME's bit in the stream's flag word; k_reproject_fix then scatters the flagged frames a
+// second time into a side buffer, zfix, under the replay rule -- only writes that come after the cell's last zero write
+// count -- and the consumer of the z-buffer (k_prepare / k_zbuf_to_depth) takes cells with lastzero > 0 from zfix.
+struct ReprojArgs {
+  const uint16_t* depth;
+  int n_frames, cols, rows;
+  Camera cam;
+  CameraInv cami;
+  const double* seg12;
+  const double* madj12;
+  const int* grid_index;
+  const float* ctr;
+  int res;
+  float grid_ul;
+  int floats_per_grid;
+  uint32_t* zbuf;
+  uint32_t* lastzero;
+  uint32_t* zfix;                        // the replay's z-buffer (all-empty outside a replay; re-armed by the consumer)
+  int* zero_flag;                        // int[2], bit f: frame f of the batch saw a write of dd == 0 (one pair per pre-pass stream)
+};
+__global__ void k_reproject_scatter(ReprojArgs A);
+
+// k_reproject_fix's launch (er_tsdf.hip): kFixBlocks single-wave workgroups
+constexpr int kFixThreads = 64;
+constexpr int kFixBlocks = 256;
+
+// Frames of the scaled-depth buffer are kScaledPad floats apart beyond their pixels; the pad stays 0.0f for ever (zero-filled at
+// create, never written): a voxel whose projection misses the image gathers from it instead of taking a predicated load.
+// tile_max / tile_lo / tile_lo_fine are laid out [tile][frame of the batch]: see k_integrate's culling.
+constexpr int kScaledPad = 64;
+constexpr int kTile = 32;
+// Granularity of tile_lo_fine, the second-level per-tile MINIMUM of the scaled depth behind k_integrate's "full" verdict: 2^kLoShift pixels.
+// 16-pixel tiles next to the 32-pixel tiles of tile_max / tile_lo: a pixel without usable depth (the warp's scatter leaves holes) spoils the
+// minimum of its whole tile.  The fine tiles are the SECOND level of the verdict (er_tsdf_math.h: patch_may_update_box): the 32-pixel minimum
+// decides first, the fine ones are read only when it fails for a patch that lies clearly in front of everything under it.
+constexpr int kLoShift = 4;
+constexpr int kLoSub = kTile >> kLoShift;               // tile_lo tiles per side of a 32 x 32 k_prepare tile: 2
+constexpr int kTileKeys = 96;
+
+constexpr int kPrepThreads = 256;                       // 32 x 8 threads, 4 pixel rows each
+constexpr int kPrepPix = kTile * kTile / kPrepThreads;  // pixels per thread
+
+__global__ __launch_bounds__(kPrepThreads) void k_prepare(
+    const uint16_t* __restrict__ depth, uint32_t* __restrict__ zbuf, int n_frames, int cols, int rows,
+    Camera cam, CameraInv cami, const float* __restrict__ lambda, const double* __restrict__ T12, float* __restrict__ scaled,
+    int* __restrict__ ht_key, int* __restrict__ ht_slot, unsigned long long* __restrict__ ht_mask, int cap_mask,
+    int hash_shift, int* __restrict__ batch, int* __restrict__ nbatch,
+    int* __restrict__ counters, float* __restrict__ tile_max, float* __restrict__ tile_lo, float* __restrict__ tile_lo_fine, int2 shard,
+    uint32_t* __restrict__ lastzero, uint32_t* __restrict__ zfix, const int* __restrict__ zero_flag);
+
+// k_plan's records and k_integrate's work items
+constexpr int kRows = 4;                  // register rows per lane of k_integrate: a wave owns an 8 x 4 x 8 box of voxels (2 x 4 x 8 lanes x 4 rows)
+constexpr int kItemsPerUnit = 256;       // work items per unit: 8 x 8 x 16 voxels per 256-thread workgroup
+
+struct Plan {
+  int n_units;
+  int next;      // work queue of k_integrate: index of the next unclaimed item (reset by k_plan)
+};
+
+// What k_integrate needs to know about one unit of the batch, in ONE 16-byte scalar load (round 3; it used to chase plan entry ->
+// hash key -> pool slot -> frame mask through four dependent loads per item).
+struct PlanRec {
+  int key;                  // hash_key of the unit (TSDFVolume.h:62-64)
+  int slot;                 // pool slot; < 0: the pool is exhausted (reported by the host), the unit is skipped
+  unsigned long long mask;  // frames of the batch that touch the unit
+};
+
+constexpr int kIntMinBlocks = 5;                          // register budget handed to the compiler: 5 workgroups of 4 waves per CU = 102 VGPRs (the kernel uses 93 with 3, 4
+                                          // or 5; with 6 it spills).  Same instructions, another register assignment: +1.0 % on the job against 4, five
+                                          // interleaved runs out of five (profiles/r06v_ab_min_blocks.txt).  The grid launches kIntBlocksPerCu = 3
+                                          // workgroups per CU -- the free registers go to the co-running pre-pass kernels
+
+// kSure: the square-root-free "sure" path of the frame loop (er_tsdf_int.hip)
+template <bool kSure>
+__global__ __launch_bounds__(kBlock, kIntMinBlocks) void k_integrate(
+    float2* __restrict__ pool, const PlanRec* __restrict__ plan_rec, Plan* __restrict__ plan,
+    const FrameXform* __restrict__ frames, const float* __restrict__ scaled, const float* __restrict__ tile_max,
+    const float* __restrict__ tile_lo, const float* __restrict__ tile_lo_fine, int tiles_x, int tiles_y, Camera cam, int cols, int rows);
+extern template __global__ void k_integrate<true>(float2* __restrict__, const PlanRec* __restrict__, Plan* __restrict__, const FrameXform* __restrict__, const float* __restrict__, const float* __restrict__, const float* __restrict__, const float* __restrict__, int, int, Camera, int, int);
+extern template __global__ void k_integrate<false>(float2* __restrict__, const PlanRec* __restrict__, Plan* __restrict__, const FrameXform* __restrict__, const float* __restrict__, const float* __restrict__, const float* __restrict__, const float* __restrict__, int, int, Camera, int, int);
+}  // namespace er_tsdf_k
+
+// (the handle is a type of the C ABI, so it lives in the global namespace)
+struct er_tsdf_s {
+  int device = 0, cols = 0, rows = 0, pixels = 0, max_units = 0;
+  er::Camera cam{};
+  er::CameraInv cami{};
+  hipStream_t own_stream = nullptr, stream = nullptr;   // `stream` carries k_plan/k_integrate/k_reset and every other call
+  hipStream_t aux_stream[er_tsdf_k::kAux] = {};                      // pre-passes (reproject, prepare) of the NEXT TWO batches run here, overlapped
+  hipStream_t copy_stream = nullptr;                      // host depth -> depth_stage[slot], overlapped with all of the above; created on
+                                                          // first use (HIP multiplexes streams over 4 hardware queues by default, see er_tsdf_create)
+  hipEvent_t copy_done[er_tsdf_k::kDepth] = {};
+  hipEvent_t consts_done[er_tsdf_k::kDepth] = {};                    // the per-batch constants of slot q have left the pinned block
+  int n_cu = 256;
+  int shard_rank = 0, shard_world = 1;                    // unit-shard mode (er_tsdf_set_unit_shard)
+  // device memory
+  float2* pool = nullptr;
+  int *ht_key = nullptr, *ht_slot = nullptr, *unit_key = nullptr, *counters = nullptr;
+  unsigned long long* stats = nullptr;
+  // triple-buffered batch state (three batches in flight: pre-passes of n+1 and n+2 overlap k_integrate of n)
+  long batch_no = 0;                                // batch b uses slot b mod kDepth and pre-pass stream b mod kAux
+  bool used[er_tsdf_k::kDepth] = {};
+  int* batch[er_tsdf_k::kDepth] = {};
+  unsigned long long* ht_mask[er_tsdf_k::kDepth] = {};
+  float *scaled[er_tsdf_k::kDepth] = {}, *tile_max[er_tsdf_k::kDepth] = {}, *tile_lo[er_tsdf_k::kDepth] = {}, *tile_lo_fine[er_tsdf_k::kDepth] = {};
+  er::FrameXform* frames[er_tsdf_k::kDepth] = {};              // = &dstage[q]->fx
+  void* dstage[er_tsdf_k::kDepth] = {};                        // device twin of the pinned per-batch constants (struct Staging)
+  hipEvent_t pre_done[er_tsdf_k::kDepth] = {}, int_done[er_tsdf_k::kDepth] = {};
+  void* pinned[er_tsdf_k::kDepth] = {};                              // host staging of the per-batch constants
+  int ht_cap = 0, ht_shift = 0;
+  float *lambda = nullptr, *ctr = nullptr;
+  // The caller's lattices, double-buffered by call parity on the host (page-locked staging) AND on the device, so that the
+  // upload of call c (copy stream) never waits for the pre-passes of call c-1 that still read the other buffer.
+  float* ctr_pinned[2] = {nullptr, nullptr};
+  float* ctr_dev[2] = {nullptr, nullptr};
+  size_t ctr_pinned_cap[2] = {0, 0}, ctr_dev_cap[2] = {0, 0};
+  hipEvent_t ctr_ev[2] = {nullptr, nullptr};                // upload of the buffer done
+  hipEvent_t ctr_rd[2][er_tsdf_k::kAux] = {};                          // last pre-pass reader of the buffer, per pre-pass stream
+  bool ctr_rd_set[2] = {false, false};
+  int ctr_parity = 0, ctr_cur = 0;
+  uint16_t* depth_stage[er_tsdf_k::kDepth] = {};              // host frames of the batch in flight, by pipeline slot
+  uint32_t *zbuf[er_tsdf_k::kAux] = {}, *lastzero[er_tsdf_k::kAux] = {}, *zfix[er_tsdf_k::kAux] = {};  // Reproject's z-buffer and replay state, one per pre-pass stream
+  double *T12 = nullptr, *seg12 = nullptr, *madj12 = nullptr, *dsum = nullptr;
+  int *grid_index = nullptr, *key_scratch = nullptr, *slot_scratch = nullptr;
+  er_tsdf_k::PlanRec* plan_rec[er_tsdf_k::kDepth] = {};
+  er_tsdf_k::Plan* plan[er_tsdf_k::kDepth] = {};
+  bool reset_pending[er_tsdf_k::kDepth] = {};                  // k_reset of the slot's last batch has not been launched yet
+  size_t key_scratch_cap = 0;
+  // profiling
+  int prof_stride = 0;                              // 0 = off, n = time every n-th k_integrate launch
+  long prof_tick = 0;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+  double ms_total = 0.0;
+  long launches = 0, frames_done = 0;
+  // round 6 (owner merge): units this GPU handed to their owner -- zeroed, still in the table, hidden from every key / count / extraction query until
+  // the next frame is integrated or the unit is imported again -- and the grow-only device scratch of the band kernels
+  std::vector<int> dropped;                         // sorted
+  void* band_scratch = nullptr;
+  size_t band_scratch_cap = 0;
+};
+
+// ---- er_tsdf.hip: host functions the other files call (hidden: not part of the library's interface) ----
+namespace er_tsdf_k {
+// Waits for h->stream; fails if the unit pool or the hash table has overflowed.
+__attribute__((visibility("hidden"))) int check_flags(er_tsdf_t h);
+// keys (host) -> slots (device, h->slot_scratch) on h->stream, optionally allocating missing units.
+__attribute__((visibility("hidden"))) int resolve_slots(er_tsdf_t h, const int* keys_host, int n, bool allocate);
+// The units this GPU holds (without the ones handed to their owner), in ascending key order: keys and pool slots.  Calls check_flags.
+__attribute__((visibility("hidden"))) int sorted_units(er_tsdf_t h, std::vector<int>& keys, std::vector<int>& slots);
+}  // namespace er_tsdf_k

@@ -1,5 +1,5 @@
 // er_tsdf_math.h -- per-pixel / per-voxel arithmetic of path A, written once as inline functions
-// that the HIP kernels in er_tsdf.hip call.  The functions are also compilable for the host (ER_HD
+// that the HIP kernels in er_tsdf*.hip call.  The functions are also compilable for the host (ER_HD
 // expands to nothing without hipcc) so tests/hostcheck can exercise the exact same expressions
 // against the oracle on a machine without a GPU; the shipped library only ever runs them on device.
 //

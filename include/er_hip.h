@@ -175,7 +175,7 @@ int er_tsdf_import_raw(er_tsdf_t h, const int* keys_host, int n_keys, const floa
 /* Round 6, BAND RECORDS: a unit as its observed voxels only (weight_ != 0: the truncation band and the free space in front of it, about a quarter of a
  * touched unit), the sdf_ only where it is not exactly 1 (free space: four observed voxels out of five) and the weight_ as 16 bits when every weight of
  * the unit is a frame count below 65536.  A never-updated voxel is (+0, 0) (TSDFVolumeUnit.cpp:4-21), so a record restores a unit bit for bit.
- * Records are DEVICE memory, 8-byte aligned, a whole number of 32-bit words (layout: csrc/er_tsdf.hip, "band records").  band_sizes: the record size in
+ * Records are DEVICE memory, 8-byte aligned, a whole number of 32-bit words (layout: csrc/er_tsdf_band.hip, "band records").  band_sizes: the record size in
  * words of each unit this GPU holds (a key it does not hold is an error).  export_band: the records of the given units back to back into dev_block
  * (sizes as band_sizes returned them; a volume that changed in between is an error).  merge_band: the OWNER's step of the frame-split merge -- unit
  * keys[u] becomes the sum of its own voxels and nsrc[u] <= 16 records (recs[16 u + k], the other GPUs' in rank order; self_pos[u] of them come before

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """profiles/pmc_latest.json from ONE scripts/pmc_summary.py summary (the file bench.py reads the static counter figures from).
 usage: python scripts/pmc_latest.py profiles/<tag>_pmc_summary.txt <tag> "<what the kernel was>" [profiles/<tag>_kernel_stats.csv] > profiles/pmc_latest.json
-Run it on the tree the profiled run used: the sha16 of the kernel sources is stamped into the file, and bench.py marks the static
-figures 'stale' when the sources have changed since."""
+Run it on the tree the profiled run used: a sha16 over csrc/er_tsdf.hip, er_tsdf_math.h and the Makefile (bench.kernel_source_sha16) is stamped
+into the file, and bench.py marks the static figures 'stale' when those files have changed since.  The text of k_reproject_scatter, k_prepare
+(er_tsdf_pre.hip) and k_integrate (er_tsdf_int.hip) is NOT under that hash: after a change to those files alone the stamp still reads fresh, so
+rerun this script whenever they change."""
 import csv
 import json
 import os

@@ -1,4 +1,4 @@
-"""Numpy restatement of the band record (csrc/er_tsdf.hip, "band records"; include/er_hip.h) and of the owner's sum of the frame-split merge.
+"""Numpy restatement of the band record (csrc/er_tsdf_band.hip, "band records"; include/er_hip.h) and of the owner's sum of the frame-split merge.
 
 Written from the layout comment alone; imports nothing from the library.  A unit is (sdf[262144], weight[262144]) float32, voxel l = (i * 64 + j) * 64 + k.
 A record, in 32-bit words:

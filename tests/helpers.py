@@ -109,7 +109,7 @@ def merge_blocks(G, per, devices):
 
 
 def band_record_words(sdf, w):
-    """Size of a unit's band record (csrc/er_tsdf.hip, "band records"): header + weights of the observed voxels (16 bits each when every weight is a frame
+    """Size of a unit's band record (csrc/er_tsdf_band.hip, "band records"): header + weights of the observed voxels (16 bits each when every weight is a frame
     count below 65536) + sdf of the observed voxels whose sdf is not exactly 1, both padded to an even number of 32-bit words."""
     import numpy as np
     on = w != 0

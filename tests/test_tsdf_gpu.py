@@ -885,3 +885,37 @@ def test_marching_cubes_of_an_analytic_sphere_is_a_closed_genus_0_surface(gpu):
     outward = np.einsum("ij,ij->i", n, (A + B + C) / 3.0 - c) > 0
     assert outward.all(), "%d triangles face the centre" % int((~outward).sum())
     vol.close()
+
+
+def test_extraction_into_a_buffer_one_element_short_is_refused(gpu):
+    """The capacity check of er_tsdf_extract_world / _surface / _mesh / _oriented, which the Python wrappers never reach (they pass the exact
+    count): with a buffer one element short of the count the entry point just reported, each returns non-zero with its message in
+    er_last_error (er_tsdf_extract_surface reports under er_tsdf_extract_world's name), still sets *count to the true count, writes
+    nothing to the buffer, and leaves the volume as it was: the wrapper returns the same array, bit for bit, afterwards.  The volume is
+    the one smoke() integrates."""
+    import ctypes as C
+    sc = synth.make_scenario(4, interval=2, warp=True, device="cuda:0")
+    vol = TSDFVolume(max_units=256, device=0)
+    vol.IntegrateFrames(synth.to_numpy_u16(sc["depth"]), sc["traj"], synth.warp_arrays(sc))
+    L = _ffi.lib()
+    cases = [   # entry point, the name it reports under, what it counts, floats per element of each buffer, the wrapper
+        ("er_tsdf_extract_world", "er_tsdf_extract_world", "points", (4,), lambda: (vol.extract_world(),)),
+        ("er_tsdf_extract_surface", "er_tsdf_extract_world", "points", (4,), lambda: (vol.extract_surface(),)),
+        ("er_tsdf_extract_mesh", "er_tsdf_extract_mesh", "triangles", (9,), lambda: (vol.extract_mesh(),)),
+        ("er_tsdf_extract_oriented", "er_tsdf_extract_oriented", "points", (4, 4), vol.extract_oriented),
+    ]
+    for entry, who, what, widths, wrapper in cases:
+        before = wrapper()
+        true_n = before[0].shape[0]
+        assert true_n > 1, (entry, true_n)
+        bufs = [np.zeros((true_n - 1, w), np.float32) for w in widths]
+        n = C.c_long(-1)
+        rc = getattr(L, entry)(vol._h, *[_ffi.ptr(b) for b in bufs], true_n - 1, C.byref(n))
+        assert rc != 0, entry
+        assert L.er_last_error().decode() == "%s: capacity %d < %d %s" % (who, true_n - 1, true_n, what), entry
+        assert n.value == true_n, (entry, n.value, true_n)
+        assert not any(b.any() for b in bufs), "%s wrote to a buffer it refused" % entry
+        after = wrapper()
+        for a, b in zip(before, after):
+            assert a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32)), entry
+    vol.close()
