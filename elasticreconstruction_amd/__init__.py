@@ -8,6 +8,7 @@ There is no CPU fallback: importing works anywhere, but every operation needs th
 extension and a HIP device.
 """
 from ._ffi import ErError, LIB_PATH, lib  # noqa: F401
+from .odometry import DepthOdometry, accumulate  # noqa: F401
 
 
 def request_hw_queues(n=8):
@@ -19,4 +20,4 @@ def request_hw_queues(n=8):
     return int(os.environ["GPU_MAX_HW_QUEUES"])
 
 
-__all__ = ["ErError", "LIB_PATH", "lib", "request_hw_queues"]
+__all__ = ["ErError", "LIB_PATH", "lib", "request_hw_queues", "DepthOdometry", "accumulate"]

@@ -27,6 +27,7 @@ SYMBOLS = [
     "er_icp_count_inliers", "er_icp_align", "er_find_correspondence",
     "er_icp_count_inliers_batch", "er_icp_align_batch", "er_find_correspondence_batch", "er_icp_release_workspaces", "er_registration_batch", "er_ransac_fitness_batch", "er_ransac_inliers",
     "er_features_create", "er_features_destroy", "er_features_size", "er_feature_knn", "er_ransac_hypotheses", "er_ransac_params_default", "er_ransac_align", "er_ransac_align_batch",
+    "er_odom_params_default", "er_odom_create", "er_odom_destroy", "er_odom_align_pairs", "er_odom_track", "er_odom_linearize", "er_odom_read_maps", "er_odom_tables",
     "er_cloud_read", "er_cloud_voxel_grid", "er_cloud_estimate_normals", "er_fpfh_estimate", "er_features_dim", "er_features_read",
     "er_fopt_create", "er_fopt_destroy", "er_fopt_set_cloud", "er_fopt_cloud_size", "er_fopt_get_points", "er_fopt_update_pose",
     "er_fopt_update_point_pn", "er_fopt_set_correspondences", "er_fopt_set_correspondences_dev", "er_fopt_group_count", "er_fopt_group_info", "er_fopt_update_normals", "er_fopt_assemble_rigid", "er_fopt_assemble_slac",
@@ -57,6 +58,12 @@ class ErRansacParams(C.Structure):
 class ErRansacStats(C.Structure):
     """struct er_ransac_stats (include/er_hip.h)."""
     _fields_ = [("iterations", C.c_longlong), ("polygon_rejections", C.c_longlong), ("normal_rejections", C.c_longlong), ("scored", C.c_longlong)]
+
+
+class ErOdomParams(C.Structure):
+    """struct er_odom_params (include/er_hip.h)."""
+    _fields_ = [("levels", C.c_int), ("iterations", C.c_int * 4), ("bilateral", C.c_int), ("max_depth_mm", C.c_int), ("min_valid", C.c_int),
+                ("dist_thresh", C.c_float), ("angle_thresh", C.c_float)]
 
 
 class ErError(RuntimeError):
@@ -172,6 +179,15 @@ def lib():
             L.er_fpfh_estimate.argtypes = [vp, C.c_float, C.POINTER(vp), vp, vp]
             L.er_features_dim.argtypes = [vp]
             L.er_features_read.argtypes = [vp, vp]
+    if hasattr(L, "er_odom_create"):
+        L.er_odom_params_default.argtypes = [C.POINTER(ErOdomParams)]
+        L.er_odom_create.argtypes = [C.c_int, C.c_int, fp, C.POINTER(ErOdomParams), C.c_int, C.POINTER(vp)]
+        L.er_odom_destroy.argtypes = [vp]
+        L.er_odom_align_pairs.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int]
+        L.er_odom_track.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int]
+        L.er_odom_linearize.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, ip]
+        L.er_odom_read_maps.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
+        L.er_odom_tables.argtypes = [vp, vp, ip]
     if hasattr(L, "er_fopt_create"):
         L.er_fopt_create.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(vp)]
         L.er_fopt_destroy.argtypes = [vp]

@@ -464,6 +464,63 @@ int er_registration_batch(int n, const er_cloud_t* src, const er_cloud_t* tgt, c
                           int* accepted, float* T_final, int* iterations, int* converged, int* const* pairs_host, const int* capacity,
                           int* n_pairs, double* info36);
 
+/* ------------------------------------------------ depth odometry ---- */
+/* The step that produces the pipeline's trajectory in the first place: KinFu-style projective point-to-plane ICP between depth frames,
+ * batched over a pair list.  The reference tree does not contain KinFu (it lives in the author's PCL fork): every entry below restates
+ * tests/odometry_restatement.py, the numpy statement of DESIGN.md 7.11, and NOTHING here is checked against PCL.
+ * Per frame: 13x13 bilateral filter (sigma_space 4.5 px, sigma_depth 30 mm, weights from two host-built float32 tables), a pyramid of
+ * 5x5 integer means of the taps within 3 sigma_depth of the centre, and per level a map of {vertex, normal} records (float32).  Per pair
+ * and iteration: project every pixel of the current frame into the model frame, test distance and normal angle, 27 float64 sums of exact
+ * products + a count, added in an order that depends on (cols, rows, level) only; a 6x6 float64 Cholesky solve and the pose update stay on
+ * the device.  A pair's result is the same bits alone, in any list, in any order, for any window, on any run. */
+typedef struct er_odom_s* er_odom_t;
+typedef struct er_odom_params {
+  int levels;             /* pyramid levels, 1 .. 4 (3) */
+  int iterations[4];      /* iterations at level 0 (finest) .. 3: (10, 5, 4, 4); the loop runs from level levels-1 down to 0 */
+  int bilateral;          /* 1; 0 copies the frame */
+  int max_depth_mm;       /* depths above it are zeroed in level 0 before anything is derived from it; 0 = off (0) */
+  int min_valid;          /* a pair with fewer matched pixels in an iteration is lost (50) */
+  float dist_thresh;      /* reject a match farther than this, metres (0.10) */
+  float angle_thresh;     /* reject a match whose |cross(ng, nm)| is >= this sine (sin 20 deg) */
+} er_odom_params;
+int er_odom_params_default(er_odom_params* p);
+
+/* Restates odometry_restatement.Odometry(cols, rows, cam, params): frames of cols x rows uint16 millimetres, cam4 = (fx, fy, cx, cy) of
+ * level 0 (level l uses cam4 / 2^l).  cols and rows must be divisible by 2^(levels-1).  Not thread-safe: one call per handle at a time. */
+int er_odom_create(int cols, int rows, const float* cam4, const er_odom_params* params, int device, er_odom_t* out);
+int er_odom_destroy(er_odom_t h);
+
+#define ER_ODOM_OK 0
+#define ER_ODOM_LOST 1
+#define ER_ODOM_TRACE 17   /* doubles per traced iteration: the row-major 4x4 pose after it, then its matched-pixel count */
+/* Restates odometry_restatement.Odometry.align for every pair of a list: pair p aligns current frame frame_idx[p] to model frame
+ * model_idx[p] of depth[n_frames][rows * cols] (host memory, or device memory of the handle's device when depth_on_device), starting from
+ * guess[p][16] (row-major float64 m_T_c; NULL = identity).  T_out[p][16]: m_T_c, float64 row-major.  status[p]: ER_ODOM_OK or ER_ODOM_LOST
+ * (an iteration matched fewer than min_valid pixels, a Cholesky pivot was not positive, or something was not finite: the pair keeps its
+ * last good pose).  trace (nullable): [n_pairs][sum of iterations over the levels used][ER_ODOM_TRACE], coarse to fine; sums (nullable):
+ * [n_pairs][27], the last iteration's 21 entries of the upper triangle of J^T J row by row, then J^T r (rows (cross(vg, nm), nm)).
+ * window: frames resident at a time (>= 2; 0 = what keeps the frame slab under 2 GiB).  The list is cut into runs of pairs whose frames fit
+ * the window; a frame that the next run needs again stays resident. */
+int er_odom_align_pairs(er_odom_t h, int n_frames, const uint16_t* depth, int depth_on_device, int n_pairs, const int* model_idx,
+                        const int* frame_idx, const double* guess, double* T_out, int* status, double* trace, double* sums, int window);
+
+/* Restates odometry_restatement.Odometry.track: er_odom_align_pairs of the list (i, i + 1), i = 0 .. n_frames - 2, from the identity.
+ * T_rel[i][16] = frame i <- frame i + 1. */
+int er_odom_track(er_odom_t h, int n_frames, const uint16_t* depth, int depth_on_device, double* T_rel, int* status, int window);
+
+/* Restates odometry_restatement.Odometry.linearize: ONE evaluation of the 27 sums and the count at the pose T (m_T_c) on `level`, for
+ * depth2 = {model frame, current frame}. */
+int er_odom_linearize(er_odom_t h, const uint16_t* depth2, int on_device, int level, const double* T, double* sums, int* count);
+
+/* Restates odometry_restatement.Odometry.maps for one frame (any output may be NULL): depth_out uint16 [rows_l * cols_l] (level 0: the
+ * filtered, depth-limited frame), vmap_out / nmap_out float [rows_l * cols_l][3], NaN where invalid. */
+int er_odom_read_maps(er_odom_t h, const uint16_t* depth1, int on_device, int level, uint16_t* depth_out, float* vmap_out, float* nmap_out);
+
+/* Restates odometry_restatement.tables(): the two weight tables of the bilateral filter as the kernels read them.  space[dx^2 + dy^2],
+ * 73 entries; depth_w[|delta| in mm], *n_depth_w entries (at most ER_ODOM_DEPTH_W), zero beyond.  Works without a device. */
+#define ER_ODOM_DEPTH_W 512
+int er_odom_tables(float* space, float* depth_w, int* n_depth_w);
+
 /* ------------------------------------------ next consumer: FragmentOptimizer ---- */
 typedef struct er_fopt_s* er_fopt_t;
 
