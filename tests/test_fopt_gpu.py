@@ -26,7 +26,7 @@ def _same_state(g, o, num):
             assert np.array_equal(a[key].view(np.uint32), b[key].view(np.uint32)), (f, key)
 
 
-def _close(A, B, what):
+def _close(A, B, what):                                       # one global bar; entry by entry: tests/test_fopt_shapes_gpu.py
     scale = np.abs(B).max()
     err = np.abs(A - B).max()
     assert err <= 1e-11 * scale, "%s: max abs error %.3g against scale %.3g" % (what, err, scale)
