@@ -29,6 +29,7 @@ SYMBOLS = [
     "er_features_create", "er_features_destroy", "er_features_size", "er_feature_knn", "er_ransac_hypotheses", "er_ransac_params_default", "er_ransac_align", "er_ransac_align_batch",
     "er_odom_params_default", "er_odom_create", "er_odom_destroy", "er_odom_align_pairs", "er_odom_track", "er_odom_linearize", "er_odom_read_maps", "er_odom_tables",
     "er_cloud_read", "er_cloud_voxel_grid", "er_cloud_estimate_normals", "er_fpfh_estimate", "er_features_dim", "er_features_read",
+    "er_pgo_create", "er_pgo_destroy", "er_pgo_optimize", "er_pgo_set_state", "er_pgo_get_state", "er_pgo_linearize", "er_pgo_trial", "er_pgo_set_profiling", "er_pgo_get_profile",
     "er_fopt_create", "er_fopt_destroy", "er_fopt_set_cloud", "er_fopt_cloud_size", "er_fopt_get_points", "er_fopt_update_pose",
     "er_fopt_update_point_pn", "er_fopt_set_correspondences", "er_fopt_set_correspondences_dev", "er_fopt_group_count", "er_fopt_group_info", "er_fopt_update_normals", "er_fopt_assemble_rigid", "er_fopt_assemble_slac",
     "er_fopt_assemble_nonrigid", "er_fopt_factor_slac", "er_fopt_factor_nonrigid", "er_fopt_solve", "er_fopt_debug_shift_diagonal",
@@ -188,6 +189,16 @@ def lib():
         L.er_odom_linearize.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, ip]
         L.er_odom_read_maps.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
         L.er_odom_tables.argtypes = [vp, vp, ip]
+    if hasattr(L, "er_pgo_create"):
+        L.er_pgo_create.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.POINTER(vp)]
+        L.er_pgo_destroy.argtypes = [vp]
+        L.er_pgo_optimize.argtypes = [vp, C.c_int, C.c_double, C.c_int, vp, vp, ip, ip, vp]
+        L.er_pgo_set_state.argtypes = [vp, vp, vp]
+        L.er_pgo_get_state.argtypes = [vp, vp, vp]
+        L.er_pgo_linearize.argtypes = [vp, C.c_double, C.c_double, vp, vp, vp]
+        L.er_pgo_trial.argtypes = [vp, C.c_double, C.c_double, vp, vp, dp, ip]
+        L.er_pgo_set_profiling.argtypes = [vp, C.c_int]
+        L.er_pgo_get_profile.argtypes = [vp, vp]
     if hasattr(L, "er_fopt_create"):
         L.er_fopt_create.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(vp)]
         L.er_fopt_destroy.argtypes = [vp]

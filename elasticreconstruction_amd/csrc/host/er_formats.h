@@ -83,6 +83,30 @@ struct FramedInformation {
   double info[36];
 };
 
+// RGBDInformation::LoadFromFile (BuildCorrespondence/Helper.h:74-105): the header as in a .log, then six rows of six.
+inline bool load_info(const std::string& path, std::vector<FramedInformation>& out) {
+  out.clear();
+  FILE* f = fopen(path.c_str(), "r");
+  if (!f) return false;
+  char buf[1024];
+  while (fgets(buf, 1024, f)) {
+    if (strlen(buf) > 0 && buf[0] != '#') {
+      FramedInformation t;
+      if (sscanf(buf, "%d %d %d", &t.id1, &t.id2, &t.frame) < 3) continue;
+      bool ok = true;
+      for (int r = 0; r < 6 && ok; r++) {
+        if (!fgets(buf, 1024, f)) { ok = false; break; }
+        double* q = &t.info[r * 6];
+        sscanf(buf, "%lf %lf %lf %lf %lf %lf", q, q + 1, q + 2, q + 3, q + 4, q + 5);
+      }
+      if (!ok) break;
+      out.push_back(t);
+    }
+  }
+  fclose(f);
+  return true;
+}
+
 inline bool save_info(const std::string& path, const std::vector<FramedInformation>& v) {
   FILE* f = fopen(path.c_str(), "w");
   if (!f) return false;

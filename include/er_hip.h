@@ -521,6 +521,49 @@ int er_odom_read_maps(er_odom_t h, const uint16_t* depth1, int on_device, int le
 #define ER_ODOM_DEPTH_W 512
 int er_odom_tables(float* space, float* depth_w, int* n_depth_w);
 
+/* ------------------------------------------------ pose graph optimisation ---- */
+/* GraphOptimizer: the candidate loop closures of GlobalRegistration in, pruned closures and fragment poses out.  The model is the
+ * reference's (GraphOptimizer/OptApp.cpp over g2o's VertexSE3 / EdgeSE3 and vertigo's switchable edge); g2o itself cannot be built from
+ * the reference tree, so every entry below restates tests/posegraph_restatement.py, the numpy statement of DESIGN.md 7.12, and NOTHING
+ * here is checked against g2o.  The Levenberg-Marquardt schedule is this project's.  float64 throughout; poses are
+ * row-major 4x4; every switch is eliminated inside its edge, so the system that is factored is dense 6 (n_poses - 1) square.  The loop
+ * stays on the device: per trial the host reads one small record.  A graph gives the same bits on every run. */
+typedef struct er_pgo_s* er_pgo_t;
+#define ER_PGO_SWITCHABLE 0   /* COptApp::OptimizeSwitchable (OptApp.cpp:51-159) */
+#define ER_PGO_EM 1           /* COptApp::OptimizeEM (OptApp.cpp:161-265) */
+
+/* COptApp::Init (OptApp.cpp:28-49) and the graph both modes build (OptApp.cpp:76-128, 185-225): n_poses vertices (2 .. 1024), vertex 0
+ * fixed, initial poses X_{i+1} = X_i odo_T[i]; odometry edge i joins i and i + 1 (odo_T[n_poses - 1][16], odo_info[n_poses - 1][36] or NULL
+ * for the identity); loop edge k joins loop_ids[2k] and loop_ids[2k + 1] (loop_T[n_loops][16], loop_info[n_loops][36] or NULL).  Several
+ * loop edges on one pair and id1 > id2 are allowed.  Refused, naming the entry: id1 == id2, an id out of range, a non-finite entry. */
+int er_pgo_create(int n_poses, int n_loops, const double* odo_T, const double* odo_info, const int* loop_ids, const double* loop_T,
+                  const double* loop_info, int device, er_pgo_t* out);
+int er_pgo_destroy(er_pgo_t h);
+
+/* optimizer->optimize(max_iteration) of OptimizeSwitchable, or the max_iteration E / M rounds of OptimizeEM (OptApp.cpp:130-131, 227-249),
+ * from the initial poses and all switches at 1, whatever an earlier call left.  weight: --weight (the switch prior's information, or the
+ * EM scale).  poses_out[n_poses][16]; switch_or_weight_out[n_loops]: the switches s_k (an edge is kept when s_k > 0.5) or the last E
+ * step's l_k (kept when l_k > 0.25).  *iterations, *trials (nullable): LM iterations begun and trials made.  chi2_trace (nullable):
+ * [10 * max_iteration][4] = (lambda of the trial, F before it, F of the candidate, accepted), one row per trial. */
+int er_pgo_optimize(er_pgo_t h, int method, double weight, int max_iteration, double* poses_out, double* switch_or_weight_out, int* iterations,
+                    int* trials, double* chi2_trace);
+
+/* Measurement (scripts/posegraph_probe.py): with profiling on, HIP events round the stages of every trial; er_pgo_get_profile returns the
+ * milliseconds of the last er_pgo_optimize summed over its trials: linearise, assemble, factor, solve, apply + evaluate. */
+int er_pgo_set_profiling(er_pgo_t h, int on);
+int er_pgo_get_profile(er_pgo_t h, double* stage_ms5);
+
+/* Test hooks.  The current state: poses[n_poses][16], switches[n_loops] (either may be NULL). */
+int er_pgo_set_state(er_pgo_t h, const double* poses, const double* switches);
+int er_pgo_get_state(er_pgo_t h, double* poses, double* switches);
+/* Restates posegraph_restatement.Graph.linearize (switchable mode) at the current state: the reduced dense system H_out[n][n] (full
+ * symmetric, lambda only inside every switch's H_ss), b_out[n], n = 6 (n_poses - 1), and chi2_out[n_poses - 1 + n_loops] = r^T Omega r of
+ * every edge, odometry first. */
+int er_pgo_linearize(er_pgo_t h, double weight, double lambda, double* H_out, double* b_out, double* chi2_out);
+/* Restates posegraph_restatement.Graph.trial: ONE factor of H + lambda I, solve and apply, without deciding; the current state stays.
+ * dx_out[n], ds_out[n_loops] (before the clamp), *F_new_out = F of the candidate, *status_out = 1 when a pivot was not positive and finite. */
+int er_pgo_trial(er_pgo_t h, double weight, double lambda, double* dx_out, double* ds_out, double* F_new_out, int* status_out);
+
 /* ------------------------------------------ next consumer: FragmentOptimizer ---- */
 typedef struct er_fopt_s* er_fopt_t;
 
