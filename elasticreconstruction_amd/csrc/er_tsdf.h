@@ -126,7 +126,13 @@ struct er_tsdf_s {
   int device = 0, cols = 0, rows = 0, pixels = 0, max_units = 0;
   er::Camera cam{};
   er::CameraInv cami{};
-  hipStream_t own_stream = nullptr, stream = nullptr;   // `stream` carries k_plan/k_integrate/k_reset and every other call
+  hipStream_t own_stream = nullptr, stream = nullptr;   // `stream` (the caller's, or own_stream) carries every call but the voxel pass; k_integrate
+                                                        // ALWAYS runs on own_stream, joined to `stream` in front of and behind er_tsdf_integrate_frames: the
+                                                        // handle's three streams are created back to back and so get hardware queues of their own,
+                                                        // a caller's stream may share one with a pre-pass stream (er_tsdf.hip: run_batch)
+  hipEvent_t caller_ev = nullptr;                       // `stream` as it stood at the start of the call, for own_stream to wait for
+  hipEvent_t voxel_done = nullptr;                      // the last voxel pass of the last call, for `stream` to wait for (join_voxel) ...
+  bool voxel_ahead = false;                             // ... which it has not done yet
   hipStream_t aux_stream[er_tsdf_k::kAux] = {};                      // pre-passes (reproject, prepare) of the NEXT TWO batches run here, overlapped
   hipStream_t copy_stream = nullptr;                      // host depth -> depth_stage[slot], overlapped with all of the above; created on
                                                           // first use (HIP multiplexes streams over 4 hardware queues by default, see er_tsdf_create)

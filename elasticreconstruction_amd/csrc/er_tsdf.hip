@@ -246,6 +246,19 @@ int drain_events(er_tsdf_t h) {
   return 0;
 }
 
+// The voxel passes run on own_stream (run_batch).  Whoever is about to use h->stream for the volume -- check_flags, resolve_slots,
+// flush_resets, sync_all: every entry point passes one of them before it touches the pool or the tables -- first makes a caller's
+// stream wait for the last voxel pass.  Lazily, not at the end of er_tsdf_integrate_frames: a wait parked in the caller's stream
+// would hold up whatever shares its hardware queue, and the next call's "own_stream behind the caller's stream" would wait behind
+// it for nothing (-1.4 % with 8 queues, profiles/r07a_timeline_queues.txt).
+int join_voxel(er_tsdf_t h) {
+  if (h->voxel_ahead) {
+    ER_HIP_TRY(hipStreamWaitEvent(h->stream, h->voxel_done, 0));
+    h->voxel_ahead = false;
+  }
+  return 0;
+}
+
 int ensure_key_scratch(er_tsdf_t h, size_t n) {
   if (n <= h->key_scratch_cap) return 0;
   if (h->key_scratch) (void)hipFree(h->key_scratch);
@@ -264,6 +277,7 @@ namespace er_tsdf_k {
 
 int check_flags(er_tsdf_t h) {
   int c[C_COUNT];
+  if (join_voxel(h)) return 1;
   ER_HIP_TRY(hipMemcpyAsync(c, h->counters, sizeof c, hipMemcpyDeviceToHost, h->stream));
   ER_HIP_TRY(hipStreamSynchronize(h->stream));
   if (c[C_POOL_OVERFLOW])
@@ -274,7 +288,7 @@ int check_flags(er_tsdf_t h) {
 
 // keys (host) -> slots (device slot_scratch), optionally allocating missing units.
 int resolve_slots(er_tsdf_t h, const int* keys_host, int n, bool allocate) {
-  if (ensure_key_scratch(h, (size_t)n)) return 1;
+  if (join_voxel(h) || ensure_key_scratch(h, (size_t)n)) return 1;
   ER_HIP_TRY(hipMemcpyAsync(h->key_scratch, keys_host, (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_ensure_units, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, h->stream, h->key_scratch, n,
                      h->ht_key, h->ht_slot, h->ht_cap - 1, h->ht_shift, h->unit_key, h->max_units, h->counters,
@@ -323,6 +337,7 @@ struct Staging {
 // stream of the batch that reuses the slot, off the main stream, whose per-batch chain is then ONE kernel.  Whoever needs the
 // accounts or leaves the pipeline (synchronise, profile read-out) flushes the pending ones on the main stream.
 int flush_resets(er_tsdf_t h) {
+  if (join_voxel(h)) return 1;                                          // (k_reset stands behind the slot's k_integrate)
   for (int q = 0; q < kDepth; q++)
     if (h->reset_pending[q]) {
       hipLaunchKernelGGL(k_reset, dim3(1), dim3(kBlock), 0, h->stream, h->batch[q], h->counters + kNbatchSlot[q], h->ht_mask[q], h->stats);
@@ -337,18 +352,59 @@ int sync_all(er_tsdf_t h) {
   if (flush_resets(h)) return 1;
   if (h->copy_stream) ER_HIP_TRY(hipStreamSynchronize(h->copy_stream));
   for (int a = 0; a < kAux; a++) ER_HIP_TRY(hipStreamSynchronize(h->aux_stream[a]));
+  if (h->stream != h->own_stream) ER_HIP_TRY(hipStreamSynchronize(h->own_stream));
   ER_HIP_TRY(hipStreamSynchronize(h->stream));
+  h->voxel_ahead = false;
   return 0;
 }
 
 // One batch (<= ER_MAX_BATCH frames).  depth_dev: n * pixels uint16 on device (must be complete: the
 // pre-passes run on the handle's auxiliary streams, which do not wait for the caller's stream).
-// Pipeline over three in-order streams, batch state triple-buffered by slot p = batch mod 3:
-//   aux stream b mod 2: wait int_done[p] -> [k_reset(p) of batch n-3] -> [H2D constants] -> k_reproject_* -> k_prepare(p) -> k_plan(p) -> event pre_done[p]
-//   main stream       : wait pre_done[p] -> k_integrate(p) -> event int_done[p]            (ONE kernel per batch: it is the critical path)
-// so the pre-passes of batches n+1 and n+2 (latency / float64 bound, each a serial chain of launches) overlap each other and
-// k_integrate of batch n (float32 VALU bound): k_integrate is shorter than one pre-pass chain, so two chains run side by side.
-// Batches still reach the volume strictly in order (main stream).
+// Pipeline over three in-order streams.  Batch b owns pipeline slot p = b mod 3 and pre-pass stream X(b) = aux_stream[b mod 2]; V is
+// the voxel stream (own_stream):
+//   X(b): wait int_done[p] -> [k_reset(p) of batch b-3] -> H2D constants(p) -> [k_reproject_scatter -> k_reproject_fix] -> k_prepare(p) -> k_plan(p) -> event pre_done[p]
+//   V   : wait pre_done[p] -> k_integrate(p) -> event int_done[p]                          (ONE kernel per batch: it is the critical path)
+// so the pre-passes of batches b+1 and b+2 (latency / float64 bound, each a serial chain of launches) overlap each other and
+// k_integrate of batch b (float32 VALU bound): the two chains run staggered, one stream's scatter next to the other's k_prepare.
+// Batches still reach the volume strictly in order (V).
+//
+// Who writes and reads what, for batches b, b+1, b+2 (b+3 is the next user of slot p, b+2 of stream X(b)):
+//
+//   buffer / flag word              written by                        read by                              what separates the next writer from them
+//   ------------------------------  --------------------------------  -----------------------------------  ---------------------------------------------
+//   pinned[p]            (host)     the host, batch b                 H2D constants(b) on X(b)             host waits consts_done[p] before batch b+3
+//   dstage[p] = frames[p], t12,     H2D constants(b) on X(b), behind  scatter, fix, k_prepare(b) on X(b);  X(b+3) waits int_done[p] of b: recorded on V behind
+//     seg, madj, gi                 int_done[p] of b-3                k_integrate(b) on V                  k_integrate(b), itself behind pre_done[p] of b
+//   zbuf / lastzero / zfix [b mod   scatter(b), fix(b); re-armed by   k_prepare(b), all on X(b)            the next writer is scatter(b+2) on the same
+//     2], zero-flag words [b mod 2] k_prepare(b), cleared by k_plan(b)                                     stream, behind k_plan(b): stream order
+//   depth_stage[p] (host frames)    frame copy(b) on the copy stream  scatter(b), k_prepare(b) on X(b),    copy(b+3) waits pre_done[p] of batch b, which
+//                                   behind pre_done[p] of batch b-3   behind copy_done[p]                  k_plan(b) records behind both readers
+//   ht_mask[p], batch[p], nbatch[p] k_prepare(b); cleared by the      k_plan(b) on X(b)                    k_reset stands behind int_done[p] of b, hence
+//                                   k_reset on X(b+3) (or on          (k_integrate reads the mask from     behind k_plan(b); k_prepare(b+3) behind k_reset
+//                                   h->stream: flush_resets, which    plan_rec)                            in stream order, or behind the int_done[p] that
+//                                   re-records int_done[p] behind it)                                      flush_resets recorded
+//   scaled[p], tile_max / tile_lo   k_prepare(b) on X(b)              k_integrate(b) on V, behind          k_prepare(b+3) on X(b+3) behind int_done[p] of b
+//     / tile_lo_fine [p]                                              pre_done[p]
+//   plan_rec[p], plan[p]            k_plan(b); the queue head by      k_integrate(b)                       k_plan(b+3) on X(b+3) behind int_done[p] of b
+//                                   k_integrate(b)
+//   ctr_dev[call parity]            upload_ctr on X(first batch),     scatter, fix of the call's batches   the upload two calls later waits ctr_rd[parity][]
+//                                   the other stream waits ctr_ev                                          of both pre-pass streams, recorded at the call's end
+//   ht_key, ht_slot, unit_key,      k_prepare / k_plan of b and b+1 concurrently, with atomics (unit_slot_acquire); k_integrate takes slots from plan_rec
+//     counters[C_NUNITS...]
+//   pool                            k_integrate only                                                       order of V
+//
+// int_done[p] and pre_done[p] are re-recorded by every user of the slot: a wait captures the record in front of it in host order,
+// which is why each wait is issued before the batch's own record of the same event.  The scatter and the constants copy touch
+// nothing of slot p but dstage[p]; moving them in front of the wait (constants in a ring of their own) was measured and is slower:
+// the two chains then fall into step, scatter next to scatter (profiles/r07a_ab_early_scatter.txt).
+//
+// The main stream of the pipeline is the handle's OWN stream even when the caller has set another one (er_tsdf_set_stream): HIP
+// multiplexes streams over GPU_MAX_HW_QUEUES hardware queues (4 unless the process asks for more), and streams that share a queue
+// run in order.  own_stream and the two pre-pass streams are created back to back and get a queue each; a caller's stream comes
+// from elsewhere and lands on one of theirs -- with 4 queues k_integrate then stood in line behind a whole pre-pass chain and the
+// voxel stream idled 240 us between launches instead of 15 (profiles/r07a_timeline_queues.txt: 146 k frames/s against 188 k with 8
+// queues).  The two are joined at both ends: own_stream waits for what the caller's stream held when er_tsdf_integrate_frames
+// began, and the caller's stream waits for the last voxel pass before the handle uses it for the volume again (join_voxel).
 int run_batch(er_tsdf_t h, int n, const uint16_t* depth_dev, const double* T, const er_warp* warp, int frame0) {
   const int p = (int)(h->batch_no % kDepth), a = (int)(h->batch_no % kAux);
   h->batch_no++;
@@ -373,7 +429,7 @@ int run_batch(er_tsdf_t h, int n, const uint16_t* depth_dev, const double* T, co
     for (int q = 0; q < 16; q++) st->fxT[q][f] = reinterpret_cast<const float*>(&st->fx[f])[q];
   }
   static_assert(offsetof(Staging, fxT) == sizeof(er::FrameXform) * ER_MAX_BATCH && sizeof(er::FrameXform) == 64, "fxT lies directly behind fx");
-  hipStream_t X = h->aux_stream[a], S = h->stream;
+  hipStream_t X = h->aux_stream[a], S = h->own_stream;     // (the voxel stream: joined to h->stream by er_tsdf_integrate_frames)
   int* nbatch = h->counters + kNbatchSlot[p];
 
   constexpr int kIntBlocksPerCu = 3;                          // persistent workgroups fed by the queue.  Fewer than fit: the pre-pass kernels need register
@@ -509,6 +565,11 @@ int er_tsdf_create(int cols, int rows, const float cam6[6], int max_units, int d
     return er::fail("er_tsdf_create: hipStreamCreate failed");
   }
   h->stream = h->own_stream;
+  if (hipEventCreateWithFlags(&h->caller_ev, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&h->voxel_done, hipEventDisableTiming) != hipSuccess) {
+    er_tsdf_destroy(h);
+    return er::fail("er_tsdf_create: event allocation failed");
+  }
   for (int q = 0; q < kDepth; q++) {
     if (hipEventCreateWithFlags(&h->pre_done[q], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->int_done[q], hipEventDisableTiming) != hipSuccess ||
@@ -576,6 +637,9 @@ int er_tsdf_destroy(er_tsdf_t h) {
   if (!h) return 0;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
+  if (h->own_stream && h->own_stream != h->stream) (void)hipStreamSynchronize(h->own_stream);
+  if (h->caller_ev) (void)hipEventDestroy(h->caller_ev);
+  if (h->voxel_done) (void)hipEventDestroy(h->voxel_done);
   for (auto& ev : h->events) {
     (void)hipEventDestroy(ev.first);
     (void)hipEventDestroy(ev.second);
@@ -754,6 +818,11 @@ int er_tsdf_integrate_frames(er_tsdf_t h, int n, const uint16_t* depth, int dept
   // (a voxel is loaded once per launch, so the short tail launch would pay the full volume traffic for a third of the frames)
   const int launches = (n + ER_MAX_BATCH - 1) / ER_MAX_BATCH;
   const int per = launches > 0 ? (n + launches - 1) / launches : 0;
+  const bool joined = h->stream != h->own_stream && n > 0;    // the voxel passes run on own_stream (run_batch): behind the caller's stream ...
+  if (joined) {
+    ER_HIP_TRY(hipEventRecord(h->caller_ev, h->stream));
+    ER_HIP_TRY(hipStreamWaitEvent(h->own_stream, h->caller_ev, 0));
+  }
   for (int start = 0; start < n; start += per) {
     const int nb = std::min(per, n - start);
     const uint16_t* ddev;
@@ -774,7 +843,12 @@ int er_tsdf_integrate_frames(er_tsdf_t h, int n, const uint16_t* depth, int dept
     }
     if (run_batch(h, nb, ddev, T + (size_t)start * 16, warp, start)) return 1;
   }
-  if (warp) {                                               // the last readers of this call's lattice buffer, per pre-pass stream
+  // ... and in front of whatever the handle puts on the caller's stream next (join_voxel: own_stream is in order, so its last event will do)
+  if (joined) {
+    ER_HIP_TRY(hipEventRecord(h->voxel_done, h->own_stream));
+    h->voxel_ahead = true;
+  }
+  if (warp) {                                              // the last readers of this call's lattice buffer, per pre-pass stream
     for (int a = 0; a < kAux; a++) ER_HIP_TRY(hipEventRecord(h->ctr_rd[h->ctr_cur][a], h->aux_stream[a]));
     h->ctr_rd_set[h->ctr_cur] = true;
   }

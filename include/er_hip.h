@@ -78,8 +78,10 @@ typedef struct er_warp {
 int er_tsdf_create(int cols, int rows, const float cam6[6], int max_units, int device, er_tsdf_t* out);
 int er_tsdf_destroy(er_tsdf_t h);
 
-/* Run the handle's voxel pass and every other call on an existing hipStream_t (e.g. torch's current stream).
- * NULL = the handle's own stream.  (The pre-passes always use two internal auxiliary streams.) */
+/* Order the handle's work with an existing hipStream_t (e.g. torch's current stream): every call but the batch pipeline runs on it.
+ * NULL = the handle's own stream.  (The pre-passes always use two internal auxiliary streams and the voxel pass the handle's own stream,
+ * so that the three never share a hardware queue; the voxel passes of er_tsdf_integrate_frames wait for what the stream held when the
+ * call began, and the stream waits for them before the handle uses it for the volume again.) */
 int er_tsdf_set_stream(er_tsdf_t h, void* hip_stream);
 int er_tsdf_synchronize(er_tsdf_t h);
 

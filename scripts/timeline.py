@@ -6,7 +6,9 @@ def short(name):
     # "(anonymous namespace)::k_x(args)" and "void (anonymous namespace)::k_x<true>(args)" -> k_x
     if name.startswith("(anonymous namespace)::") or name.startswith("void (anonymous namespace)::"):
         name = name.split("(anonymous namespace)::", 1)[1]
-    return name.split("(")[0].split("<")[0][:22]
+    if name.startswith("void "):
+        name = name[5:]
+    return name.split("(")[0].split("<")[0].split("::")[-1][:22]          # (er_tsdf_k::k_prepare: the kernels with external linkage)
 ks = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"]), short(r["Kernel_Name"]), r.get("Queue_Id", "?")) for r in rows]
 ks.sort()
 ints = [i for i, k in enumerate(ks) if k[2].startswith("k_integrate")]
