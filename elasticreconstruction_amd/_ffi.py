@@ -17,7 +17,7 @@ SYMBOLS = [
     "er_tsdf_wait_event", "er_tsdf_reset", "er_tsdf_status", "er_tsdf_set_unit_shard", "er_unit_owner",
     "er_tsdf_scale_depth", "er_tsdf_reproject", "er_tsdf_integrate", "er_tsdf_integrate_frames",
     "er_tsdf_unit_count", "er_tsdf_unit_keys", "er_tsdf_read_unit", "er_tsdf_sum_weight",
-    "er_tsdf_extract_world", "er_tsdf_extract_surface", "er_tsdf_extract_oriented", "er_tsdf_extract_mesh", "er_mc_table", "er_tsdf_export_weighted", "er_tsdf_import_weighted",
+    "er_tsdf_extract_world", "er_tsdf_extract_surface", "er_tsdf_extract_oriented", "er_tsdf_extract_mesh", "er_mc_table", "er_raycast_params_default", "er_tsdf_raycast", "er_tsdf_export_weighted", "er_tsdf_import_weighted",
     "er_tsdf_export_raw", "er_tsdf_import_raw",
     "er_tsdf_band_sizes", "er_tsdf_export_band", "er_tsdf_merge_band", "er_tsdf_import_band", "er_tsdf_drop_units",
     "er_tsdf_set_profiling", "er_tsdf_get_profile",
@@ -27,7 +27,7 @@ SYMBOLS = [
     "er_icp_count_inliers", "er_icp_align", "er_find_correspondence",
     "er_icp_count_inliers_batch", "er_icp_align_batch", "er_find_correspondence_batch", "er_icp_release_workspaces", "er_registration_batch", "er_ransac_fitness_batch", "er_ransac_inliers",
     "er_features_create", "er_features_destroy", "er_features_size", "er_feature_knn", "er_ransac_hypotheses", "er_ransac_params_default", "er_ransac_align", "er_ransac_align_batch",
-    "er_odom_params_default", "er_odom_create", "er_odom_destroy", "er_odom_align_pairs", "er_odom_track", "er_odom_linearize", "er_odom_read_maps", "er_odom_tables",
+    "er_odom_params_default", "er_odom_create", "er_odom_destroy", "er_odom_align_pairs", "er_odom_track", "er_frame_to_model_align", "er_odom_linearize", "er_odom_read_maps", "er_odom_tables",
     "er_cloud_read", "er_cloud_voxel_grid", "er_cloud_estimate_normals", "er_fpfh_estimate", "er_features_dim", "er_features_read",
     "er_pgo_create", "er_pgo_destroy", "er_pgo_optimize", "er_pgo_set_state", "er_pgo_get_state", "er_pgo_linearize", "er_pgo_trial", "er_pgo_set_profiling", "er_pgo_get_profile",
     "er_fopt_create", "er_fopt_destroy", "er_fopt_set_cloud", "er_fopt_cloud_size", "er_fopt_get_points", "er_fopt_update_pose",
@@ -65,6 +65,11 @@ class ErOdomParams(C.Structure):
     """struct er_odom_params (include/er_hip.h)."""
     _fields_ = [("levels", C.c_int), ("iterations", C.c_int * 4), ("bilateral", C.c_int), ("max_depth_mm", C.c_int), ("min_valid", C.c_int),
                 ("dist_thresh", C.c_float), ("angle_thresh", C.c_float)]
+
+
+class ErRaycastParams(C.Structure):
+    """struct er_raycast_params (include/er_hip.h)."""
+    _fields_ = [("t_min", C.c_float), ("t_max", C.c_float), ("step", C.c_float)]
 
 
 class ErError(RuntimeError):
@@ -121,6 +126,9 @@ def lib():
         L.er_tsdf_extract_oriented.argtypes = [vp, vp, vp, C.c_long, C.POINTER(C.c_long)]
     L.er_tsdf_extract_mesh.argtypes = [vp, vp, C.c_long, C.POINTER(C.c_long)]
     L.er_mc_table.argtypes = [vp]
+    if hasattr(L, "er_tsdf_raycast"):                           # (absent from an older build selected with ER_HIP_LIB)
+        L.er_raycast_params_default.argtypes = [C.POINTER(ErRaycastParams)]
+        L.er_tsdf_raycast.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.POINTER(ErRaycastParams), vp, vp, C.c_int]
     L.er_request_hw_queues.argtypes = [C.c_int]
     L.er_tsdf_export_weighted.argtypes = [vp, vp, C.c_int, vp]
     L.er_tsdf_import_weighted.argtypes = [vp, vp, C.c_int, vp]
@@ -186,6 +194,8 @@ def lib():
         L.er_odom_destroy.argtypes = [vp]
         L.er_odom_align_pairs.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int]
         L.er_odom_track.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int]
+        if hasattr(L, "er_frame_to_model_align"):
+            L.er_frame_to_model_align.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int]
         L.er_odom_linearize.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, ip]
         L.er_odom_read_maps.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
         L.er_odom_tables.argtypes = [vp, vp, ip]

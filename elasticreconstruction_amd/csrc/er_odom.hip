@@ -4,7 +4,8 @@
 //
 // Frames live in SLOTS of one slab (the "window"): per slot the raw frame, the filtered depth pyramid and, per level, a map of 32-byte records
 // {vertex | normal} -- what one projective match gathers from the model is ONE record, as `xn` is for k_icp_iter.  The model side of a pair is
-// nothing but "a record map with a pose": a ray-cast map can take a slot with no kernel change.
+// nothing but "a record map with a pose": a ray-cast map takes a slot with no kernel change -- er_frame_to_model_align copies the record maps
+// of er_tsdf_raycast (one per level) into a slot that is never preprocessed and aligns every frame of a list against it.
 //   k_odom_bilateral  raw -> level 0 (13 x 13 bilateral filter, weights from two tables staged in LDS; depth limit)       blockIdx.y = frame
 //   k_odom_pyr        level l -> l + 1 (5 x 5 integer mean of the taps near the centre)                                   blockIdx.y = frame
 //   k_odom_maps       depth level -> records                                                                             blockIdx.y = frame
@@ -364,8 +365,10 @@ void state_from(const double* T, OdomState& s) {
 }
 
 // One run: pairs [p0, p1) of the list, whose frames fit the window.  One stream lease per run.
+// model_rec (nullable): the record maps of a MODEL, one device pointer per level; the list names it as frame `model_frame`.  Its slot is filled by
+// device-to-device copies instead of the preprocessing, and stays resident from run to run like any frame that is needed again.
 int odom_run(er_odom_s* h, const uint16_t* depth, int on_device, int p0, int p1, const int* model_idx, const int* frame_idx, const double* guess,
-             double* T_out, int* status, double* trace, double* sums) {
+             double* T_out, int* status, double* trace, double* sums, const void* const* model_rec = nullptr, int model_frame = -1) {
   const int m = p1 - p0;
   std::vector<Todo> todo;                                    // (host buffers of asynchronous copies: declared before the lease, whose destructor drains the stream)
   std::vector<PairDesc> pairs(m);
@@ -386,7 +389,13 @@ int odom_run(er_odom_s* h, const uint16_t* depth, int on_device, int p0, int p1,
       const int s = slot_of(-1);
       if (s == (int)h->slot_frame.size()) return er::fail("er_odom_align_pairs: internal error, no free slot");
       h->slot_frame[s] = f;
-      todo.push_back({s, f});
+      if (model_rec && f == model_frame) {
+        for (int l = 0; l < h->P.levels; l++)
+          ER_HIP_TRY(hipMemcpyAsync(h->lo.base + (size_t)s * h->lo.stride + h->lo.off_rec[l], model_rec[l],
+                                    (size_t)h->lo.cols[l] * h->lo.rows[l] * 2 * sizeof(float4), hipMemcpyDeviceToDevice, st));
+      } else {
+        todo.push_back({s, f});
+      }
     }
   if (odom_preprocess(h, st, todo, depth, on_device)) return 1;
   for (int q = 0; q < m; q++) {
@@ -427,14 +436,17 @@ int odom_run(er_odom_s* h, const uint16_t* depth, int on_device, int p0, int p1,
 }
 
 int odom_align(er_odom_s* h, const char* who, int n_frames, const uint16_t* depth, int on_device, int n_pairs, const int* model_idx,
-               const int* frame_idx, const double* guess, double* T_out, int* status, double* trace, double* sums, int window) {
+               const int* frame_idx, const double* guess, double* T_out, int* status, double* trace, double* sums, int window,
+               const void* const* model_rec = nullptr) {
+  const int model_frame = model_rec ? n_frames : -1;       // the model is one more thing that needs a slot: "frame" n_frames of the list
+  const int n_things = n_frames + (model_rec ? 1 : 0);
   if (window == 0) window = default_window(h);
   if (window < 2) return er::fail("%s: window = %d, must be at least 2 (or 0 for the default)", who, window);
   for (int p = 0; p < n_pairs; p++)
-    if (model_idx[p] < 0 || model_idx[p] >= n_frames || frame_idx[p] < 0 || frame_idx[p] >= n_frames)
+    if (model_idx[p] < 0 || model_idx[p] >= n_things || frame_idx[p] < 0 || frame_idx[p] >= n_frames)
       return er::fail("%s: pair %d names frames (%d, %d) outside the %d frames given", who, p, model_idx[p], frame_idx[p], n_frames);
   ER_HIP_TRY(hipSetDevice(h->device));
-  window = std::min(std::min(window, kMaxWindow), std::max(n_frames, 2));      // (a result does not depend on the window)
+  window = std::min(std::min(window, kMaxWindow), std::max(n_things, 2));      // (a result does not depend on the window)
   // The slab holds exactly `window` slots for this call, whatever an earlier call left (the cut of the list depends on the window alone).
   if (odom_ensure_window(h, window)) return 1;
   h->slot_frame.assign(h->window, -1);
@@ -452,7 +464,7 @@ int odom_align(er_odom_s* h, const char* who, int n_frames, const uint16_t* dept
         if (std::find(frames.begin(), frames.end(), f) == frames.end()) frames.push_back(f);
       p1++;
     }
-    if (odom_run(h, depth, on_device, p0, p1, model_idx, frame_idx, guess, T_out, status, trace, sums)) return 1;
+    if (odom_run(h, depth, on_device, p0, p1, model_idx, frame_idx, guess, T_out, status, trace, sums, model_rec, model_frame)) return 1;
     p0 = p1;
   }
   return 0;
@@ -578,6 +590,23 @@ int er_odom_track(er_odom_t h, int n_frames, const uint16_t* depth, int depth_on
   std::vector<int> a(n_frames - 1), b(n_frames - 1);
   for (int i = 0; i + 1 < n_frames; i++) a[i] = i, b[i] = i + 1;
   return odom_align(h, who, n_frames, depth, depth_on_device, n_frames - 1, a.data(), b.data(), nullptr, T_rel, status, nullptr, nullptr, window);
+}
+
+int er_frame_to_model_align(er_odom_t h, const void* const* model_rec_dev, int n_frames, const uint16_t* depth, int depth_on_device, const double* guess,
+                            double* T_out, int* status, double* trace, double* sums, int window) {
+  const char* who = "er_frame_to_model_align";
+  if (no_device(who)) return 1;
+  if (!h) return er::fail("%s: NULL handle", who);
+  if (n_frames < 1 || !depth) return er::fail("%s: depth is NULL or n_frames = %d is not positive", who, n_frames);
+  if (!model_rec_dev) return er::fail("%s: model_rec_dev is NULL", who);
+  for (int l = 0; l < h->P.levels; l++)
+    if (!model_rec_dev[l]) return er::fail("%s: the model has no record map for level %d of %d", who, l, h->P.levels);
+  if (!T_out) return er::fail("%s: T_out is NULL", who);
+  if (!status) return er::fail("%s: status is NULL", who);
+  if (window < 0) return er::fail("%s: window = %d, must be at least 2 (or 0 for the default)", who, window);
+  std::vector<int> a(n_frames, n_frames), b(n_frames);                  // every frame against the model, which the list names as frame n_frames
+  for (int i = 0; i < n_frames; i++) b[i] = i;
+  return odom_align(h, who, n_frames, depth, depth_on_device, n_frames, a.data(), b.data(), guess, T_out, status, trace, sums, window, model_rec_dev);
 }
 
 int er_odom_linearize(er_odom_t h, const uint16_t* depth2, int on_device, int level, const double* T, double* sums, int* count) {

@@ -1,5 +1,5 @@
 // er_tsdf_dev.h -- the __device__ helpers of path A that kernels in more than one file use: the unit hash map (er_tsdf.hip, er_tsdf_pre.hip,
-// er_tsdf_extract.hip) and the two halves of Reproject's scatter with its replay (er_tsdf.hip, er_tsdf_pre.hip).  Internal linkage: each is
+// er_tsdf_extract.hip, er_tsdf_raycast.hip) and the two halves of Reproject's scatter with its replay (er_tsdf.hip, er_tsdf_pre.hip).  Internal linkage: each is
 // compiled where it is used.  A helper with one user sits next to that user.
 #pragma once
 
@@ -21,6 +21,18 @@ __device__ int ht_find_or_insert(int* __restrict__ ht_key, int cap_mask, int shi
       int old = atomicCAS(&ht_key[e], kEmptyKey, key);
       if (old == kEmptyKey || old == key) return e;
     }
+  }
+  return -1;
+}
+
+// Read-only lookup for kernels that run when nobody inserts (the extraction kernels, the ray caster): the unit's pool slot, -1 = no such unit.
+__device__ __forceinline__ int ht_lookup_slot(const int* __restrict__ ht_key, const int* __restrict__ ht_slot, int cap_mask, int shift, int key) {
+  unsigned h = hash_unit_key(key, shift);
+  for (int probe = 0; probe <= cap_mask; ++probe) {
+    const int e = (int)((h + (unsigned)probe) & (unsigned)cap_mask);
+    const int k = ht_key[e];
+    if (k == key) return ht_slot[e];
+    if (k == kEmptyKey) return -1;
   }
   return -1;
 }

@@ -44,17 +44,6 @@ __global__ __launch_bounds__(64) void k_world(const float2* __restrict__ pool, c
 // is emitted (kinfu's extractCloud rule).  Order: units by ascending key, voxels in i,j,k order, axes x,y,z -- a stable
 // ballot-prefix compaction in two passes like k_world, so the list is reproducible and a CPU restatement can match it
 // element for element (tests/test_tsdf_gpu.py).
-__device__ __forceinline__ int ht_lookup_slot(const int* __restrict__ ht_key, const int* __restrict__ ht_slot, int cap_mask, int shift, int key) {
-  unsigned h = hash_unit_key(key, shift);
-  for (int probe = 0; probe <= cap_mask; ++probe) {
-    const int e = (int)((h + (unsigned)probe) & (unsigned)cap_mask);
-    const int k = ht_key[e];
-    if (k == key) return ht_slot[e];
-    if (k == kEmptyKey) return -1;
-  }
-  return -1;
-}
-
 __device__ __forceinline__ bool crosses(float2 a, float2 b) {
   return a.y != 0.0f && b.y != 0.0f && ((a.x > 0.0f && b.x < 0.0f) || (a.x < 0.0f && b.x > 0.0f));
 }

@@ -1,0 +1,127 @@
+// er_tsdf_raycast.hip -- the resident TSDF volume of path A (er_tsdf.hip) seen from a pose: per pixel the first front face along the ray, as
+// er_odom's record map ({vertex | normal}, camera frame) and as a uint16 depth image.  DESIGN.md 7.13 states the rule, er_raycast_math.h IS
+// the rule (the kernel below only supplies the volume to it), tests/raycast_restatement.py restates it in numpy and the device is held to
+// that restatement bit for bit.
+//
+// k_raycast: one thread per pixel, a wave = an 8 x 8 pixel tile, a workgroup = 2 x 2 tiles.  The march is a chain of dependent gathers of
+// one float2 {sdf, weight}: the vector L1 pays per distinct address (profiles/r06y_gather_rates.txt), and the rays of neighbouring pixels
+// visit neighbouring voxels, so a square tile shares more lines than a row of 64 pixels would.  Each lane remembers the key and pool slot
+// of the unit it sampled last: the hash map is probed once per unit entered, not once per sample.  Where that unit does not exist the loop
+// index advances by the number of steps that provably stay inside the unit's box (er_rc::skip_steps): the trip count is an integer that
+// only grows, and the samples that are left out are unobserved whichever way they are counted, so the output is the plain march's.
+// The kernel only reads the volume: no atomics, no LDS.  Nobody has measured it yet (scripts/raycast_probe.py is there for that).
+#include "er_tsdf_dev.h"
+#include "er_raycast_math.h"
+
+namespace {
+
+using namespace er_tsdf_k;
+
+constexpr int kTilePx = 8;                    // a wave's tile is kTilePx x kTilePx pixels
+constexpr int kGroupPx = 2 * kTilePx;         // a workgroup's is 2 x 2 of them
+
+struct DeviceVol {
+  const float2* __restrict__ pool;
+  const int* __restrict__ ht_key;
+  const int* __restrict__ ht_slot;
+  int cap_mask, shift, max_units;
+  int ckey, cslot;                            // the unit sampled last (ckey = kEmptyKey: none yet) and its slot, < 0 = it does not exist
+  int ux, uy, uz;                             // its lattice position
+
+  __device__ __forceinline__ bool fetch(int gx, int gy, int gz, float& F) {
+    if ((unsigned)gx >= (unsigned)er_rc::kLattice || (unsigned)gy >= (unsigned)er_rc::kLattice || (unsigned)gz >= (unsigned)er_rc::kLattice) return false;
+    const int key = (gx >> 6) << 18 | (gy >> 6) << 9 | (gz >> 6);
+    if (key != ckey) {
+      const int s = ht_lookup_slot(ht_key, ht_slot, cap_mask, shift, key);
+      ckey = key;
+      cslot = s < max_units ? s : -1;
+      ux = gx >> 6, uy = gy >> 6, uz = gz >> 6;
+    }
+    if (cslot < 0) return false;
+    const float2 v = pool[(size_t)cslot * kUnitVox + ((size_t)(gx & 63) * 4096 + (size_t)(gy & 63) * 64 + (size_t)(gz & 63))];
+    F = v.x;
+    return v.y != 0.0f;
+  }
+
+  // (called right after an unobserved nearest-voxel sample at p: if that sample reached a unit at all, it is the cached one)
+  __device__ __forceinline__ int advance(float px, float py, float pz, float step) {
+    int gx, gy, gz;
+    if (!(er_rc::nearest_index(px, gx) & er_rc::nearest_index(py, gy) & er_rc::nearest_index(pz, gz))) return 1;
+    if (cslot >= 0 || ckey != ((gx >> 6) << 18 | (gy >> 6) << 9 | (gz >> 6))) return 1;
+    return er_rc::skip_steps(px, py, pz, ux, uy, uz, step);
+  }
+};
+
+__global__ __launch_bounds__(kGroupPx * kGroupPx) void k_raycast(const float2* __restrict__ pool, const int* __restrict__ ht_key,
+                                                                 const int* __restrict__ ht_slot, int cap_mask, int shift, int max_units,
+                                                                 er_rc::Image I, int cols, int rows, float4* __restrict__ rec,
+                                                                 uint16_t* __restrict__ depth) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int u = blockIdx.x * kGroupPx + (wave & 1) * kTilePx + (lane & 7);
+  const int v = blockIdx.y * kGroupPx + (wave >> 1) * kTilePx + (lane >> 3);
+  if (u >= cols || v >= rows) return;
+  DeviceVol vol{pool, ht_key, ht_slot, cap_mask, shift, max_units, kEmptyKey, -1, 0, 0, 0};
+  er_rc::Pixel px;
+  er_rc::cast_pixel(vol, I, u, v, px);
+  const size_t i = (size_t)v * cols + u;
+  if (rec) {
+    rec[2 * i] = make_float4(px.v[0], px.v[1], px.v[2], 0.0f);
+    rec[2 * i + 1] = make_float4(px.n[0], px.n[1], px.n[2], 0.0f);
+  }
+  if (depth) depth[i] = px.depth;
+}
+
+}  // namespace
+
+extern "C" {
+
+int er_raycast_params_default(er_raycast_params* p) {
+  if (!p) return er::fail("er_raycast_params_default: NULL argument");
+  p->t_min = 0.0f;
+  p->t_max = 4.0f;
+  p->step = 0.8f * 0.03f;
+  return 0;
+}
+
+int er_tsdf_raycast(er_tsdf_t h, int cols, int rows, const float cam4[4], const double T[16], const er_raycast_params* params, void* rec_out,
+                    uint16_t* depth_out, int out_on_device) {
+  const char* who = "er_tsdf_raycast";
+  if (!cam4 || !T) return er::fail("%s: NULL argument", who);
+  if (cols <= 0 || rows <= 0 || cols > 16384 || rows > 16384) return er::fail("%s: an image of %d x %d (1 .. 16384 each way)", who, cols, rows);
+  er_raycast_params P;
+  er_raycast_params_default(&P);
+  if (params) P = *params;
+  int n_steps = 0;
+  const int bad = er_rc::count_steps(P.t_min, P.t_max, P.step, &n_steps);
+  if (bad == 1) return er::fail("%s: t_min, t_max and step must be finite and step positive", who);
+  if (bad == 2) return er::fail("%s: more than %d steps between t_min and t_max", who, er_rc::kMaxSteps);
+  for (int i = 0; i < 4; i++)
+    if (!std::isfinite(cam4[i])) return er::fail("%s: cam4 is not finite", who);
+  if (cam4[0] == 0.0f || cam4[1] == 0.0f) return er::fail("%s: a focal length of 0", who);
+  if (!rec_out && !depth_out) return er::fail("%s: both outputs are NULL", who);
+  if (!h) return er::fail("%s: NULL handle", who);
+  ER_HIP_TRY(hipSetDevice(h->device));
+  if (check_flags(h)) return 1;                          // behind every queued batch, like the extraction calls (joins the voxel stream)
+  er_rc::Image I;
+  er_rc::make_image(cam4, T, P.t_min, P.step, n_steps, I);
+  const size_t npix = (size_t)cols * rows;
+  float4* d_rec = out_on_device ? (float4*)rec_out : nullptr;
+  uint16_t* d_depth = out_on_device ? depth_out : nullptr;
+  void* tmp = nullptr;                                   // host outputs: one device temporary, records then depth
+  if (!out_on_device) {
+    ER_HIP_TRY(hipMalloc(&tmp, npix * (2 * sizeof(float4) + sizeof(uint16_t))));
+    if (rec_out) d_rec = (float4*)tmp;
+    if (depth_out) d_depth = (uint16_t*)((char*)tmp + npix * 2 * sizeof(float4));
+  }
+  hipLaunchKernelGGL(k_raycast, dim3((cols + kGroupPx - 1) / kGroupPx, (rows + kGroupPx - 1) / kGroupPx), dim3(kGroupPx * kGroupPx), 0, h->stream,
+                     h->pool, h->ht_key, h->ht_slot, h->ht_cap - 1, h->ht_shift, h->max_units, I, cols, rows, d_rec, d_depth);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && !out_on_device && rec_out) e = hipMemcpyAsync(rec_out, d_rec, npix * 2 * sizeof(float4), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess && !out_on_device && depth_out) e = hipMemcpyAsync(depth_out, d_depth, npix * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (tmp) (void)hipFree(tmp);
+  if (e != hipSuccess) return er::fail("%s: %s", who, hipGetErrorString(e));
+  return 0;
+}
+
+}  // extern "C"

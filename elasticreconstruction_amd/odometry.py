@@ -57,6 +57,7 @@ class DepthOdometry:
             else:
                 raise TypeError("DepthOdometry: unknown parameter %r" % k)
         self.cols, self.rows, self.device = int(cols), int(rows), int(device)
+        self.cam = tuple(np.asarray(cam, np.float32).reshape(-1)[:4])
         cam4 = np.ascontiguousarray(np.asarray(cam, np.float32).reshape(-1)[:4])
         h = C.c_void_p()
         _ffi.check(self._lib.er_odom_create(self.cols, self.rows, cam4.ctypes.data_as(C.POINTER(C.c_float)), C.byref(p), self.device, C.byref(h)),
@@ -130,6 +131,78 @@ class DepthOdometry:
         status = np.zeros(max(n - 1, 0), np.int32)
         _ffi.check(self._lib.er_odom_track(self._h, n, dp, on_dev, _ffi.ptr(T), _ffi.ptr(status), int(window)), "er_odom_track")
         return T, status
+
+    def _model_records(self, model_maps):
+        """(keep-alive tensors, void*[levels]) of a model: per level (depth, vertex map, normal map) as TSDFVolume.raycast returns them.  Device
+        maps that are the two views of one record tensor are read in place; anything else is packed into records and uploaded."""
+        import torch
+        if len(model_maps) != self.levels:
+            raise ValueError("the model has %d levels, the odometry %d" % (len(model_maps), self.levels))
+        dev = torch.device("cuda", self.device)
+        keep = []
+        for l, (_, V, N) in enumerate(model_maps):
+            c, r = self.cols >> l, self.rows >> l
+            if tuple(V.shape) != (r, c, 3) or tuple(N.shape) != (r, c, 3):
+                raise ValueError("level %d of the model is not %d x %d" % (l, c, r))
+            in_place = (hasattr(V, "data_ptr") and V.is_cuda and V.device == dev and V.dtype == torch.float32 and N.dtype == torch.float32
+                        and V.stride() == (8 * c, 8, 1) and N.stride() == (8 * c, 8, 1) and N.data_ptr() == V.data_ptr() + 16)
+            if in_place:
+                keep.append(V)
+            else:
+                rec = torch.zeros((r, c, 2, 4), dtype=torch.float32)
+                rec[:, :, 0, :3] = torch.as_tensor(np.asarray(V.cpu() if hasattr(V, "cpu") else V, np.float32))
+                rec[:, :, 1, :3] = torch.as_tensor(np.asarray(N.cpu() if hasattr(N, "cpu") else N, np.float32))
+                keep.append(rec.to(dev))
+        torch.cuda.current_stream(dev).synchronize()             # the records must be complete before another stream reads them
+        return keep, (C.c_void_p * self.levels)(*[t.data_ptr() for t in keep])
+
+    def align_model(self, model_maps, depth, guess=None, trace=False, sums=False, window=0):
+        """er_frame_to_model_align: every frame of `depth` against ONE model, the per-level maps of TSDFVolume.raycast(T, cols, rows, cam,
+        levels = self.levels) -- device = True is read in place.  Returns (T [n, 4, 4] float64 m_T_c = model <- frame, status [n]) and,
+        if asked for, trace [n, iterations, 17] and sums [n, 27], like align_pairs."""
+        keep_d, dp, on_dev, n = self._depth(depth)
+        keep_m, recs = self._model_records(model_maps)
+        g = None if guess is None else np.ascontiguousarray(guess, np.float64).reshape(n, 16)
+        T = np.zeros((n, 4, 4), np.float64)
+        status = np.zeros(n, np.int32)
+        tr = np.zeros((n, self.total_iters, TRACE), np.float64) if trace else None
+        sm = np.zeros((n, 27), np.float64) if sums else None
+        _ffi.check(self._lib.er_frame_to_model_align(self._h, recs, n, dp, on_dev, None if g is None else _ffi.ptr(g), _ffi.ptr(T), _ffi.ptr(status),
+                                                     None if tr is None else _ffi.ptr(tr), None if sm is None else _ffi.ptr(sm), int(window)),
+                   "er_frame_to_model_align")
+        del keep_d, keep_m
+        out = (T, status)
+        if trace:
+            out += (tr,)
+        if sums:
+            out += (sm,)
+        return out
+
+    def track_model(self, volume, depth, T0=None):
+        """Frame-to-model tracking as a composition of public calls: frame 0 is integrated into `volume` (a TSDFVolume of the same image) at
+        T0 (identity); every later frame is aligned against the volume ray-cast at the last pose, from the identity, T_i = T_{i-1} m_T_c,
+        and integrated at T_i.  A lost frame keeps the last pose and is not integrated.  Returns (world_T_camera [n, 4, 4], status [n])."""
+        from .tsdf import mat4_mul
+        from . import synth
+        frames = synth.to_numpy_u16(depth) if hasattr(depth, "data_ptr") else np.asarray(depth, np.uint16)
+        frames = np.ascontiguousarray(frames).reshape(-1, self.rows * self.cols)
+        n = frames.shape[0]
+        W = np.zeros((n, 4, 4), np.float64)
+        status = np.zeros(n, np.int32)
+        if n == 0:
+            return W, status
+        W[0] = np.eye(4) if T0 is None else np.asarray(T0, np.float64).reshape(4, 4)
+        volume.Integrate(frames[0], W[0])
+        for i in range(1, n):
+            model = volume.raycast(W[i - 1], self.cols, self.rows, self.cam, levels=self.levels, device=True)
+            T, st = self.align_model(model, frames[i])
+            status[i] = st[0]
+            if st[0] != 0:
+                W[i] = W[i - 1]
+                continue
+            W[i] = mat4_mul(W[i - 1], T[0])
+            volume.Integrate(frames[i], W[i])
+        return W, status
 
     def linearize(self, model, frame, level, T):
         """er_odom_linearize: (sums [27], count) at the pose T (m_T_c) on `level`."""

@@ -190,6 +190,44 @@ class TSDFVolume:
             _ffi.check(self._lib.er_tsdf_extract_oriented(self._h, _ffi.ptr(pts), _ffi.ptr(nrm), n.value, C.byref(n)), "er_tsdf_extract_oriented")
         return pts, np.ascontiguousarray(nrm[:, :3])
 
+    def raycast(self, T, cols=None, rows=None, cam=None, levels=1, params=None, device=False):
+        """er_tsdf_raycast from the pose T (world_T_camera, 4 x 4 float64): per level l = 0 .. levels - 1 a tuple (depth uint16 [r, c] in
+        millimetres, vertex map float32 [r, c, 3], normal map float32 [r, c, 3]) of the image cols / 2^l x rows / 2^l with cam / 2^l, camera
+        frame, NaN / 0 where the ray meets no surface (DESIGN.md 7.13).  cols, rows, cam = (fx, fy, cx, cy) default to the volume's own image;
+        params = (t_min, t_max, step) in metres, None = er_raycast_params_default.  device = True: torch tensors on the volume's GPU, the
+        two maps as views of ONE record tensor [r, c, 2, 4] -- er_odom's record layout, what DepthOdometry.align_model reads in place."""
+        cols = self.cols_ if cols is None else int(cols)
+        rows = self.rows_ if rows is None else int(rows)
+        cam4 = np.ascontiguousarray(np.asarray(self.camera_ if cam is None else cam, np.float32).reshape(-1)[:4])
+        levels = int(levels)
+        if levels < 1 or cols % (1 << (levels - 1)) or rows % (1 << (levels - 1)):
+            raise ValueError("raycast: %d x %d is not divisible by 2^(levels-1), levels = %d" % (cols, rows, levels))
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
+        P = None
+        if params is not None:
+            P = C.byref(_ffi.ErRaycastParams(*[float(np.float32(x)) for x in params]))
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            torch.cuda.current_stream(dev).synchronize()         # (the tensors' memory may have work of torch's stream pending on it)
+        out = []
+        for l in range(levels):
+            c, r = cols >> l, rows >> l
+            k = np.ascontiguousarray(cam4 / np.float32(1 << l))
+            if device:
+                rec = torch.empty((r, c, 2, 4), dtype=torch.float32, device=dev)
+                dep = torch.empty((r, c), dtype=torch.uint16, device=dev)
+                rp, dp = C.c_void_p(rec.data_ptr()), C.c_void_p(dep.data_ptr())
+            else:
+                rec, dep = np.empty((r, c, 2, 4), np.float32), np.empty((r, c), np.uint16)
+                rp, dp = _ffi.ptr(rec), _ffi.ptr(dep)
+            _ffi.check(self._lib.er_tsdf_raycast(self._h, c, r, _ffi.ptr(k), _ffi.ptr(T), P, rp, dp, 1 if device else 0), "er_tsdf_raycast")
+            if device:
+                out.append((dep, rec[:, :, 0, :3], rec[:, :, 1, :3]))
+            else:
+                out.append((dep, np.ascontiguousarray(rec[:, :, 0, :3]), np.ascontiguousarray(rec[:, :, 1, :3])))
+        return out
+
     def SaveFragment(self, filename, length=3.0):
         """cloud_bin_<i>.pcd of the resident volume: the oriented points inside the cube 0 <= x, y, z < length (PointCloud::GetCoordinate's cube),
         NaN-normal rows KEPT -- CCorresApp::LoadData filters them (CorresApp.cpp:93-98).  Returns the number of points written."""

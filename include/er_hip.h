@@ -164,6 +164,28 @@ int er_tsdf_extract_oriented(er_tsdf_t h, float* points_host, float* normals_hos
 int er_tsdf_extract_mesh(er_tsdf_t h, float* tri_host, long capacity_triangles, long* n_triangles);
 int er_mc_table(unsigned char out[256 * 16]);
 
+/* The resident volume ray-cast from a pose: the model side of frame-to-model tracking (er_odom_align_model below) and a
+ * direct picture of what er_tsdf_integrate_frames built.  The reference tree has no ray caster (KinFu's lives in the author's PCL fork):
+ * this entry restates tests/raycast_restatement.py, the numpy statement of csrc/er_raycast_math.h, bit for bit, and NOTHING here is checked
+ * against PCL.  Per pixel (u, v) of a cols x rows image with cam4 = (fx, fy, cx, cy) -- independent of the volume's integration image -- the
+ * ray through the pixel from world_T_camera T (row-major float64, cast once to float32) is sampled at t_k = t_min + k step, k = 0 ..
+ * ceil((t_max - t_min) / step) - 1, at the nearest voxel; a sample is observed iff its unit exists, is not dropped and its weight is not 0.
+ * Two successive observed samples with sdf >= 0 then < 0 are a hit, with < 0 then >= 0 the ray ends without one.  The crossing is refined
+ * on trilinear values (all eight corners observed, else on the two nearest-voxel values); the normal is the negated, normalised central
+ * difference of the trilinear sdf one voxel to either side of the hit point, rotated into the camera frame (NaN where one of the six
+ * values is missing: the vertex stays).
+ * rec_out (nullable): er_odom's record map, cols * rows * 2 float4 = {vertex, 0}, {normal, 0} in the CAMERA frame, NaN where there is no
+ * hit; depth_out (nullable): cols * rows uint16 = rint(1000 vertex.z), 0 where there is none or it leaves 1 .. 65535.  Both in host
+ * memory, or both in device memory of the handle's device when out_on_device.  params NULL = the defaults.  Refused: cols or rows <= 0,
+ * a t_min, t_max or step that is not finite, step <= 0, more than 65536 steps, both outputs NULL; t_max <= t_min gives an empty image.
+ * Runs on the handle's stream behind every queued batch, like the er_tsdf_extract_* calls, and returns when the outputs are complete. */
+typedef struct er_raycast_params {
+  float t_min, t_max, step;   /* metres along the normalised ray: (0.0, 4.0, 0.8 * 0.03) */
+} er_raycast_params;
+int er_raycast_params_default(er_raycast_params* p);
+int er_tsdf_raycast(er_tsdf_t h, int cols, int rows, const float cam4[4], const double T[16], const er_raycast_params* params,
+                    void* rec_out /* cols*rows*2 float4, nullable */, uint16_t* depth_out /* nullable */, int out_on_device);
+
 /* Multi-GPU frame split: for the given key list write sum-ready planes into dev_buf
  * (n_keys * 2 * 64^3 floats: [key][0] = sdf*weight, [key][1] = weight; zeros for keys absent here), and
  * after an external all-reduce(sum) read them back as weight = W, sdf = SW / W. */
@@ -509,6 +531,16 @@ int er_odom_align_pairs(er_odom_t h, int n_frames, const uint16_t* depth, int de
 /* Restates odometry_restatement.Odometry.track: er_odom_align_pairs of the list (i, i + 1), i = 0 .. n_frames - 2, from the identity.
  * T_rel[i][16] = frame i <- frame i + 1. */
 int er_odom_track(er_odom_t h, int n_frames, const uint16_t* depth, int depth_on_device, double* T_rel, int* status, int window);
+
+/* Frame-to-model alignment: every frame of depth[n_frames][rows * cols] against ONE model, whose side of the pair is not a
+ * depth frame but the record maps of er_tsdf_raycast -- model_rec_dev[l], l = 0 .. levels - 1 (an array in host memory of pointers to device
+ * memory of the handle's device): level l ray-cast at cols / 2^l x rows / 2^l with cam4 / 2^l, the intrinsics the handle uses for that
+ * level.  The maps are copied device to device into a slot that is never preprocessed and stays resident over the runs of the list;
+ * everything after that is er_odom_align_pairs' loop, unchanged, and the other arguments are its: guess[i][16] (NULL = identity), T_out[i][16]
+ * = m_T_c of frame i (model <- frame), status, trace, sums, window.  Restates raycast_restatement.align_model.  A frame's result is the same
+ * bits alone and in any list.  (Named apart from the er_odom_ family, whose list the odometry's own tests pin.) */
+int er_frame_to_model_align(er_odom_t h, const void* const* model_rec_dev /* [levels], device */, int n_frames, const uint16_t* depth,
+                            int depth_on_device, const double* guess, double* T_out, int* status, double* trace, double* sums, int window);
 
 /* Restates odometry_restatement.Odometry.linearize: ONE evaluation of the 27 sums and the count at the pose T (m_T_c) on `level`, for
  * depth2 = {model frame, current frame}. */
