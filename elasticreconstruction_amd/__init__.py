@@ -8,6 +8,7 @@ There is no CPU fallback: importing works anywhere, but every operation needs th
 extension and a HIP device.
 """
 from ._ffi import ErError, LIB_PATH, lib  # noqa: F401
+from .fragments import FragmentBuilder  # noqa: F401
 from .odometry import DepthOdometry, accumulate  # noqa: F401
 from .posegraph import PoseGraph, graph_optimizer  # noqa: F401
 
@@ -21,4 +22,4 @@ def request_hw_queues(n=8):
     return int(os.environ["GPU_MAX_HW_QUEUES"])
 
 
-__all__ = ["ErError", "LIB_PATH", "lib", "request_hw_queues", "DepthOdometry", "accumulate", "PoseGraph", "graph_optimizer"]
+__all__ = ["ErError", "LIB_PATH", "lib", "request_hw_queues", "DepthOdometry", "accumulate", "FragmentBuilder", "PoseGraph", "graph_optimizer"]

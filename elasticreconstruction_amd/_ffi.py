@@ -17,7 +17,7 @@ SYMBOLS = [
     "er_tsdf_wait_event", "er_tsdf_reset", "er_tsdf_status", "er_tsdf_set_unit_shard", "er_unit_owner",
     "er_tsdf_scale_depth", "er_tsdf_reproject", "er_tsdf_integrate", "er_tsdf_integrate_frames",
     "er_tsdf_unit_count", "er_tsdf_unit_keys", "er_tsdf_read_unit", "er_tsdf_sum_weight",
-    "er_tsdf_extract_world", "er_tsdf_extract_surface", "er_tsdf_extract_oriented", "er_tsdf_extract_mesh", "er_mc_table", "er_raycast_params_default", "er_tsdf_raycast", "er_tsdf_export_weighted", "er_tsdf_import_weighted",
+    "er_tsdf_extract_world", "er_tsdf_extract_surface", "er_tsdf_extract_oriented", "er_tsdf_extract_mesh", "er_mc_table", "er_raycast_params_default", "er_tsdf_raycast", "er_tsdf_raycast_batch", "er_tsdf_export_weighted", "er_tsdf_import_weighted",
     "er_tsdf_export_raw", "er_tsdf_import_raw",
     "er_tsdf_band_sizes", "er_tsdf_export_band", "er_tsdf_merge_band", "er_tsdf_import_band", "er_tsdf_drop_units",
     "er_tsdf_set_profiling", "er_tsdf_get_profile",
@@ -27,8 +27,9 @@ SYMBOLS = [
     "er_icp_count_inliers", "er_icp_align", "er_find_correspondence",
     "er_icp_count_inliers_batch", "er_icp_align_batch", "er_find_correspondence_batch", "er_icp_release_workspaces", "er_registration_batch", "er_ransac_fitness_batch", "er_ransac_inliers",
     "er_features_create", "er_features_destroy", "er_features_size", "er_feature_knn", "er_ransac_hypotheses", "er_ransac_params_default", "er_ransac_align", "er_ransac_align_batch",
-    "er_odom_params_default", "er_odom_create", "er_odom_destroy", "er_odom_align_pairs", "er_odom_track", "er_frame_to_model_align", "er_odom_linearize", "er_odom_read_maps", "er_odom_tables",
+    "er_odom_params_default", "er_odom_create", "er_odom_destroy", "er_odom_align_pairs", "er_odom_track", "er_frame_to_model_align", "er_frames_to_models_align", "er_odom_linearize", "er_odom_read_maps", "er_odom_tables",
     "er_cloud_read", "er_cloud_voxel_grid", "er_cloud_estimate_normals", "er_fpfh_estimate", "er_features_dim", "er_features_read",
+    "er_frag_params_default", "er_frag_create", "er_frag_destroy", "er_frag_lane_bytes", "er_frag_build", "er_frag_count", "er_frag_read",
     "er_pgo_create", "er_pgo_destroy", "er_pgo_optimize", "er_pgo_set_state", "er_pgo_get_state", "er_pgo_linearize", "er_pgo_trial", "er_pgo_set_profiling", "er_pgo_get_profile",
     "er_fopt_create", "er_fopt_destroy", "er_fopt_set_cloud", "er_fopt_cloud_size", "er_fopt_get_points", "er_fopt_update_pose",
     "er_fopt_update_point_pn", "er_fopt_set_correspondences", "er_fopt_set_correspondences_dev", "er_fopt_group_count", "er_fopt_group_info", "er_fopt_update_normals", "er_fopt_assemble_rigid", "er_fopt_assemble_slac",
@@ -70,6 +71,11 @@ class ErOdomParams(C.Structure):
 class ErRaycastParams(C.Structure):
     """struct er_raycast_params (include/er_hip.h)."""
     _fields_ = [("t_min", C.c_float), ("t_max", C.c_float), ("step", C.c_float)]
+
+
+class ErFragParams(C.Structure):
+    """struct er_frag_params (include/er_hip.h)."""
+    _fields_ = [("interval", C.c_int), ("lanes", C.c_int), ("max_units", C.c_int), ("length", C.c_float), ("raycast", ErRaycastParams)]
 
 
 class ErError(RuntimeError):
@@ -129,6 +135,16 @@ def lib():
     if hasattr(L, "er_tsdf_raycast"):                           # (absent from an older build selected with ER_HIP_LIB)
         L.er_raycast_params_default.argtypes = [C.POINTER(ErRaycastParams)]
         L.er_tsdf_raycast.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.POINTER(ErRaycastParams), vp, vp, C.c_int]
+    if hasattr(L, "er_tsdf_raycast_batch"):
+        L.er_tsdf_raycast_batch.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "er_frag_create"):
+        L.er_frag_params_default.argtypes = [C.POINTER(ErFragParams)]
+        L.er_frag_create.argtypes = [C.c_int, C.c_int, vp, C.POINTER(ErOdomParams), C.POINTER(ErFragParams), C.c_int, C.POINTER(vp)]
+        L.er_frag_destroy.argtypes = [vp]
+        L.er_frag_lane_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
+        L.er_frag_build.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]
+        L.er_frag_count.argtypes = [vp, ip]
+        L.er_frag_read.argtypes = [vp, C.c_int, vp, vp, C.c_long, C.POINTER(C.c_long)]
     L.er_request_hw_queues.argtypes = [C.c_int]
     L.er_tsdf_export_weighted.argtypes = [vp, vp, C.c_int, vp]
     L.er_tsdf_import_weighted.argtypes = [vp, vp, C.c_int, vp]
@@ -196,6 +212,8 @@ def lib():
         L.er_odom_track.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int]
         if hasattr(L, "er_frame_to_model_align"):
             L.er_frame_to_model_align.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int]
+        if hasattr(L, "er_frames_to_models_align"):
+            L.er_frames_to_models_align.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int]
         L.er_odom_linearize.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, ip]
         L.er_odom_read_maps.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
         L.er_odom_tables.argtypes = [vp, vp, ip]

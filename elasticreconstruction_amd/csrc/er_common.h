@@ -33,6 +33,16 @@ hipStream_t tsdf_stream(er_tsdf_s* h);
 int tsdf_device(er_tsdf_s* h);
 }  // namespace er
 
+// er_odom.hip for the fragment builder (er_fragments.hip): er_odom_align_pairs' loop over ANY pair list whose model side may name one of n_models
+// models (model k = "frame" n_frames + k; model_rec_dev[k * levels + l] in device memory), and the handle's level count.
+struct er_odom_s;
+namespace er {
+__attribute__((visibility("hidden"))) int odom_align_models(er_odom_s* h, const char* who, int n_models, const void* const* model_rec_dev, int n_frames,
+                                                            const uint16_t* depth, int on_device, int n_pairs, const int* model_idx, const int* frame_idx,
+                                                            const double* guess, double* T_out, int* status, double* trace, double* sums, int window);
+__attribute__((visibility("hidden"))) int odom_levels(er_odom_s* h);
+}  // namespace er
+
 // er_cloud_create for rows that already live on `device` (er_cloud_create_from_tsdf): xyz_dev / normal_dev are packed [n][3] float arrays in
 // device memory whose contents are complete (their producer's stream has been synchronised); they are free again when the call returns.
 // (Declared here for er_tsdf_extract.hip; the rest of what path B's translation units share is er_cloud.h.)

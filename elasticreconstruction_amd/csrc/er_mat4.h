@@ -48,4 +48,13 @@ inline void mat4_identity(double* M) {
   for (int i = 0; i < 16; i++) M[i] = (i % 5 == 0) ? 1.0 : 0.0;
 }
 
+// The kinfu fragment convention (BuildCorrespondence/CorresApp.cpp:45-48; synth.basepose states it in Python): a fragment's first camera sits
+// at (length / 2, length / 2, -0.3) of the fragment's own length^3 cube, looking along +z.
+inline void frag_basepose(double length, double* M) {
+  mat4_identity(M);
+  M[3] = length / 2.0;
+  M[7] = length / 2.0;
+  M[11] = -0.3;
+}
+
 }  // namespace er

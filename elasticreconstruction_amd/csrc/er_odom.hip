@@ -5,7 +5,8 @@
 // Frames live in SLOTS of one slab (the "window"): per slot the raw frame, the filtered depth pyramid and, per level, a map of 32-byte records
 // {vertex | normal} -- what one projective match gathers from the model is ONE record, as `xn` is for k_icp_iter.  The model side of a pair is
 // nothing but "a record map with a pose": a ray-cast map takes a slot with no kernel change -- er_frame_to_model_align copies the record maps
-// of er_tsdf_raycast (one per level) into a slot that is never preprocessed and aligns every frame of a list against it.
+// of er_tsdf_raycast (one per level) into a slot that is never preprocessed and aligns every frame of a list against it;
+// er_frames_to_models_align does the same with n_models models, a slot each, and one of them per frame.
 //   k_odom_bilateral  raw -> level 0 (13 x 13 bilateral filter, weights from two tables staged in LDS; depth limit)       blockIdx.y = frame
 //   k_odom_pyr        level l -> l + 1 (5 x 5 integer mean of the taps near the centre)                                   blockIdx.y = frame
 //   k_odom_maps       depth level -> records                                                                             blockIdx.y = frame
@@ -365,10 +366,10 @@ void state_from(const double* T, OdomState& s) {
 }
 
 // One run: pairs [p0, p1) of the list, whose frames fit the window.  One stream lease per run.
-// model_rec (nullable): the record maps of a MODEL, one device pointer per level; the list names it as frame `model_frame`.  Its slot is filled by
-// device-to-device copies instead of the preprocessing, and stays resident from run to run like any frame that is needed again.
+// model_rec (nullable): the record maps of the MODELS, [model][level] device pointers; the list names model k as frame `n_frames + k`.  A model's
+// slot is filled by device-to-device copies instead of the preprocessing, and stays resident from run to run like any frame that is needed again.
 int odom_run(er_odom_s* h, const uint16_t* depth, int on_device, int p0, int p1, const int* model_idx, const int* frame_idx, const double* guess,
-             double* T_out, int* status, double* trace, double* sums, const void* const* model_rec = nullptr, int model_frame = -1) {
+             double* T_out, int* status, double* trace, double* sums, const void* const* model_rec = nullptr, int n_frames = 0) {
   const int m = p1 - p0;
   std::vector<Todo> todo;                                    // (host buffers of asynchronous copies: declared before the lease, whose destructor drains the stream)
   std::vector<PairDesc> pairs(m);
@@ -389,9 +390,9 @@ int odom_run(er_odom_s* h, const uint16_t* depth, int on_device, int p0, int p1,
       const int s = slot_of(-1);
       if (s == (int)h->slot_frame.size()) return er::fail("er_odom_align_pairs: internal error, no free slot");
       h->slot_frame[s] = f;
-      if (model_rec && f == model_frame) {
+      if (model_rec && f >= n_frames) {
         for (int l = 0; l < h->P.levels; l++)
-          ER_HIP_TRY(hipMemcpyAsync(h->lo.base + (size_t)s * h->lo.stride + h->lo.off_rec[l], model_rec[l],
+          ER_HIP_TRY(hipMemcpyAsync(h->lo.base + (size_t)s * h->lo.stride + h->lo.off_rec[l], model_rec[(size_t)(f - n_frames) * h->P.levels + l],
                                     (size_t)h->lo.cols[l] * h->lo.rows[l] * 2 * sizeof(float4), hipMemcpyDeviceToDevice, st));
       } else {
         todo.push_back({s, f});
@@ -437,9 +438,8 @@ int odom_run(er_odom_s* h, const uint16_t* depth, int on_device, int p0, int p1,
 
 int odom_align(er_odom_s* h, const char* who, int n_frames, const uint16_t* depth, int on_device, int n_pairs, const int* model_idx,
                const int* frame_idx, const double* guess, double* T_out, int* status, double* trace, double* sums, int window,
-               const void* const* model_rec = nullptr) {
-  const int model_frame = model_rec ? n_frames : -1;       // the model is one more thing that needs a slot: "frame" n_frames of the list
-  const int n_things = n_frames + (model_rec ? 1 : 0);
+               const void* const* model_rec = nullptr, int n_models = 0) {
+  const int n_things = n_frames + (model_rec ? n_models : 0);      // a model is one more thing that needs a slot: model k is "frame" n_frames + k of the list
   if (window == 0) window = default_window(h);
   if (window < 2) return er::fail("%s: window = %d, must be at least 2 (or 0 for the default)", who, window);
   for (int p = 0; p < n_pairs; p++)
@@ -464,13 +464,26 @@ int odom_align(er_odom_s* h, const char* who, int n_frames, const uint16_t* dept
         if (std::find(frames.begin(), frames.end(), f) == frames.end()) frames.push_back(f);
       p1++;
     }
-    if (odom_run(h, depth, on_device, p0, p1, model_idx, frame_idx, guess, T_out, status, trace, sums, model_rec, model_frame)) return 1;
+    if (odom_run(h, depth, on_device, p0, p1, model_idx, frame_idx, guess, T_out, status, trace, sums, model_rec, n_frames)) return 1;
     p0 = p1;
   }
   return 0;
 }
 
 }  // namespace
+
+// The general form behind er_frames_to_models_align, for the fragment builder (er_fragments.hip): any pair list whose model side names models.
+int er::odom_align_models(er_odom_s* h, const char* who, int n_models, const void* const* model_rec_dev, int n_frames, const uint16_t* depth,
+                          int on_device, int n_pairs, const int* model_idx, const int* frame_idx, const double* guess, double* T_out, int* status,
+                          double* trace, double* sums, int window) {
+  for (int k = 0; k < n_models; k++)
+    for (int l = 0; l < h->P.levels; l++)
+      if (!model_rec_dev[(size_t)k * h->P.levels + l]) return er::fail("%s: model %d has no record map for level %d of %d", who, k, l, h->P.levels);
+  if (n_pairs > 0 && (!T_out || !status)) return er::fail("%s: T_out or status is NULL", who);
+  if (window < 0) return er::fail("%s: window = %d, must be at least 2 (or 0 for the default)", who, window);
+  return odom_align(h, who, n_frames, depth, on_device, n_pairs, model_idx, frame_idx, guess, T_out, status, trace, sums, window, model_rec_dev, n_models);
+}
+int er::odom_levels(er_odom_s* h) { return h->P.levels; }
 
 extern "C" {
 
@@ -606,7 +619,25 @@ int er_frame_to_model_align(er_odom_t h, const void* const* model_rec_dev, int n
   if (window < 0) return er::fail("%s: window = %d, must be at least 2 (or 0 for the default)", who, window);
   std::vector<int> a(n_frames, n_frames), b(n_frames);                  // every frame against the model, which the list names as frame n_frames
   for (int i = 0; i < n_frames; i++) b[i] = i;
-  return odom_align(h, who, n_frames, depth, depth_on_device, n_frames, a.data(), b.data(), guess, T_out, status, trace, sums, window, model_rec_dev);
+  return odom_align(h, who, n_frames, depth, depth_on_device, n_frames, a.data(), b.data(), guess, T_out, status, trace, sums, window, model_rec_dev, 1);
+}
+
+int er_frames_to_models_align(er_odom_t h, int n_models, const void* const* model_rec_dev, int n_frames, const uint16_t* depth, int depth_on_device,
+                              const int* model_of_frame, const double* guess, double* T_out, int* status, double* trace, double* sums, int window) {
+  const char* who = "er_frames_to_models_align";
+  if (no_device(who)) return 1;
+  if (!h) return er::fail("%s: NULL handle", who);
+  if (n_frames < 1 || !depth) return er::fail("%s: depth is NULL or n_frames = %d is not positive", who, n_frames);
+  if (n_models < 1 || !model_rec_dev) return er::fail("%s: model_rec_dev is NULL or n_models = %d is not positive", who, n_models);
+  if (!model_of_frame) return er::fail("%s: model_of_frame is NULL", who);
+  std::vector<int> a(n_frames), b(n_frames);                            // frame i against its model, which the list names as frame n_frames + k
+  for (int i = 0; i < n_frames; i++) {
+    if (model_of_frame[i] < 0 || model_of_frame[i] >= n_models) return er::fail("%s: frame %d names model %d of %d", who, i, model_of_frame[i], n_models);
+    a[i] = n_frames + model_of_frame[i];
+    b[i] = i;
+  }
+  return er::odom_align_models(h, who, n_models, model_rec_dev, n_frames, depth, depth_on_device, n_frames, a.data(), b.data(), guess, T_out, status, trace,
+                               sums, window);
 }
 
 int er_odom_linearize(er_odom_t h, const uint16_t* depth2, int on_device, int level, const double* T, double* sums, int* count) {

@@ -10,8 +10,15 @@
 // index advances by the number of steps that provably stay inside the unit's box (er_rc::skip_steps): the trip count is an integer that
 // only grows, and the samples that are left out are unobserved whichever way they are counted, so the output is the plain march's.
 // The kernel only reads the volume: no atomics, no LDS.  Nobody has measured it yet (scripts/raycast_probe.py is there for that).
+//
+// k_raycast_batch: the same body for a LIST of jobs (er_tsdf_raycast_batch) -- job = (volume, image, pose, outputs), one per
+// blockIdx.z, read once from a table in device memory (the index is the workgroup's, so the reads are scalar).  x and y of the grid are
+// sized for the largest image of the list; the workgroups that lie outside a smaller image leave at once.
 #include "er_tsdf_dev.h"
 #include "er_raycast_math.h"
+#include "er_cloud.h"
+
+#include <mutex>
 
 namespace {
 
@@ -71,6 +78,67 @@ __global__ __launch_bounds__(kGroupPx * kGroupPx) void k_raycast(const float2* _
   if (depth) depth[i] = px.depth;
 }
 
+// One job of k_raycast_batch: what k_raycast takes as arguments.
+struct RayJob {
+  const float2* pool;
+  const int* ht_key;
+  const int* ht_slot;
+  float4* rec;
+  uint16_t* depth;
+  int cap_mask, shift, max_units, cols, rows;
+  er_rc::Image I;
+};
+static_assert(sizeof(RayJob) == 136, "five pointers, five ints and the image: the job table is read with scalar loads, keep it small");
+
+__global__ __launch_bounds__(kGroupPx * kGroupPx) void k_raycast_batch(const RayJob* __restrict__ jobs) {
+  const RayJob& J = jobs[blockIdx.z];
+  const int cols = J.cols, rows = J.rows;
+  if ((int)blockIdx.x * kGroupPx >= cols || (int)blockIdx.y * kGroupPx >= rows) return;     // (workgroup-uniform) a smaller image than the list's largest
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int u = blockIdx.x * kGroupPx + (wave & 1) * kTilePx + (lane & 7);
+  const int v = blockIdx.y * kGroupPx + (wave >> 1) * kTilePx + (lane >> 3);
+  if (u >= cols || v >= rows) return;
+  DeviceVol vol{J.pool, J.ht_key, J.ht_slot, J.cap_mask, J.shift, J.max_units, kEmptyKey, -1, 0, 0, 0};
+  const er_rc::Image I = J.I;
+  float4* __restrict__ rec = J.rec;
+  uint16_t* __restrict__ depth = J.depth;
+  er_rc::Pixel px;
+  er_rc::cast_pixel(vol, I, u, v, px);
+  const size_t i = (size_t)v * cols + u;
+  if (rec) {
+    rec[2 * i] = make_float4(px.v[0], px.v[1], px.v[2], 0.0f);
+    rec[2 * i + 1] = make_float4(px.n[0], px.n[1], px.n[2], 0.0f);
+  }
+  if (depth) depth[i] = px.depth;
+}
+
+constexpr int kMaxJobs = 65535;               // jobs sit on blockIdx.z
+
+// The job table of er_tsdf_raycast_batch: a page-locked block and its device twin, grow-only, one pair per process; a call holds the lock
+// from the first entry it writes until its stream is drained.
+struct JobTable {
+  std::mutex lock;
+  int device = -1;
+  size_t cap = 0;
+  RayJob *host = nullptr, *dev = nullptr;
+};
+JobTable g_jobs;
+
+int job_table_reserve(JobTable& t, int device, size_t n) {
+  if (t.device == device && n <= t.cap) return 0;
+  if (t.host) (void)hipHostFree(t.host);
+  if (t.dev) (void)hipFree(t.dev);
+  t.host = t.dev = nullptr;
+  t.cap = 0;
+  t.device = -1;
+  const size_t cap = std::max<size_t>(n, 256);
+  ER_HIP_TRY(hipHostMalloc((void**)&t.host, cap * sizeof(RayJob), hipHostMallocDefault));
+  ER_HIP_TRY(hipMalloc((void**)&t.dev, cap * sizeof(RayJob)));
+  t.cap = cap;
+  t.device = device;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -121,6 +189,75 @@ int er_tsdf_raycast(er_tsdf_t h, int cols, int rows, const float cam4[4], const 
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (tmp) (void)hipFree(tmp);
   if (e != hipSuccess) return er::fail("%s: %s", who, hipGetErrorString(e));
+  return 0;
+}
+
+int er_tsdf_raycast_batch(int n_jobs, const er_tsdf_t* vol, const int* cols, const int* rows, const float* cam4, const double* T,
+                          const er_raycast_params* params, void* const* rec_out_dev, uint16_t* const* depth_out_dev) {
+  const char* who = "er_tsdf_raycast_batch";
+  if (n_jobs < 0) return er::fail("%s: n_jobs = %d is negative", who, n_jobs);
+  if (n_jobs == 0) return 0;
+  if (n_jobs > kMaxJobs) return er::fail("%s: %d jobs, at most %d in one call", who, n_jobs, kMaxJobs);
+  if (!vol || !cols || !rows || !cam4 || !T) return er::fail("%s: NULL argument", who);
+  // every refusal of er_tsdf_raycast, per job, before anything is launched
+  std::vector<int> n_steps((size_t)n_jobs);
+  int max_cols = 0, max_rows = 0;
+  for (int j = 0; j < n_jobs; j++) {
+    if (!vol[j]) return er::fail("%s: job %d: NULL handle", who, j);
+    if (vol[j]->device != vol[0]->device)
+      return er::fail("%s: job %d: its volume is on device %d, job 0's on device %d (one device per call)", who, j, vol[j]->device, vol[0]->device);
+    if (cols[j] <= 0 || rows[j] <= 0 || cols[j] > 16384 || rows[j] > 16384)
+      return er::fail("%s: job %d: an image of %d x %d (1 .. 16384 each way)", who, j, cols[j], rows[j]);
+    er_raycast_params P;
+    er_raycast_params_default(&P);
+    if (params) P = params[j];
+    const int bad = er_rc::count_steps(P.t_min, P.t_max, P.step, &n_steps[(size_t)j]);
+    if (bad == 1) return er::fail("%s: job %d: t_min, t_max and step must be finite and step positive", who, j);
+    if (bad == 2) return er::fail("%s: job %d: more than %d steps between t_min and t_max", who, j, er_rc::kMaxSteps);
+    for (int i = 0; i < 4; i++)
+      if (!std::isfinite(cam4[4 * (size_t)j + i])) return er::fail("%s: job %d: cam4 is not finite", who, j);
+    if (cam4[4 * (size_t)j] == 0.0f || cam4[4 * (size_t)j + 1] == 0.0f) return er::fail("%s: job %d: a focal length of 0", who, j);
+    if (!(rec_out_dev && rec_out_dev[j]) && !(depth_out_dev && depth_out_dev[j])) return er::fail("%s: job %d: both outputs are NULL", who, j);
+    max_cols = std::max(max_cols, cols[j]);
+    max_rows = std::max(max_rows, rows[j]);
+  }
+  const int device = vol[0]->device;
+  ER_HIP_TRY(hipSetDevice(device));
+  // Behind every queued batch of every volume named: check_flags joins the volume's voxel stream and waits for it, so whatever this call
+  // launches afterwards, on any stream, stands behind the volume's last integration.
+  for (int j = 0; j < n_jobs; j++) {
+    bool seen = false;
+    for (int q = 0; q < j && !seen; q++) seen = vol[q] == vol[j];
+    if (!seen && check_flags(vol[j])) return 1;
+  }
+  std::lock_guard<std::mutex> guard(g_jobs.lock);
+  if (job_table_reserve(g_jobs, device, (size_t)n_jobs)) return 1;
+  for (int j = 0; j < n_jobs; j++) {
+    er_raycast_params P;
+    er_raycast_params_default(&P);
+    if (params) P = params[j];
+    er_tsdf_t h = vol[j];
+    RayJob& J = g_jobs.host[j];
+    J.pool = h->pool;
+    J.ht_key = h->ht_key;
+    J.ht_slot = h->ht_slot;
+    J.rec = rec_out_dev ? (float4*)rec_out_dev[j] : nullptr;
+    J.depth = depth_out_dev ? depth_out_dev[j] : nullptr;
+    J.cap_mask = h->ht_cap - 1;
+    J.shift = h->ht_shift;
+    J.max_units = h->max_units;
+    J.cols = cols[j];
+    J.rows = rows[j];
+    er_rc::make_image(cam4 + 4 * (size_t)j, T + 16 * (size_t)j, P.t_min, P.step, n_steps[(size_t)j], J.I);
+  }
+  er::StreamLease lease;                                   // a stream of the call's own; its destructor drains it
+  if (lease.acquire(device)) return 1;
+  hipStream_t st = lease.stream;
+  ER_HIP_TRY(hipMemcpyAsync(g_jobs.dev, g_jobs.host, sizeof(RayJob) * (size_t)n_jobs, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_raycast_batch, dim3((max_cols + kGroupPx - 1) / kGroupPx, (max_rows + kGroupPx - 1) / kGroupPx, n_jobs), dim3(kGroupPx * kGroupPx),
+                     0, st, g_jobs.dev);
+  ER_HIP_TRY(hipGetLastError());
+  ER_HIP_TRY(hipStreamSynchronize(st));
   return 0;
 }
 

@@ -178,6 +178,35 @@ class DepthOdometry:
             out += (sm,)
         return out
 
+    def align_models(self, models, depth, model_of_frame, guess=None, trace=False, sums=False, window=0):
+        """er_frames_to_models_align: frame i of `depth` against models[model_of_frame[i]], each model what align_model takes.  Returns what
+        align_model returns, and for every frame the bits of align_model(models[model_of_frame[i]], frame i)."""
+        keep_d, dp, on_dev, n = self._depth(depth)
+        keep_m, ptrs = [], []
+        for m in models:
+            k, r = self._model_records(m)
+            keep_m.append(k)
+            ptrs += list(r)
+        recs = (C.c_void_p * len(ptrs))(*ptrs)
+        mof = np.ascontiguousarray(model_of_frame, np.int32).reshape(-1)
+        if mof.shape[0] != n:
+            raise ValueError("model_of_frame names %d frames, depth holds %d" % (mof.shape[0], n))
+        g = None if guess is None else np.ascontiguousarray(guess, np.float64).reshape(n, 16)
+        T = np.zeros((n, 4, 4), np.float64)
+        status = np.zeros(n, np.int32)
+        tr = np.zeros((n, self.total_iters, TRACE), np.float64) if trace else None
+        sm = np.zeros((n, 27), np.float64) if sums else None
+        _ffi.check(self._lib.er_frames_to_models_align(self._h, len(models), recs, n, dp, on_dev, _ffi.ptr(mof), None if g is None else _ffi.ptr(g),
+                                                       _ffi.ptr(T), _ffi.ptr(status), None if tr is None else _ffi.ptr(tr),
+                                                       None if sm is None else _ffi.ptr(sm), int(window)), "er_frames_to_models_align")
+        del keep_d, keep_m
+        out = (T, status)
+        if trace:
+            out += (tr,)
+        if sums:
+            out += (sm,)
+        return out
+
     def track_model(self, volume, depth, T0=None):
         """Frame-to-model tracking as a composition of public calls: frame 0 is integrated into `volume` (a TSDFVolume of the same image) at
         T0 (identity); every later frame is aligned against the volume ray-cast at the last pose, from the identity, T_i = T_{i-1} m_T_c,

@@ -312,6 +312,41 @@ class TSDFVolume:
         return {"integrate_ms": ms.value, "launches": ln.value, "frames": fr.value, "unit_visits": uv.value}
 
 
+def raycast_batch(jobs, depth=True):
+    """er_tsdf_raycast_batch: a list of ray-casts in ONE launch.  jobs: dicts (or tuples in this order) of volume (a TSDFVolume), T
+    (world_T_camera), cols, rows, cam = (fx, fy, cx, cy) and optionally params = (t_min, t_max, step); all volumes on one device.  Returns
+    per job (depth uint16 [r, c] or None, vertex map [r, c, 3], normal map [r, c, 3]) as torch tensors on that device, the two maps views
+    of one record tensor [r, c, 2, 4] as TSDFVolume.raycast(device = True) returns them -- and the same bits.  depth = False: no depth image."""
+    import torch
+    lib = _ffi.lib()
+    keys = ("volume", "T", "cols", "rows", "cam", "params")
+    jobs = [j if isinstance(j, dict) else dict(zip(keys, j)) for j in jobs]
+    n = len(jobs)
+    if n == 0:
+        _ffi.check(lib.er_tsdf_raycast_batch(0, None, None, None, None, None, None, None, None), "er_tsdf_raycast_batch")
+        return []
+    dev = torch.device("cuda", jobs[0]["volume"].device)
+    vols = (C.c_void_p * n)(*[j["volume"]._h.value for j in jobs])
+    cols = np.array([int(j["cols"]) for j in jobs], np.int32)
+    rows = np.array([int(j["rows"]) for j in jobs], np.int32)
+    cam = np.ascontiguousarray([np.asarray(j["cam"], np.float32).reshape(-1)[:4] for j in jobs], dtype=np.float32)
+    T = np.ascontiguousarray([np.asarray(j["T"], np.float64).reshape(16) for j in jobs], dtype=np.float64)
+    P = None
+    if any(j.get("params") is not None for j in jobs):
+        d = _ffi.ErRaycastParams()
+        _ffi.check(lib.er_raycast_params_default(C.byref(d)), "er_raycast_params_default")
+        P = (_ffi.ErRaycastParams * n)()
+        for q, j in enumerate(jobs):
+            P[q] = d if j.get("params") is None else _ffi.ErRaycastParams(*[float(np.float32(x)) for x in j["params"]])
+    recs = [torch.empty((max(int(r), 0), max(int(c), 0), 2, 4), dtype=torch.float32, device=dev) for c, r in zip(cols, rows)]
+    deps = [torch.empty((max(int(r), 0), max(int(c), 0)), dtype=torch.uint16, device=dev) if depth else None for c, r in zip(cols, rows)]
+    torch.cuda.current_stream(dev).synchronize()                 # (the tensors' memory may have work of torch's stream pending on it)
+    rp = (C.c_void_p * n)(*[t.data_ptr() for t in recs])
+    dp = (C.c_void_p * n)(*[t.data_ptr() for t in deps]) if depth else None
+    _ffi.check(lib.er_tsdf_raycast_batch(n, vols, _ffi.ptr(cols), _ffi.ptr(rows), _ffi.ptr(cam), _ffi.ptr(T), P, rp, dp), "er_tsdf_raycast_batch")
+    return [(deps[q], recs[q][:, :, 0, :3], recs[q][:, :, 1, :3]) for q in range(n)]
+
+
 class IntegrateApp:
     """CIntegrateApp (IntegrateApp.h:33-94) without the OpenNI grabber: frames are fed by the caller.
 

@@ -186,6 +186,17 @@ int er_raycast_params_default(er_raycast_params* p);
 int er_tsdf_raycast(er_tsdf_t h, int cols, int rows, const float cam4[4], const double T[16], const er_raycast_params* params,
                     void* rec_out /* cols*rows*2 float4, nullable */, uint16_t* depth_out /* nullable */, int out_on_device);
 
+/* A LIST of ray-casts in one launch: job j casts volume vol[j] into a cols[j] x rows[j] image with cam4[4 j ..] from the pose
+ * T[16 j ..] under params[j] (params NULL: the defaults for every job), exactly as er_tsdf_raycast does -- the same bits, whatever else is in
+ * the list.  The same volume may appear in any number of jobs; all volumes must live on ONE device.  Outputs are DEVICE memory only:
+ * rec_out_dev[j] (nullable) and depth_out_dev[j] (nullable; the whole array may be NULL), not both NULL.  The launch goes on a stream of the
+ * call's own, behind every queued batch of every volume named, and the call returns when all outputs are complete.  Everything er_tsdf_raycast
+ * refuses is refused for the whole list before anything is launched, the message naming the job ("job 3: ..."); also more than 65535 jobs and
+ * volumes of two devices.  n_jobs == 0 returns 0 and touches nothing. */
+int er_tsdf_raycast_batch(int n_jobs, const er_tsdf_t* vol, const int* cols, const int* rows, const float* cam4 /* [n_jobs][4] */,
+                          const double* T /* [n_jobs][16] */, const er_raycast_params* params /* [n_jobs], nullable */,
+                          void* const* rec_out_dev, uint16_t* const* depth_out_dev);
+
 /* Multi-GPU frame split: for the given key list write sum-ready planes into dev_buf
  * (n_keys * 2 * 64^3 floats: [key][0] = sdf*weight, [key][1] = weight; zeros for keys absent here), and
  * after an external all-reduce(sum) read them back as weight = W, sdf = SW / W. */
@@ -542,6 +553,13 @@ int er_odom_track(er_odom_t h, int n_frames, const uint16_t* depth, int depth_on
 int er_frame_to_model_align(er_odom_t h, const void* const* model_rec_dev /* [levels], device */, int n_frames, const uint16_t* depth,
                             int depth_on_device, const double* guess, double* T_out, int* status, double* trace, double* sums, int window);
 
+/* The same against n_models models, one per frame: frame i is aligned against model model_of_frame[i]; model k's record maps are
+ * model_rec_dev[k * levels + l].  er_frame_to_model_align is the n_models == 1 case, bit for bit, and a frame's result is what that call gives
+ * for the frame and its model alone -- in any list, in any order, for any window. */
+int er_frames_to_models_align(er_odom_t h, int n_models, const void* const* model_rec_dev /* [n_models][levels], device */, int n_frames,
+                              const uint16_t* depth, int depth_on_device, const int* model_of_frame /* [n_frames] */, const double* guess,
+                              double* T_out, int* status, double* trace, double* sums, int window);
+
 /* Restates odometry_restatement.Odometry.linearize: ONE evaluation of the 27 sums and the count at the pose T (m_T_c) on `level`, for
  * depth2 = {model frame, current frame}. */
 int er_odom_linearize(er_odom_t h, const uint16_t* depth2, int on_device, int level, const double* T, double* sums, int* count);
@@ -554,6 +572,39 @@ int er_odom_read_maps(er_odom_t h, const uint16_t* depth1, int on_device, int le
  * 73 entries; depth_w[|delta| in mm], *n_depth_w entries (at most ER_ODOM_DEPTH_W), zero beyond.  Works without a device. */
 #define ER_ODOM_DEPTH_W 512
 int er_odom_tables(float* space, float* depth_w, int* n_depth_w);
+
+/* ------------------------------------------------ fragments from a depth stream ---- */
+/* The step that comes before everything else in the pipeline (pcl_kinfu_largeScale in the author's PCL fork; not in the reference tree):
+ * a depth stream is cut into fragments of `interval` frames, every fragment is tracked frame-to-model against a TSDF volume of its own and
+ * leaves its frame poses and the oriented surface points of that volume (cloud_bin_<k>.pcd).  `lanes` fragments run in lockstep: one ray-cast
+ * launch, one alignment run and one integration per lane and step.
+ * THE CONTRACT: fragment k's poses and statuses are the bits of DepthOdometry.track_model (odometry.py) on its frames with its T0 on a fresh
+ * volume, its points and normals the bits of TSDFVolume.SaveFragment of that volume -- for any lanes, host or device depth, any run. */
+typedef struct er_frag_s* er_frag_t;
+typedef struct er_frag_params {
+  int interval;               /* frames per fragment (50) */
+  int lanes;                  /* fragments in flight, 1 .. 64 (8); NOT part of any result */
+  int max_units;              /* unit pool of each lane's volume (512) */
+  float length;               /* edge of the fragment cube, metres (3.0) */
+  er_raycast_params raycast;  /* the model's ray-cast (er_raycast_params_default) */
+} er_frag_params;
+int er_frag_params_default(er_frag_params* p);
+/* cam6 as er_tsdf_create (NULL = its defaults); odom_params / frag_params NULL = the defaults.  Every lane owns an er_tsdf_t of max_units units:
+ * at 640 x 480 roughly 0.85 GB of batch staging plus max_units x 2 MiB.  A lane that cannot be allocated is a refusal that names the bytes. */
+int er_frag_create(int cols, int rows, const float cam6[6], const er_odom_params* odom_params, const er_frag_params* frag_params, int device,
+                   er_frag_t* out);
+int er_frag_destroy(er_frag_t h);
+int er_frag_lane_bytes(er_frag_t h, size_t* bytes);   /* device memory the first lane took at create (measured) */
+/* Fragment k = frames [k interval, min((k + 1) interval, n_frames)); a short last fragment is a fragment.  depth: n_frames * rows * cols uint16
+ * millimetres, host memory (uploaded once) or complete device memory.  T0: the pose of every fragment's first frame -- n_T0 == 1: one for all,
+ * n_T0 == the fragment count: one each, NULL: the kinfu convention, (length / 2, length / 2, -0.3) looking along +z.  Frame i of a fragment:
+ * the volume is ray-cast at W_{i-1}, the frame aligned against it from the identity, W_i = W_{i-1} m_T_c, the frame integrated at W_i; a lost
+ * frame keeps W_{i-1} and is not integrated.  W_out[n_frames][16], status[n_frames] (ER_ODOM_OK / ER_ODOM_LOST; a fragment's first frame is
+ * never lost).  The fragments' points stay with the handle until the next call: er_frag_count, er_frag_read. */
+int er_frag_build(er_frag_t h, int n_frames, const uint16_t* depth, int depth_on_device, const double* T0, int n_T0, double* W_out, int* status);
+int er_frag_count(er_frag_t h, int* n_fragments);
+/* xyz_out / normals_out: [count][3] floats, the points inside 0 <= x, y, z < length, NaN-normal rows kept.  Both NULL: only the count. */
+int er_frag_read(er_frag_t h, int fragment, float* xyz_out, float* normals_out, long capacity, long* count);
 
 /* ------------------------------------------------ pose graph optimisation ---- */
 /* GraphOptimizer: the candidate loop closures of GlobalRegistration in, pruned closures and fragment poses out.  The model is the
