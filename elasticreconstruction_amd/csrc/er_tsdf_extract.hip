@@ -1,8 +1,12 @@
 // er_tsdf_extract.hip -- what leaves the resident TSDF volume of path A (er_tsdf.hip): SaveWorld's voxel list, the zero crossings with and without
-// normals, the oriented cloud handed to path B on the device, and the marching-cubes mesh.  Every kernel here makes two passes over the slabs
-// (64 per unit) of the units in ascending key order -- count, then write at the slab's offset -- so the lists are reproducible element for element.
+// normals, the oriented cloud handed to path B on the device, and the marching-cubes mesh, as a triangle soup and indexed -- and SaveWorld's
+// inverse, the one way back in.  Every extraction kernel makes two passes over the slabs (64 per unit) of the units in ascending key order --
+// count, then write at the slab's offset -- so the lists are reproducible element for element.
 #include "er_tsdf_dev.h"
 #include "er_mc_table.h"
+
+#include <climits>
+#include <cmath>
 
 namespace {
 
@@ -288,6 +292,270 @@ __global__ __launch_bounds__(64) void k_mesh(const float2* __restrict__ pool, co
   if (!pass && lane == 0) slab_count[blockIdx.x] = total;
 }
 
+// The INDEXED mesh (er_tsdf_extract_mesh_indexed): k_mesh's triangles as three int32 indices into a list of unique vertices.
+// A vertex is a lattice EDGE -- its lower voxel L and an axis -- that at least one emitted triangle uses, never a position: two edges that
+// meet in a voxel whose sdf is exactly 0 give the same coordinates and stay two vertices.  Vertex order: the unit of L by ascending key, L in
+// i, j, k order, axes x, y, z (k_surface's order; not its set).  No sort and no float atomic; four passes over the slabs:
+//   k_mesh_index, pass 0   k_mesh's cell loop; every edge a triangle uses sets one bit of a per-unit bitmap, 3 axes x 64^3 bits, at the edge's
+//                          OWNER voxel L (which may lie in the +x / +y / +z neighbour unit: it exists, the cell is valid).  Row (unit, i, j) of
+//                          the bitmap = three 64-bit masks over k.  The wave gathers the bits of a row of cells with one ballot per cell edge
+//                          and lane 0 ORs the row masks in with 32-bit atomicOr: OR commutes, so the bitmap does not depend on who runs when.
+//                          Counts the slab's triangles as k_mesh's pass 0 does.
+//   k_mesh_rows            one wave per slab, lane = j: the popcount of the row's three masks and its exclusive prefix inside the slab.
+//   k_mesh_verts           one wave per slab, lane = k: the vertex of bit (row, axis, k) goes to
+//                              slab offset + row prefix + popc(the three masks below k) + (set bits of the lower axes at k)
+//                          with k_mesh's own position expression, from the two sdf values the lane reads itself.
+//   k_mesh_index, pass 1   the cell loop again, writing at k_mesh's slab offsets: a triangle corner's index is the same sum, read from the
+//                          owner's row.  A row of cells touches four rows of the bitmap (i, i + 1) x (j, j + 1), the same for all 64 lanes --
+//                          wave-uniform loads, once per row of cells -- and lane 63 alone four more in the +z unit.
+// The bitmap is 96 KiB per unit, the row prefixes 16 KiB.
+
+// element idx of a table of eight that lives in registers: a select chain over the VALUES (a run-time index, or a chain over references to
+// the array's elements, which the compiler folds back into one, sends the table through scratch)
+__device__ __forceinline__ int pick8v(int t0, int t1, int t2, int t3, int t4, int t5, int t6, int t7, int idx) {
+  int r = t0;
+  r = idx == 1 ? t1 : r;
+  r = idx == 2 ? t2 : r;
+  r = idx == 3 ? t3 : r;
+  r = idx == 4 ? t4 : r;
+  r = idx == 5 ? t5 : r;
+  r = idx == 6 ? t6 : r;
+  r = idx == 7 ? t7 : r;
+  return r;
+}
+#define ER_PICK8(t, idx) pick8v(t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], idx)
+
+// ORs a row mask into bitmap row (unit of rank r, i, j), axis: two 32-bit words (little endian: word 0 = k 0 .. 31)
+__device__ __forceinline__ void mark_row(unsigned long long* __restrict__ bm, int r, int i, int j, int axis, unsigned long long m) {
+  if (r < 0) return;                           // (no such unit: cannot be the owner of an edge of a valid cell)
+  unsigned* w = reinterpret_cast<unsigned*>(bm + ((size_t)r * 4096 + (size_t)i * 64 + j) * 3 + axis);
+  const unsigned lo = (unsigned)m, hi = (unsigned)(m >> 32);
+  if (lo) atomicOr(w, lo);
+  if (hi) atomicOr(w + 1, hi);
+}
+
+__global__ __launch_bounds__(64) void k_mesh_index(const float2* __restrict__ pool, const int* __restrict__ slots, const int* __restrict__ keys,
+                                                   const int* __restrict__ ht_key, const int* __restrict__ ht_slot, int cap_mask, int shift,
+                                                   const unsigned char* __restrict__ table, const int* __restrict__ slot_rank,
+                                                   unsigned long long* __restrict__ bm, const int* __restrict__ row_off,
+                                                   const long* __restrict__ vslab_off, long* __restrict__ slab_count,
+                                                   const long* __restrict__ slab_offset, int* __restrict__ out, int pass) {
+  __shared__ unsigned char s_tab[256 * 16];
+  for (int t = threadIdx.x; t < 256 * 16 / 4; t += 64) reinterpret_cast<unsigned*>(s_tab)[t] = reinterpret_cast<const unsigned*>(table)[t];
+  __syncthreads();
+  const int rank = blockIdx.x >> 6;          // unit in ascending key order
+  const int i = blockIdx.x & 63;
+  const int lane = threadIdx.x;              // = k
+  const int key = keys[rank];
+  const int xi = key >> 18, yi = (key >> 9) & 511, zi = key & 511;
+  // the (up to) eight units a slab of cells can touch, as in k_mesh: pool slots and ranks, [dx << 2 | dy << 1 | dz]; -1 = none (rank: or dropped)
+  int us[8], rk[8];
+#pragma unroll
+  for (int dx = 0; dx < 2; dx++)
+#pragma unroll
+    for (int dy = 0; dy < 2; dy++)
+#pragma unroll
+      for (int dz = 0; dz < 2; dz++) {
+        const bool need = (dx == 0 || i == 63);
+        const bool ok = xi + dx < 512 && yi + dy < 512 && zi + dz < 512;
+        const int s = (dx | dy | dz) == 0 ? slots[rank]
+                      : (need && ok ? ht_lookup_slot(ht_key, ht_slot, cap_mask, shift, key + dx * 512 * 512 + dy * 512 + dz) : -1);
+        us[dx << 2 | dy << 1 | dz] = s;
+        rk[dx << 2 | dy << 1 | dz] = s >= 0 ? slot_rank[s] : -1;
+      }
+  const int ia[2] = {i, i == 63 ? 0 : i + 1}, ux[2] = {0, i == 63 ? 1 : 0};      // slab index and unit offset of the two i layers (constant indices only)
+  const float2 none = make_float2(0.0f, 0.0f);
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  long base = pass ? slab_offset[blockIdx.x] : 0;
+  long total = 0;
+  for (int j = 0; j < 64; j++) {
+    // the eight corners of this lane's cell: f[a][b][c] = voxel (i + a, j + b, k + c)
+    float2 f[2][2][2];
+#pragma unroll
+    for (int a = 0; a < 2; a++)
+#pragma unroll
+      for (int b = 0; b < 2; b++) {
+        const int jb = (j + b) & 63, uy = (j + b) >> 6;
+        const int s0 = ER_PICK8(us, ux[a] << 2 | uy << 1), s1 = ER_PICK8(us, ux[a] << 2 | uy << 1 | 1);
+        const size_t ro = (size_t)ia[a] * 4096 + (size_t)jb * 64;
+        const float2 v = s0 >= 0 ? pool[(size_t)s0 * kUnitVox + ro + lane] : none;
+        f[a][b][0] = v;
+        float2 w;
+        w.x = __shfl_down(v.x, 1);
+        w.y = __shfl_down(v.y, 1);
+        if (lane == 63) w = s1 >= 0 ? pool[(size_t)s1 * kUnitVox + ro] : none;
+        f[a][b][1] = w;
+      }
+    bool valid = true;
+    int cs = 0;
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+      const float2 v = f[c & 1][(c >> 1) & 1][c >> 2];
+      valid = valid && v.y != 0.0f;
+      cs |= (v.x < 0.0f ? 1 : 0) << c;
+    }
+    const unsigned char* __restrict__ row = s_tab + cs * 16;
+    int nt = 0;
+    if (valid)
+      while (nt < 5 && row[3 * nt] != 255) nt++;
+    // wave-level exclusive prefix of the triangle counts (k order)
+    int incl = nt;
+    for (int sft = 1; sft < 64; sft <<= 1) {
+      const int t = __shfl_up(incl, sft);
+      if (lane >= sft) incl += t;
+    }
+    const int wave_total = __shfl(incl, 63);
+    total += wave_total;
+    if (wave_total == 0) continue;             // (wave-uniform)
+    if (!pass) {
+      // the cell edges this lane's triangles use: bit e = edge id e of the table (axis = e >> 2, u = e & 1, v = (e >> 1) & 1)
+      unsigned used = 0;
+      for (int t = 0; t < 3 * nt; t++) used |= 1u << row[t];
+#pragma unroll
+      for (int e = 0; e < 12; e++) {
+        const unsigned long long m = __ballot((used >> e) & 1u);
+        if (m == 0 || lane != 0) continue;
+        const int axis = e >> 2, u = e & 1, v = (e >> 1) & 1;
+        const int a0 = axis == 0 ? 0 : u, b0 = axis == 1 ? 0 : (axis == 0 ? u : v), c0 = axis == 2 ? 0 : v;
+        const int jb = (j + b0) & 63, uy = (j + b0) >> 6;
+        // owner voxel (i + a0, j + b0, k + c0): bit k + c0 of its row; k + c0 == 64 is voxel 0 of the row in the +z unit
+        mark_row(bm, ER_PICK8(rk, ux[a0] << 2 | uy << 1), ia[a0], jb, axis, c0 ? m << 1 : m);
+        if (c0 && (m >> 63)) mark_row(bm, ER_PICK8(rk, ux[a0] << 2 | uy << 1 | 1), ia[a0], jb, axis, 1ull);
+      }
+      continue;
+    }
+    // pass 1.  Per corner cl = a | b << 1 | c << 2 of the cell, for the edges that START there: P = index of the first vertex of that
+    // voxel, B = which of its x (bit 0) and y (bit 1) edges are vertices -- the index of (voxel, axis) is P + the set bits of the lower axes.
+    int P[8], B[8];
+#pragma unroll
+    for (int a = 0; a < 2; a++)
+#pragma unroll
+      for (int b = 0; b < 2; b++) {
+        const int jb = (j + b) & 63, uy = (j + b) >> 6;
+        const int r0 = ER_PICK8(rk, ux[a] << 2 | uy << 1), r1 = ER_PICK8(rk, ux[a] << 2 | uy << 1 | 1);
+        unsigned long long mx = 0, my = 0, mz = 0;
+        int rb = 0;
+        if (r0 >= 0) {                         // (wave-uniform: one fetch of the row serves all 64 lanes)
+          const size_t r = (size_t)r0 * 4096 + (size_t)ia[a] * 64 + jb;
+          mx = bm[r * 3];
+          my = bm[r * 3 + 1];
+          mz = bm[r * 3 + 2];
+          rb = (int)vslab_off[r0 * 64 + ia[a]] + row_off[r];
+        }
+        const int c = a | b << 1;
+        P[c] = rb + __popcll(mx & lt) + __popcll(my & lt) + __popcll(mz & lt);
+        B[c] = (int)((mx >> lane) & 1ull) | (int)((my >> lane) & 1ull) << 1;
+        // k + 1: the same row one bit up; for lane 63 voxel 0 of the row in the +z unit
+        const int k1 = (lane + 1) & 63;
+        const unsigned long long lt1 = (lt << 1) | 1ull;
+        int p1 = rb + __popcll(mx & lt1) + __popcll(my & lt1) + __popcll(mz & lt1);
+        int q1 = (int)((mx >> k1) & 1ull) | (int)((my >> k1) & 1ull) << 1;
+        if (lane == 63) {
+          p1 = q1 = 0;
+          if (r1 >= 0) {
+            const size_t r = (size_t)r1 * 4096 + (size_t)ia[a] * 64 + jb;
+            p1 = (int)vslab_off[r1 * 64 + ia[a]] + row_off[r];
+            q1 = (int)(bm[r * 3] & 1ull) | (int)(bm[r * 3 + 1] & 1ull) << 1;
+          }
+        }
+        P[c | 4] = p1;
+        B[c | 4] = q1;
+      }
+    if (nt > 0) {
+      int* __restrict__ o = out + (size_t)(base + (total - wave_total) + (incl - nt)) * 3;
+      for (int t = 0; t < 3 * nt; t++) {
+        const int e = row[t];
+        const int axis = e >> 2, u = e & 1, v = (e >> 1) & 1;
+        const int a0 = axis == 0 ? 0 : u, b0 = axis == 1 ? 0 : (axis == 0 ? u : v), c0 = axis == 2 ? 0 : v;
+        const int cl = a0 | b0 << 1 | c0 << 2;
+        const int bits = ER_PICK8(B, cl);
+        o[t] = ER_PICK8(P, cl) + (axis > 0 ? bits & 1 : 0) + (axis > 1 ? bits >> 1 : 0);
+      }
+    }
+  }
+  if (!pass && lane == 0) slab_count[blockIdx.x] = total;
+}
+
+#undef ER_PICK8
+
+// One wave per slab, lane = j: vertices of row (unit, i, j) and their exclusive prefix inside the slab (at most 64 * 192: an int).
+__global__ __launch_bounds__(64) void k_mesh_rows(const unsigned long long* __restrict__ bm, int* __restrict__ row_off, long* __restrict__ vslab_count) {
+  const int lane = threadIdx.x;
+  const size_t r = (size_t)blockIdx.x * 64 + lane;
+  const int c = __popcll(bm[r * 3]) + __popcll(bm[r * 3 + 1]) + __popcll(bm[r * 3 + 2]);
+  int incl = c;
+  for (int sft = 1; sft < 64; sft <<= 1) {
+    const int t = __shfl_up(incl, sft);
+    if (lane >= sft) incl += t;
+  }
+  row_off[r] = incl - c;
+  if (lane == 63) vslab_count[blockIdx.x] = incl;
+}
+
+// One wave per slab, lane = k: the vertices of the slab's marked edges, float4 = x y z axis like k_surface's points, the position by k_mesh's
+// expression pos(L) + (F_L / (F_L - F_H)) * voxel size.  The upper voxel H exists wherever a bit is set (the cell that set it was valid).
+__global__ __launch_bounds__(64) void k_mesh_verts(const float2* __restrict__ pool, const int* __restrict__ slots, const int* __restrict__ keys,
+                                                   const int* __restrict__ ht_key, const int* __restrict__ ht_slot, int cap_mask, int shift,
+                                                   const unsigned long long* __restrict__ bm, const int* __restrict__ row_off,
+                                                   const long* __restrict__ vslab_off, float4* __restrict__ out) {
+  const int rank = blockIdx.x >> 6;          // unit in ascending key order
+  const int i = blockIdx.x & 63;
+  const int lane = threadIdx.x;              // = k
+  const int key = keys[rank];
+  const int xi = key >> 18, yi = (key >> 9) & 511, zi = key & 511;
+  const float2* unit = pool + (size_t)slots[rank] * kUnitVox;
+  const float2* slab = unit + (size_t)i * 4096;
+  const int sx = (i == 63 && xi < 511) ? ht_lookup_slot(ht_key, ht_slot, cap_mask, shift, key + 512 * 512) : -1;
+  const int sy = yi < 511 ? ht_lookup_slot(ht_key, ht_slot, cap_mask, shift, key + 512) : -1;
+  const int sz = zi < 511 ? ht_lookup_slot(ht_key, ht_slot, cap_mask, shift, key + 1) : -1;
+  const float2 none = make_float2(0.0f, 0.0f);
+  const float2* slab_x = i < 63 ? slab + 4096 : (sx >= 0 ? pool + (size_t)sx * kUnitVox : nullptr);
+  const float2* unit_y = sy >= 0 ? pool + (size_t)sy * kUnitVox + (size_t)i * 4096 : nullptr;
+  const float2* unit_z = sz >= 0 ? pool + (size_t)sz * kUnitVox + (size_t)i * 4096 : nullptr;
+  const float ulf = (float)kUnitLength;
+  const float gx = (float)((double)(i + (xi - 256) * 64) * kUnitLength);
+  const float gz = (float)((double)(lane + (zi - 256) * 64) * kUnitLength);
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  const long base = vslab_off[blockIdx.x];
+  for (int j = 0; j < 64; j++) {
+    const size_t r = (size_t)blockIdx.x * 64 + j;
+    const unsigned long long mx = bm[r * 3], my = bm[r * 3 + 1], mz = bm[r * 3 + 2];
+    if ((mx | my | mz) == 0) continue;         // (wave-uniform)
+    const float2 v = slab[j * 64 + lane];
+    float nz = __shfl_down(v.x, 1);
+    if (lane == 63) nz = unit_z ? unit_z[j * 64].x : 0.0f;
+    const bool cx = (mx >> lane) & 1ull, cy = (my >> lane) & 1ull, cz = (mz >> lane) & 1ull;
+    long o = base + row_off[r] + __popcll(mx & lt) + __popcll(my & lt) + __popcll(mz & lt);
+    const float gy = (float)((double)(j + (yi - 256) * 64) * kUnitLength);
+    if (cx) {
+      const float2 nx = slab_x ? slab_x[j * 64 + lane] : none;
+      out[o++] = make_float4(gx + (v.x / (v.x - nx.x)) * ulf, gy, gz, 0.0f);
+    }
+    if (cy) {
+      const float2 ny = j < 63 ? slab[(j + 1) * 64 + lane] : (unit_y ? unit_y[lane] : none);
+      out[o++] = make_float4(gx, gy + (v.x / (v.x - ny.x)) * ulf, gz, 1.0f);
+    }
+    if (cz) out[o++] = make_float4(gx, gy, gz + (v.x / (v.x - nz)) * ulf, 2.0f);
+  }
+}
+
+// SaveWorld's inverse (er_tsdf_import_world): one thread per row x y z intensity of er_tsdf_extract_world's layout -- the host has checked that
+// the coordinates are integers on the lattice and has created the row's unit -- stores (intensity, 1) in its voxel, one 8-byte vector store.
+// The units were (+0, 0) everywhere, so afterwards the weights sum to the number of DISTINCT voxels listed: to the number of rows iff no
+// voxel is listed twice.  (Adding 1 to the weight instead would not tell: that sum is the number of rows whatever they name.)
+__global__ __launch_bounds__(256) void k_import_world(float2* __restrict__ pool, const int* __restrict__ ht_key, const int* __restrict__ ht_slot,
+                                                      int cap_mask, int shift, const float4* __restrict__ rows, long n) {
+  const long r = (long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= n) return;
+  const float4 p = rows[r];
+  const int gx = (int)p.x + 256 * 64, gy = (int)p.y + 256 * 64, gz = (int)p.z + 256 * 64;
+  if ((unsigned)gx >= 512u * 64u || (unsigned)gy >= 512u * 64u || (unsigned)gz >= 512u * 64u) return;   // (refused by the host)
+  const int slot = ht_lookup_slot(ht_key, ht_slot, cap_mask, shift, (gx >> 6) << 18 | (gy >> 6) << 9 | (gz >> 6));
+  if (slot < 0) return;                                                                                  // (the pool is exhausted: refused by the host)
+  float2* v = pool + (size_t)slot * kUnitVox + (size_t)(gx & 63) * 4096 + (size_t)(gy & 63) * 64 + (size_t)(gz & 63);
+  *v = make_float2(p.w, 1.0f);
+}
+
 // One HIP call of an entry point: a failure is reported under the entry point's name and ends the function.
 #define ER_W(who, expr)                                                                         \
   do {                                                                                          \
@@ -536,6 +804,169 @@ int er_tsdf_extract_mesh(er_tsdf_t h, float* tri_host, long capacity_triangles, 
     ER_W(who, hipMemcpyAsync(tri_host, d_out, (size_t)total * 9 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     ER_W(who, hipStreamSynchronize(h->stream));
   }
+  return 0;
+}
+
+int er_tsdf_extract_mesh_indexed(er_tsdf_t h, float* verts_host, float* normals_host, long capacity_vertices, int* tri_host,
+                                 long capacity_triangles, long* n_vertices, long* n_triangles) {
+  const char* who = "er_tsdf_extract_mesh_indexed";
+  if (!h || !n_vertices || !n_triangles) return er::fail("er_tsdf_extract_mesh_indexed: NULL argument");
+  ER_HIP_TRY(hipSetDevice(h->device));
+  std::vector<int> keys, slots;
+  if (sorted_units(h, keys, slots)) return 1;
+  const int n = (int)keys.size();
+  *n_vertices = *n_triangles = 0;
+  if (n == 0) return 0;
+  const int nslab = n * 64;
+  const size_t nrow = (size_t)nslab * 64;
+  SlabPass t;
+  unsigned char* d_tab = nullptr;
+  unsigned long long* d_bm = nullptr;     // [row][axis]: the edge bitmap
+  int *d_rank = nullptr, *d_rowoff = nullptr, *d_tri = nullptr;
+  long *d_vcnt = nullptr, *d_voff = nullptr;
+  float4 *d_verts = nullptr, *d_nrm = nullptr;
+  std::vector<int> rank((size_t)h->max_units, -1);           // pool slot -> position in the key order; -1: a dropped unit's slot
+  for (int r = 0; r < n; r++) rank[(size_t)slots[(size_t)r]] = r;
+  long ntri = 0, nv = 0;
+  auto launch = [&](int* out, int pass) {
+    hipLaunchKernelGGL(k_mesh_index, dim3(nslab), dim3(64), 0, h->stream, h->pool, t.d_slots, t.d_keys, h->ht_key, h->ht_slot, h->ht_cap - 1, h->ht_shift,
+                       d_tab, d_rank, d_bm, d_rowoff, d_voff, t.d_cnt, t.d_off, out, pass);
+    ER_W(who, hipGetLastError());
+    return 0;
+  };
+  if (t.alloc(who, n)) return 1;
+  ER_W_OWNED(who, t, &d_tab, 256 * 16);
+  ER_W_OWNED(who, t, &d_bm, nrow * 3 * sizeof(unsigned long long));
+  ER_W_OWNED(who, t, &d_rank, rank.size() * sizeof(int));
+  ER_W_OWNED(who, t, &d_rowoff, nrow * sizeof(int));
+  ER_W_OWNED(who, t, &d_vcnt, (size_t)nslab * sizeof(long));
+  ER_W_OWNED(who, t, &d_voff, (size_t)nslab * sizeof(long));
+  auto count_launch = [&] {
+    ER_W(who, hipMemcpyAsync(d_tab, er::mc_table().tri, 256 * 16, hipMemcpyHostToDevice, h->stream));
+    ER_W(who, hipMemcpyAsync(d_rank, rank.data(), rank.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    ER_W(who, hipMemsetAsync(d_bm, 0, nrow * 3 * sizeof(unsigned long long), h->stream));
+    if (launch(nullptr, 0)) return 1;                        // marks the bitmap, counts the triangles
+    hipLaunchKernelGGL(k_mesh_rows, dim3(nslab), dim3(64), 0, h->stream, d_bm, d_rowoff, d_vcnt);
+    ER_W(who, hipGetLastError());
+    return 0;
+  };
+  if (t.count(h, who, keys, slots, count_launch, &ntri)) return 1;
+  std::vector<long> vcnt((size_t)nslab);
+  ER_W(who, hipMemcpyAsync(vcnt.data(), d_vcnt, (size_t)nslab * sizeof(long), hipMemcpyDeviceToHost, h->stream));
+  ER_W(who, hipStreamSynchronize(h->stream));
+  for (int s = 0; s < nslab; s++) {
+    const long c = vcnt[(size_t)s];
+    vcnt[(size_t)s] = nv;                                    // (now the slab's offset)
+    nv += c;
+  }
+  *n_vertices = nv;
+  *n_triangles = ntri;
+  if (nv > (long)INT_MAX) return er::fail("er_tsdf_extract_mesh_indexed: %ld vertices; the limit is 2^31 - 1 (int32 indices)", nv);
+  const bool want_v = verts_host || normals_host;
+  if (want_v && capacity_vertices < nv) return er::fail("er_tsdf_extract_mesh_indexed: capacity %ld < %ld vertices", capacity_vertices, nv);
+  if (tri_host && capacity_triangles < ntri) return er::fail("er_tsdf_extract_mesh_indexed: capacity %ld < %ld triangles", capacity_triangles, ntri);
+  if (nv == 0 || (!want_v && !tri_host)) return 0;           // (nothing has been written to the host)
+  ER_W(who, hipMemcpyAsync(d_voff, vcnt.data(), (size_t)nslab * sizeof(long), hipMemcpyHostToDevice, h->stream));
+  if (want_v) {
+    ER_W_OWNED(who, t, &d_verts, (size_t)nv * sizeof(float4));
+    hipLaunchKernelGGL(k_mesh_verts, dim3(nslab), dim3(64), 0, h->stream, h->pool, t.d_slots, t.d_keys, h->ht_key, h->ht_slot, h->ht_cap - 1, h->ht_shift,
+                       d_bm, d_rowoff, d_voff, d_verts);
+    ER_W(who, hipGetLastError());
+    if (verts_host) ER_W(who, hipMemcpyAsync(verts_host, d_verts, (size_t)nv * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
+    if (normals_host) {
+      ER_W_OWNED(who, t, &d_nrm, (size_t)nv * sizeof(float4));
+      hipLaunchKernelGGL(k_surface_normals, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, h->stream, h->pool, h->ht_key, h->ht_slot, h->ht_cap - 1,
+                         h->ht_shift, d_verts, nv, d_nrm);
+      ER_W(who, hipGetLastError());
+      ER_W(who, hipMemcpyAsync(normals_host, d_nrm, (size_t)nv * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
+    }
+  }
+  if (tri_host) {
+    ER_W_OWNED(who, t, &d_tri, (size_t)ntri * 3 * sizeof(int));
+    if (t.upload_offsets(h, who) || launch(d_tri, 1)) return 1;
+    ER_W(who, hipMemcpyAsync(tri_host, d_tri, (size_t)ntri * 3 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  }
+  ER_W(who, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int er_tsdf_import_world(er_tsdf_t h, const float* xyzi_host, long n, int* n_units) {
+  const char* who = "er_tsdf_import_world";
+  if (!h || (n > 0 && !xyzi_host)) return er::fail("er_tsdf_import_world: NULL argument");
+  if (n_units) *n_units = 0;
+  if (n < 0) return er::fail("er_tsdf_import_world: n = %ld", n);
+  ER_HIP_TRY(hipSetDevice(h->device));
+  if (check_flags(h)) return 1;
+  int held = 0;
+  ER_W(who, hipMemcpy(&held, h->counters + C_NUNITS, sizeof(int), hipMemcpyDeviceToHost));
+  if (held != 0) {
+    (void)er_tsdf_reset(h);
+    return er::fail("er_tsdf_import_world: the volume already holds %d units (er_tsdf_reset it first); it is empty now", held);
+  }
+  // the rows, in order: the first one that cannot be a voxel is named
+  std::vector<int> ukeys;
+  int last = -1;
+  for (long r = 0; r < n; r++) {
+    const float* p = xyzi_host + 4 * r;
+    int g[3];
+    for (int a = 0; a < 3; a++) {
+      const float c = p[a];
+      if (!(c >= -16384.0f && c <= 16383.0f) || c != std::floor(c))
+        return er::fail("er_tsdf_import_world: row %ld: %c = %.9g is not a voxel index of the 512-unit lattice (an integer in -16384 .. 16383)", r,
+                        "xyz"[a], (double)c);
+      g[a] = (int)c + 256 * 64;
+    }
+    if (p[3] != p[3]) return er::fail("er_tsdf_import_world: row %ld: the intensity is NaN", r);
+    const int key = (g[0] >> 6) << 18 | (g[1] >> 6) << 9 | (g[2] >> 6);
+    if (key != last) ukeys.push_back(last = key);
+  }
+  std::sort(ukeys.begin(), ukeys.end());
+  ukeys.erase(std::unique(ukeys.begin(), ukeys.end()), ukeys.end());
+  if ((long)ukeys.size() > (long)h->max_units)
+    return er::fail("er_tsdf_import_world: the list needs %ld units, max_units is %d", (long)ukeys.size(), h->max_units);
+  if (n == 0) return 0;
+  // From here on a failure leaves units behind: every exit but the last resets the volume.
+  struct Undo {
+    er_tsdf_t h;
+    bool armed = true;
+    ~Undo() { if (armed) (void)er_tsdf_reset(h); }
+  } undo{h};
+  SlabPass t;                                                // (only as the owner of the staging buffer)
+  const long chunk = std::min<long>(n, 1L << 22);            // 64 MiB of rows at a time
+  float4* d_rows = nullptr;
+  ER_W_OWNED(who, t, &d_rows, (size_t)chunk * sizeof(float4));
+  // the units: fresh ones of an empty volume are (+0, 0) everywhere (er_tsdf_create, er_tsdf_reset)
+  if (resolve_slots(h, ukeys.data(), (int)ukeys.size(), true) || check_flags(h)) return 1;
+  for (long r0 = 0; r0 < n; r0 += chunk) {
+    const long m = std::min(chunk, n - r0);
+    ER_W(who, hipMemcpyAsync(d_rows, xyzi_host + 4 * r0, (size_t)m * sizeof(float4), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_import_world, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, h->pool, h->ht_key, h->ht_slot, h->ht_cap - 1,
+                       h->ht_shift, d_rows, m);
+    ER_W(who, hipGetLastError());
+    ER_W(who, hipStreamSynchronize(h->stream));             // (the host rows may be pageable, the staging buffer is reused)
+  }
+  double sum = 0.0;
+  if (er_tsdf_sum_weight(h, &sum)) return 1;
+  if (sum != (double)n) {
+    // fewer distinct voxels than rows: one is listed twice.  The slow way to the FIRST row that repeats an earlier one:
+    std::vector<std::pair<long long, long>> id((size_t)n);
+    for (long r = 0; r < n; r++) {
+      const float* p = xyzi_host + 4 * r;
+      id[(size_t)r] = std::make_pair(((long long)((int)p[0] + 16384) << 30) | ((long long)((int)p[1] + 16384) << 15) | (long long)((int)p[2] + 16384), r);
+    }
+    std::sort(id.begin(), id.end());
+    long first = -1, of = -1;
+    for (long q = 1; q < n; q++)
+      if (id[(size_t)q].first == id[(size_t)q - 1].first && (first < 0 || id[(size_t)q].second < first)) {
+        first = id[(size_t)q].second;
+        of = id[(size_t)q - 1].second;
+      }
+    if (first < 0) return er::fail("er_tsdf_import_world: the weights sum to %.17g, not to the %ld rows", sum, n);
+    const float* p = xyzi_host + 4 * first;
+    return er::fail("er_tsdf_import_world: row %ld lists voxel (%d, %d, %d) again (row %ld has it already)", first, (int)p[0], (int)p[1], (int)p[2], of);
+  }
+  undo.armed = false;
+  if (n_units) *n_units = (int)ukeys.size();
   return 0;
 }
 

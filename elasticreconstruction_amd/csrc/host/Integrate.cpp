@@ -22,6 +22,8 @@
 //                         (er_tsdf_set_unit_shard): no collective, world.pcd BIT-identical to the single-GPU run
 //   --save_fragment <file.pcd> [--fragment_length <m>, 3.0]   after the run also write cloud_bin_<i>.pcd-style points with normals
 //                         (er_tsdf_extract_oriented, inside the cube [0, length)); single-GPU runs only
+//   --save_mesh <file.ply>   after the run also write the volume's marching-cubes mesh: indexed, with normals, binary PLY
+//                         (er_tsdf_extract_mesh_indexed; bin/MeshOutput makes the same kind of file from world.pcd); single-GPU runs only
 //   --force_merge         with --gpus 1: run the frame-split merge anyway (exercises the RCCL path on a 1-GPU box)
 //
 // Control flow = CIntegrateApp::StartMainLoop/Execute: 1-based frame ids, frame_ == -1 skips a frame,
@@ -71,6 +73,7 @@ int print_help() {
   std::cout << "MI355X options:" << std::endl;
   std::cout << "    --device <gpu> (0)  --max_units <n> (2048)  --batch <frames> (64)" << std::endl;
   std::cout << "    --save_fragment <pcd_file> [--fragment_length <m> (3.0)] : also write the volume's surface points with normals, cloud_bin-style (single GPU only)" << std::endl;
+  std::cout << "    --save_mesh <ply_file>          : also write the volume's marching-cubes mesh, indexed, with normals, binary PLY (single GPU only)" << std::endl;
   std::cout << "    --gpus <N> (1)  --shard frame|unit (frame: frame blocks + the merge by unit owner over RCCL; unit: bit-exact, no collective)  --merge_root <g>  --force_merge" << std::endl;
   return 0;
 }
@@ -365,6 +368,20 @@ struct App {
     printf("%ld fragment points have been written.\n", (long)(rows.size() / 6));
     return true;
   }
+
+  // --save_mesh: the indexed marching-cubes mesh of the resident volume as binary PLY with normals (er_tsdf_extract_mesh_indexed) -- what
+  // bin/MeshOutput makes of world.pcd, without the file in between and from the voxels SaveWorld's filter drops as well
+  bool SaveMesh(const std::string& filename) {
+    long nv = 0, nt = 0;
+    if (er_tsdf_extract_mesh_indexed(volume_, nullptr, nullptr, 0, nullptr, 0, &nv, &nt) != 0) { fprintf(stderr, "Integrate: %s\n", er_last_error()); return false; }
+    std::vector<float> verts((size_t)nv * 4), nrm((size_t)nv * 4);
+    std::vector<int> tris((size_t)nt * 3);
+    if (nv > 0 && er_tsdf_extract_mesh_indexed(volume_, verts.data(), nrm.data(), nv, tris.data(), nt, &nv, &nt) != 0) { fprintf(stderr, "Integrate: %s\n", er_last_error()); return false; }
+    static const float none[4] = {0.f, 0.f, 0.f, 0.f};                 // (an empty mesh still declares nx ny nz)
+    if (!erfmt::save_ply(filename, verts.data(), 4, nv > 0 ? nrm.data() : none, 4, (size_t)nv, tris.data(), (size_t)nt, true)) { fprintf(stderr, "Integrate: cannot write %s\n", filename.c_str()); return false; }
+    printf("%ld mesh vertices and %ld triangles have been written.\n", nv, nt);
+    return true;
+  }
 };
 
 // hash_key of the unit a SaveWorld point (voxel index coordinates, TSDFVolume.cpp:119-121) belongs to.
@@ -463,6 +480,8 @@ int main(int argc, char* argv[]) {
   double fragment_length = 3.0;
   parse_argument(argc, argv, "--save_fragment", fragment_file);
   parse_argument(argc, argv, "--fragment_length", fragment_length);
+  std::string mesh_file;                                                // --save_mesh <file.ply>: the indexed mesh of the volume
+  parse_argument(argc, argv, "--save_mesh", mesh_file);
   const bool force_merge = find_switch(argc, argv, "--force_merge");
   int merge_root = ER_MERGE_DISTRIBUTED;                                // --merge_root <g>: gather the merged volume on worker g before SaveWorld
   parse_argument(argc, argv, "--merge_root", merge_root);
@@ -477,6 +496,10 @@ int main(int argc, char* argv[]) {
   if (merge_root != ER_MERGE_DISTRIBUTED && (merge_root < 0 || merge_root >= gpus)) { fprintf(stderr, "Integrate: --merge_root must name one of the %d workers\n", gpus); return 1; }
   if (!fragment_file.empty() && gpus > 1) {
     fprintf(stderr, "Integrate: --save_fragment needs the whole volume on one GPU; it is not available with --gpus %d\n", gpus);
+    return 1;
+  }
+  if (!mesh_file.empty() && gpus > 1) {
+    fprintf(stderr, "Integrate: --save_mesh needs the whole volume on one GPU; it is not available with --gpus %d\n", gpus);
     return 1;
   }
   const bool unit_shard = shard == "unit";
@@ -574,6 +597,10 @@ int main(int argc, char* argv[]) {
   if (rc == 0 && !fragment_file.empty()) {
     if (!apps[0].SaveFragment(fragment_file, (float)fragment_length)) rc = 1;
     stage_done("SaveFragment");
+  }
+  if (rc == 0 && !mesh_file.empty()) {
+    if (!apps[0].SaveMesh(mesh_file)) rc = 1;
+    stage_done("SaveMesh");
   }
   std::cout << "Total " << last_id << " frames processed." << std::endl;
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

@@ -1,0 +1,120 @@
+// MeshOutput -- the last box of the reference workflow (README.txt:100-103: "pcl_kinfu_largeScale_mesh_output world.pcd", a tool of the
+// author's PCL fork, outside the reference tree): world.pcd in, a triangle mesh out, with the numeric core on MI355X through liber_hip.so.
+//
+//   MeshOutput <world.pcd> [--save_to mesh.ply] [--ascii] [--no_normals] [--device D]
+//
+// world.pcd is TSDFVolume::SaveWorld's voxel list (FIELDS x y z intensity; ascii, binary or binary_compressed): integer voxel indices and
+// the sdf.  The list goes back into a volume sized from its own unit keys (er_tsdf_import_world: every listed voxel observed with weight 1),
+// the volume's marching-cubes mesh comes out indexed with a normal per vertex (er_tsdf_extract_mesh_indexed), and the mesh is written as
+// PLY (binary little endian unless --ascii; nx ny nz unless --no_normals; a vertex without a normal gets 0 0 0).  The mesh is the one of the
+// voxels the file holds: SaveWorld drops |sdf| >= 0.98 and unobserved voxels, so cells next to those are missing here and present in
+// `Integrate --save_mesh`, which reads the resident volume.  ER_TIMING=1 prints the stages.
+#include <cmath>
+#include <cstdio>
+#include <string>
+#include <vector>
+
+#include "er_formats.h"
+#include "er_hip.h"
+
+namespace {
+
+const char* kWho = "MeshOutput";
+
+int print_help() {
+  printf("Usage: MeshOutput <world.pcd> [options]\n"
+         "  world.pcd                 the voxel list Integrate writes (FIELDS x y z intensity)\n"
+         "  --save_to <file> (=mesh.ply)  the mesh: indexed triangles, PLY\n"
+         "  --ascii                   write an ascii PLY (default: binary_little_endian)\n"
+         "  --no_normals              leave out the per-vertex normals nx ny nz\n"
+         "  --device <gpu> (=0)\n"
+         "  -h [ --help ]             print this message\n");
+  return 0;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  erfmt::stage_done("process start");
+  using namespace erfmt;
+  if (argc == 1 || find_switch(argc, argv, "--help") || find_switch(argc, argv, "-h")) return print_help();
+  std::string in_file = argv[1], out_file = "mesh.ply";
+  int device = 0;
+  parse_argument(argc, argv, "--save_to", out_file);
+  parse_argument(argc, argv, "--device", device);
+  const bool ascii = find_switch(argc, argv, "--ascii"), no_normals = find_switch(argc, argv, "--no_normals");
+
+  std::vector<std::vector<float>> cols;
+  size_t n = 0;
+  if (!file_exists(in_file)) {
+    fprintf(stderr, "%s: cannot open %s\n", kWho, in_file.c_str());
+    return 1;
+  }
+  if (!load_pcd_fields(in_file, {"x", "y", "z", "intensity"}, cols, n)) {
+    fprintf(stderr, "%s: %s is not a PCD file this program can read\n", kWho, in_file.c_str());
+    return 1;
+  }
+  // rows x y z intensity, and the units they name: the volume is sized from the file (a row that is no voxel index is left to
+  // er_tsdf_import_world, which names it)
+  std::vector<float> rows(n * 4);
+  std::vector<int> keys;
+  int last = -1;
+  for (size_t i = 0; i < n; i++) {
+    int g[3];
+    bool ok = true;
+    for (int a = 0; a < 3; a++) {
+      const float c = cols[(size_t)a][i];
+      rows[i * 4 + (size_t)a] = c;
+      ok = ok && c >= -16384.0f && c <= 16383.0f;
+      g[a] = ok ? (int)std::floor(c) + 256 * 64 : 0;
+    }
+    rows[i * 4 + 3] = cols[3][i];
+    const int key = (g[0] >> 6) << 18 | (g[1] >> 6) << 9 | (g[2] >> 6);
+    if (ok && key != last) keys.push_back(last = key);
+  }
+  std::sort(keys.begin(), keys.end());
+  keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+  stage_done("read world.pcd");
+
+  if (er_device_count() <= 0) {
+    fprintf(stderr, "%s: no HIP device available (liber_hip has no CPU fallback)\n", kWho);
+    return 1;
+  }
+  er_tsdf_t vol = nullptr;
+  float cam[6];
+  load_camera("", cam);                                      // (the volume's image plays no part here: the default camera)
+  if (er_tsdf_create(640, 480, cam, (int)std::max<size_t>(keys.size(), 1), device, &vol) != 0) {
+    fprintf(stderr, "%s: %s\n", kWho, er_last_error());
+    return 1;
+  }
+  stage_done("HIP runtime up, volume created");
+  int rc = 0, n_units = 0;
+  long nv = 0, nt = 0;
+  std::vector<float> verts, nrm;
+  std::vector<int> tris;
+  if (er_tsdf_import_world(vol, rows.data(), (long)n, &n_units) != 0) rc = 1;
+  stage_done("import (er_tsdf_import_world)");
+  if (rc == 0 && er_tsdf_extract_mesh_indexed(vol, nullptr, nullptr, 0, nullptr, 0, &nv, &nt) != 0) rc = 1;
+  if (rc == 0 && nv > 0) {
+    verts.resize((size_t)nv * 4);
+    if (!no_normals) nrm.resize((size_t)nv * 4);
+    tris.resize((size_t)nt * 3);
+    if (er_tsdf_extract_mesh_indexed(vol, verts.data(), no_normals ? nullptr : nrm.data(), nv, tris.data(), nt, &nv, &nt) != 0) rc = 1;
+  }
+  stage_done("mesh (er_tsdf_extract_mesh_indexed)");
+  if (rc != 0) {
+    fprintf(stderr, "%s: %s\n", kWho, er_last_error());
+    er_tsdf_destroy(vol);
+    return 1;
+  }
+  static const float none[4] = {0.f, 0.f, 0.f, 0.f};         // (an empty mesh with normals still declares nx ny nz)
+  if (!save_ply(out_file, verts.data(), 4, no_normals ? nullptr : (nv > 0 ? nrm.data() : none), 4, (size_t)nv, tris.data(), (size_t)nt, !ascii)) {
+    fprintf(stderr, "%s: cannot write %s\n", kWho, out_file.c_str());
+    er_tsdf_destroy(vol);
+    return 1;
+  }
+  stage_done("write PLY");
+  printf("%s: %zu voxels in %d units -> %ld vertices, %ld triangles -> %s\n", kWho, n, n_units, nv, nt, out_file.c_str());
+  er_tsdf_destroy(vol);
+  return 0;
+}

@@ -323,6 +323,48 @@ inline bool save_pcd_xyzn(const std::string& path, const float* rows, size_t n) 
   return true;
 }
 
+// A triangle mesh as PLY, byte for byte what formats.save_ply writes: verts = nv rows of vstride >= 3 floats (x y z first -- the rows of
+// er_tsdf_extract_mesh_indexed have 4), normals = nullptr or nv rows of nstride >= 3 floats, tris = nt x 3 int32.  A normal with a NaN
+// component is written as 0 0 0 (the ABI's "no normal"; a viewer chokes on NaN).  binary: little-endian float32 rows, then uchar 3 + int32
+// rows; ascii: %.9g floats, one space between columns.
+inline bool save_ply(const std::string& path, const float* verts, int vstride, const float* normals, int nstride, size_t nv, const int32_t* tris,
+                     size_t nt, bool binary) {
+  FILE* f = fopen(path.c_str(), "wb");
+  if (!f) return false;
+  fprintf(f, "ply\nformat %s 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n%s"
+             "element face %zu\nproperty list uchar int vertex_indices\nend_header\n",
+          binary ? "binary_little_endian" : "ascii", nv, normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "", nt);
+  const int k = normals ? 6 : 3;
+  std::vector<uint8_t> buf;
+  if (binary) buf.reserve(std::max(nv * (size_t)k * 4, nt * 13));
+  for (size_t i = 0; i < nv; i++) {
+    float r[6] = {verts[i * vstride], verts[i * vstride + 1], verts[i * vstride + 2], 0.f, 0.f, 0.f};
+    if (normals) {
+      const float* q = normals + i * (size_t)nstride;
+      if (!(q[0] != q[0] || q[1] != q[1] || q[2] != q[2])) { r[3] = q[0]; r[4] = q[1]; r[5] = q[2]; }
+    }
+    if (binary) {
+      buf.insert(buf.end(), (const uint8_t*)r, (const uint8_t*)r + 4 * k);       // (little-endian hosts only, like the PCD writers)
+    } else {
+      for (int c = 0; c < k; c++) fprintf(f, c ? " %.9g" : "%.9g", (double)r[c]);
+      fputc('\n', f);
+    }
+  }
+  if (binary && !buf.empty()) fwrite(buf.data(), 1, buf.size(), f);
+  buf.clear();
+  for (size_t t = 0; t < nt; t++) {
+    if (binary) {
+      buf.push_back(3);
+      buf.insert(buf.end(), (const uint8_t*)(tris + 3 * t), (const uint8_t*)(tris + 3 * t + 3));
+    } else {
+      fprintf(f, "3 %d %d %d\n", tris[3 * t], tris[3 * t + 1], tris[3 * t + 2]);
+    }
+  }
+  if (binary && !buf.empty()) fwrite(buf.data(), 1, buf.size(), f);
+  const bool ok = !ferror(f);
+  return fclose(f) == 0 && ok;
+}
+
 // LZF stream writer (the format lzf_decompress above reads; liblzf's published container-less format as PCL's
 // "DATA binary_compressed" uses it): greedy matcher over a hash of 3-byte strings, back references of 3..264 bytes
 // up to 8192 bytes back, literal runs of up to 32 bytes.

@@ -349,6 +349,96 @@ def save_pcd_xyzn(path, xyz, normals, binary=True):
             f.write(s.getvalue().encode("ascii"))
 
 
+def _ply_header(n, m, normals, binary):
+    return ("ply\nformat %s 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n%s"
+            "element face %d\nproperty list uchar int vertex_indices\nend_header\n"
+            % ("binary_little_endian" if binary else "ascii", n,
+               "property float nx\nproperty float ny\nproperty float nz\n" if normals else "", m))
+
+
+def save_ply(path, verts, tris, normals=None, binary=True):
+    """A triangle mesh as PLY (what kinfu's mesh output leaves for a viewer; csrc/host/er_formats.h's save_ply writes the same bytes).
+    verts: float32[n, 3] -- or [n, 4], TSDFVolume.extract_indexed_mesh's x y z axis rows: the fourth column is not written; tris: int32[m, 3];
+    normals: float32[n, 3] or None.  A normal with a NaN component is written as 0 0 0: the ABI keeps the NaN ("no normal"), a viewer chokes
+    on it, and a zero vector is what mesh tools take for "unset".  binary: little-endian float32 / uchar 3 + int32 rows; ascii: %.9g floats,
+    one space between columns."""
+    v = np.asarray(verts, np.float32)
+    if v.ndim != 2 or v.shape[1] not in (3, 4):
+        raise ValueError("save_ply: verts must be [n, 3] or [n, 4], not %s" % (v.shape,))
+    v = np.ascontiguousarray(v[:, :3])
+    t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    cols = [v]
+    if normals is not None:
+        nr = np.array(normals, np.float32).reshape(-1, 3)
+        if nr.shape[0] != v.shape[0]:
+            raise ValueError("save_ply: %d normals for %d vertices" % (nr.shape[0], v.shape[0]))
+        nr[np.isnan(nr).any(axis=1)] = 0.0
+        cols.append(nr)
+    a = np.ascontiguousarray(np.concatenate(cols, axis=1))
+    with open(path, "wb") as f:
+        f.write(_ply_header(v.shape[0], t.shape[0], normals is not None, binary).encode("ascii"))
+        if binary:
+            f.write(a.astype("<f4").tobytes())
+            face = np.empty(t.shape[0], np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+            face["n"] = 3
+            face["i"] = t
+            f.write(face.tobytes())
+        else:
+            s = io.StringIO()
+            np.savetxt(s, a, fmt="%.9g")
+            np.savetxt(s, np.concatenate([np.full((t.shape[0], 1), 3, np.int32), t], axis=1), fmt="%d")
+            f.write(s.getvalue().encode("ascii"))
+
+
+def load_ply(path):
+    """Reads what save_ply writes (and any PLY of that shape: float x y z, optionally nx ny nz, faces as list uchar int, triangles only).
+    Returns (verts float32[n, 3], tris int32[m, 3], normals float32[n, 3] or None)."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    end = raw.index(b"end_header\n") + len(b"end_header\n")
+    lines = raw[:end].decode("ascii").split("\n")
+    if lines[0] != "ply":
+        raise ValueError("%s is not a PLY file" % path)
+    mode, n, m, props, cur = None, 0, 0, [], None
+    for line in lines[1:]:
+        w = line.split()
+        if not w or w[0] == "comment":
+            continue
+        if w[0] == "format":
+            mode = w[1]
+        elif w[0] == "element":
+            cur = w[1]
+            if cur == "vertex":
+                n = int(w[2])
+            elif cur == "face":
+                m = int(w[2])
+        elif w[0] == "property" and cur == "vertex":
+            if w[1] != "float":
+                raise ValueError("load_ply: vertex property %s is not a float" % w[-1])
+            props.append(w[2])
+        elif w[0] == "property" and cur == "face" and w[1:4] != ["list", "uchar", "int"]:
+            raise ValueError("load_ply: faces must be 'list uchar int'")
+    if props not in (["x", "y", "z"], ["x", "y", "z", "nx", "ny", "nz"]):
+        raise ValueError("load_ply: vertex properties %s" % props)
+    k = len(props)
+    if mode == "binary_little_endian":
+        a = np.frombuffer(raw, "<f4", n * k, end).reshape(n, k).astype(np.float32)
+        face = np.frombuffer(raw, np.dtype([("n", "u1"), ("i", "<i4", (3,))]), m, end + 4 * n * k)
+        if m and (face["n"] != 3).any():
+            raise ValueError("load_ply: a face is not a triangle")
+        t = face["i"].astype(np.int32).reshape(m, 3)
+    elif mode == "ascii":
+        tok = raw[end:].decode("ascii").split()
+        a = np.array(tok[:n * k], dtype=np.float32).reshape(n, k)
+        ft = np.array(tok[n * k:n * k + 4 * m], dtype=np.int64).reshape(m, 4)
+        if m and (ft[:, 0] != 3).any():
+            raise ValueError("load_ply: a face is not a triangle")
+        t = ft[:, 1:].astype(np.int32)
+    else:
+        raise ValueError("load_ply: unsupported format %r" % mode)
+    return np.ascontiguousarray(a[:, :3]), np.ascontiguousarray(t), (np.ascontiguousarray(a[:, 3:]) if k == 6 else None)
+
+
 # GlobalRegistration's alignment.config (helper.h's Configuration): key=value lines.  The defaults are the values of the file the reference ships.
 ALIGNMENT_DEFAULTS = dict(visualization=False, estimate_normal=True, aux_data=False, smart_swap=True, pcl_verbose=3, normal_radius=0.1,
                           feature_radius=0.25, max_iteration=4000000, num_of_samples=4, correspondence_randomness=2, edge_similarity=0.9,

@@ -8,6 +8,7 @@ All arithmetic runs in the HIP kernels of liber_hip.so; this file only marshals 
 reproduces the reference's per-frame control flow (frame ids are 1-based, IntegrateApp.cpp:185).
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -250,6 +251,40 @@ class TSDFVolume:
         pts = self.extract_world()
         formats.save_pcd_xyzi(filename, pts)
         return pts.shape[0]
+
+    def extract_indexed_mesh(self):
+        """extract_mesh's triangles as an indexed mesh (er_tsdf_extract_mesh_indexed): (verts float32[n, 4] = x y z axis, normals float32[n, 3],
+        tris int32[m, 3]).  A vertex is a lattice edge that a triangle uses, in extract_surface's order; verts[tris][..., :3] is extract_mesh's
+        soup bit for bit; a normal is extract_oriented's rule at the vertex, NaN where it gives none."""
+        nv, nt = C.c_long(0), C.c_long(0)
+        _ffi.check(self._lib.er_tsdf_extract_mesh_indexed(self._h, None, None, 0, None, 0, C.byref(nv), C.byref(nt)), "er_tsdf_extract_mesh_indexed")
+        verts = np.empty((nv.value, 4), dtype=np.float32)
+        nrm = np.empty((nv.value, 4), dtype=np.float32)
+        tris = np.empty((nt.value, 3), dtype=np.int32)
+        if nv.value:
+            _ffi.check(self._lib.er_tsdf_extract_mesh_indexed(self._h, _ffi.ptr(verts), _ffi.ptr(nrm), nv.value, _ffi.ptr(tris), nt.value,
+                                                              C.byref(nv), C.byref(nt)), "er_tsdf_extract_mesh_indexed")
+        return verts, np.ascontiguousarray(nrm[:, :3]), tris
+
+    def SaveMesh(self, filename, normals=True, binary=True):
+        """The indexed mesh of the resident volume as PLY (formats.save_ply; NaN normals become 0 0 0).  Returns (vertices, triangles)."""
+        verts, nrm, tris = self.extract_indexed_mesh()
+        formats.save_ply(filename, verts, tris, nrm if normals else None, binary)
+        return verts.shape[0], tris.shape[0]
+
+    def LoadWorld(self, path_or_array):
+        """SaveWorld's inverse (er_tsdf_import_world) into this EMPTY volume: a world.pcd path, or float32[n, 4] = x y z intensity rows as
+        extract_world returns them.  Every listed voxel becomes (intensity, weight 1) -- the file carries no weights, 1 marks "observed".
+        Returns the number of units created; after a refusal the volume is empty."""
+        if isinstance(path_or_array, (str, bytes, os.PathLike)):
+            f = formats.load_pcd(path_or_array)
+            a = np.stack([np.asarray(f[k], np.float32).reshape(-1) for k in ("x", "y", "z", "intensity")], axis=1)
+        else:
+            a = np.asarray(path_or_array, np.float32)
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 4)
+        nu = C.c_int(0)
+        _ffi.check(self._lib.er_tsdf_import_world(self._h, _ffi.ptr(a), a.shape[0], C.byref(nu)), "er_tsdf_import_world")
+        return nu.value
 
     # -- multi-GPU frame split (SURVEY.md 8e) ----------------------------------------------------
     def export_weighted(self, keys, dev_ptr):

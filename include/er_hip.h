@@ -164,6 +164,33 @@ int er_tsdf_extract_oriented(er_tsdf_t h, float* points_host, float* normals_hos
 int er_tsdf_extract_mesh(er_tsdf_t h, float* tri_host, long capacity_triangles, long* n_triangles);
 int er_mc_table(unsigned char out[256 * 16]);
 
+/* The same mesh INDEXED (what kinfu's mesh output hands to a viewer): unique vertices, a normal each, and int32 triangles.
+ * Triangles: exactly er_tsdf_extract_mesh's, in its order, as three indices into the vertex list -- verts[tri] reproduces the soup bit for bit.
+ * A vertex is a lattice EDGE (its lower voxel L and an axis) that at least one emitted triangle uses: the edge is crossed, (F_L < 0) != (F_H < 0),
+ * and at least one of the up to four cells around it has all eight voxels observed.  It is not keyed by its position: two edges that meet in a
+ * voxel whose sdf is exactly 0 give the same coordinates and stay two vertices.  Position: er_tsdf_extract_mesh's expression from the edge's
+ * lower end.  Order: the unit of L by ascending key, L in i, j, k order, axes x, y, z -- er_tsdf_extract_surface's order but not its set (a
+ * surface point needs two observed voxels of strictly opposite sign; a mesh vertex needs a complete cell and counts sdf == 0 as outside).
+ * verts_host: 4 floats per vertex (x y z axis), er_tsdf_extract_surface's layout; normals_host: 4 floats per vertex (nx ny nz 0): the rule of
+ * er_tsdf_extract_oriented applied to the vertex position, NaN NaN NaN 0 where it gives none; tri_host: 3 ints per triangle.  Any of the three
+ * may be NULL; all three NULL: only counts.  Capacities are in vertices and in triangles; one that is too small is refused with the need in the
+ * message, after *n_vertices and *n_triangles have been set, and nothing is written.  More than 2^31 - 1 vertices are refused.  An empty
+ * volume, or one without a crossing, gives 0 and 0 and succeeds.  No result depends on the order in which workgroups run: the same bytes on
+ * every call. */
+int er_tsdf_extract_mesh_indexed(er_tsdf_t h, float* verts_host, float* normals_host, long capacity_vertices, int* tri_host,
+                                 long capacity_triangles, long* n_vertices, long* n_triangles);
+
+/* TSDFVolume::SaveWorld's inverse: a world.pcd voxel list back into a volume.  xyzi_host: n rows x y z intensity in er_tsdf_extract_world's
+ * layout -- x, y, z integer voxel indices as floats, i + (xi - 256) * 64; intensity = the sdf.  Afterwards every listed voxel is (intensity, 1)
+ * and every other voxel of a created unit (+0, 0); the created units are those with at least one listed voxel, *n_units (nullable) their number.
+ * world.pcd carries no weights: 1 only marks "observed", so the volume is one to extract from, not one to go on integrating into.  What
+ * SaveWorld's filter dropped (|sdf| >= 0.98, never-observed voxels) stays unobserved.
+ * Refused, each naming the first offending row: a coordinate that is not an integer value or lies outside the 512-unit lattice; a NaN
+ * intensity; a voxel listed twice.  Also refused: a volume that already holds units (er_tsdf_reset it first), and a list that needs more than
+ * max_units units (the message names both numbers).  After any of these refusals the volume is empty -- also the one that held units.
+ * n == 0 succeeds with no units. */
+int er_tsdf_import_world(er_tsdf_t h, const float* xyzi_host, long n, int* n_units);
+
 /* The resident volume ray-cast from a pose: the model side of frame-to-model tracking (er_odom_align_model below) and a
  * direct picture of what er_tsdf_integrate_frames built.  The reference tree has no ray caster (KinFu's lives in the author's PCL fork):
  * this entry restates tests/raycast_restatement.py, the numpy statement of csrc/er_raycast_math.h, bit for bit, and NOTHING here is checked
