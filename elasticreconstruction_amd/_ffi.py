@@ -24,7 +24,7 @@ SYMBOLS = [
     "er_comm_unique_id", "er_comm_create", "er_comm_create_local", "er_comm_create_loopback", "er_comm_destroy", "er_comm_rank", "er_comm_world",
     "er_tsdf_allreduce", "er_comm_merge_stats", "er_comm_merge_stats_owner", "er_frame_block",
     "er_cloud_create", "er_cloud_create_batch", "er_cloud_create_from_tsdf", "er_cloud_destroy", "er_cloud_size",
-    "er_icp_count_inliers", "er_icp_align", "er_find_correspondence",
+    "er_icp_count_inliers", "er_icp_align", "er_icp_align_trace", "er_find_correspondence",
     "er_icp_count_inliers_batch", "er_icp_align_batch", "er_find_correspondence_batch", "er_icp_release_workspaces", "er_registration_batch", "er_ransac_fitness_batch", "er_ransac_inliers",
     "er_features_create", "er_features_destroy", "er_features_size", "er_feature_knn", "er_ransac_hypotheses", "er_ransac_params_default", "er_ransac_align", "er_ransac_align_batch",
     "er_odom_params_default", "er_odom_create", "er_odom_destroy", "er_odom_align_pairs", "er_odom_track", "er_frame_to_model_align", "er_frames_to_models_align", "er_odom_linearize", "er_odom_read_maps", "er_odom_tables",
@@ -181,6 +181,8 @@ def lib():
         L.er_cloud_size.argtypes = [vp]
         L.er_icp_count_inliers.argtypes = [vp, vp, vp, C.c_double, ip]
         L.er_icp_align.argtypes = [vp, vp, vp, C.c_double, C.c_int, C.c_double, C.c_int, vp, ip, ip, dp]
+        if hasattr(L, "er_icp_align_trace"):                    # (absent from an older build selected with ER_HIP_LIB)
+            L.er_icp_align_trace.argtypes = [vp, vp, vp, C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, ip, vp, ip, ip]
         L.er_find_correspondence.argtypes = [vp, vp, vp, C.c_double, C.c_double, vp, C.c_int, ip, vp]
         L.er_icp_count_inliers_batch.argtypes = [C.c_int, vp, vp, vp, C.c_double, vp]
         L.er_icp_align_batch.argtypes = [C.c_int, vp, vp, vp, C.c_double, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp]

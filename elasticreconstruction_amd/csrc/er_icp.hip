@@ -517,8 +517,9 @@ __global__ __launch_bounds__(kBlock, 6) void k_icp_iter(const PairDev* __restric
 // (8 strided slices per value, then the slices in order) and decides -- 6x6 solve, increment, stop rule: the loop never leaves
 // the device.  A separate launch on purpose: finishing inside k_icp_iter ("last workgroup done" ticket + __threadfence) costs
 // an L2 write-back per workgroup on this multi-XCD part (measured in round 1: 100-600 us per launch instead of ~25).
+// tot_out (NULL everywhere but er_icp_align_trace): the 29 totals as dev_icp_decide receives them, 32 doubles per active pair.
 __global__ __launch_bounds__(kBlock) void k_icp_final(const PairDev* __restrict__ P, const int* __restrict__ active, IcpDev* __restrict__ S, IcpParams prm,
-                                                      int pts) {
+                                                      int pts, double* __restrict__ tot_out) {
   const int slot = active[blockIdx.x];
   IcpDev* st = S + slot;
   if (st->done) return;
@@ -551,6 +552,7 @@ __global__ __launch_bounds__(kBlock) void k_icp_final(const PairDev* __restrict_
     }
     // value = h 2^64 + l (two's complement): two roundings to float64, far below the wave sums' own
     tot[threadIdx.x] = (ldexp((double)h, 64) + (double)l) * P[slot].fx_inv[threadIdx.x];
+    if (tot_out) tot_out[(size_t)blockIdx.x * kAcc + threadIdx.x] = tot[threadIdx.x];
   }
   __syncthreads();
   if (threadIdx.x == 0) dev_icp_decide(tot, st, prm);
@@ -1208,7 +1210,7 @@ int er_icp_align_batch(int n, const er_cloud_t* src, const er_cloud_t* tgt, cons
       for (int c = 0; c < chunk_len; c++) {
         hipLaunchKernelGGL(k_icp_iter, dim3(mxp, n_active), dim3(kBlock), 0, g->stream, g->d_pairs, g->d_active, g->d_state, (float)max_dist,
                            max_dist * max_dist, pts);
-        hipLaunchKernelGGL(k_icp_final, dim3(n_active), dim3(kBlock), 0, g->stream, g->d_pairs, g->d_active, g->d_state, prm, pts);
+        hipLaunchKernelGGL(k_icp_final, dim3(n_active), dim3(kBlock), 0, g->stream, g->d_pairs, g->d_active, g->d_state, prm, pts, (double*)nullptr);
       }
       ER_HIP_TRY(hipGetLastError());
       ER_HIP_TRY(hipMemcpyAsync(g->h_state, g->d_state, (size_t)m * sizeof(IcpDev), hipMemcpyDeviceToHost, g->stream));
@@ -1244,6 +1246,64 @@ int er_icp_align(er_cloud_t src, er_cloud_t tgt, const float guess[16], double m
                  double transformation_epsilon, int stop_rule, float out[16], int* iterations, int* converged, double* fitness) {
   if (!guess || !out) return er::fail("er_icp_align: NULL argument");
   return er_icp_align_batch(1, &src, &tgt, guess, max_dist, max_iter, transformation_epsilon, stop_rule, out, iterations, converged, fitness);
+}
+
+// Test hook: er_icp_align for ONE pair with one iteration per host visit -- the same k_icp_iter, k_icp_final and dev_icp_decide, `pts` slices per
+// workgroup as the caller says -- and after every iteration the totals k_icp_final handed to dev_icp_decide and the state it left (include/er_hip.h).
+int er_icp_align_trace(er_cloud_t src, er_cloud_t tgt, const float guess[16], double max_dist, int max_iter, double transformation_epsilon, int stop_rule,
+                       int pts, int row_capacity, double* totals, float* fin, float* delta, int* state, double* prev_mse, double* fx_scale, int* n_rows,
+                       float out[16], int* iterations, int* converged) {
+  int device;
+  if (!guess || !out || !n_rows || row_capacity < 0 || (row_capacity > 0 && (!totals || !fin || !delta || !state || !prev_mse)))
+    return er::fail("er_icp_align_trace: NULL argument");
+  if (pts < 1 || pts > kIcpPtsMax) return er::fail("er_icp_align_trace: pts = %d outside 1..%d", pts, kIcpPtsMax);
+  if (batch_prologue(1, &src, &tgt, max_dist, "er_icp_align_trace", &device)) return 1;
+  GroupLease L;
+  if (L.acquire(device)) return 1;
+  Group* g = L.g;
+  const IcpParams prm{transformation_epsilon, max_iter, stop_rule};
+  if (group_describe(g, 0, 1, &src, &tgt, nullptr, true)) return 1;
+  if (fx_scale)
+    for (int k = 0; k < 29; k++) fx_scale[k] = g->h_pairs[0].fx_scale[k];
+  IcpDev& st = g->h_state[0];
+  memset(&st, 0, sizeof st);
+  memcpy(st.fin, guess, sizeof st.fin);
+  bool ident = true;
+  for (int i = 0; i < 16; i++) {
+    st.delta[i] = st.prev_delta[i] = (i % 5 == 0) ? 1.f : 0.f;
+    ident = ident && guess[i] == ((i % 5 == 0) ? 1.f : 0.f);
+  }
+  st.prev_mse = DBL_MAX;
+  st.init_apply = ident ? 0 : 1;
+  if (src->n == 0 || tgt->n == 0) st.done = 1;
+  g->h_active[0] = 0;
+  ER_HIP_TRY(hipMemcpyAsync(g->d_state, g->h_state, sizeof(IcpDev), hipMemcpyHostToDevice, g->stream));
+  ER_HIP_TRY(hipMemcpyAsync(g->d_active, g->h_active, sizeof(int), hipMemcpyHostToDevice, g->stream));
+  const int mxp = (g->h_pairs[0].nb + pts - 1) / pts;
+  int rows = 0;
+  while (!st.done) {
+    hipLaunchKernelGGL(k_icp_iter, dim3(mxp, 1), dim3(kBlock), 0, g->stream, g->d_pairs, g->d_active, g->d_state, (float)max_dist, max_dist * max_dist, pts);
+    hipLaunchKernelGGL(k_icp_final, dim3(1), dim3(kBlock), 0, g->stream, g->d_pairs, g->d_active, g->d_state, prm, pts, g->d_info);
+    ER_HIP_TRY(hipGetLastError());
+    ER_HIP_TRY(hipMemcpyAsync(g->h_state, g->d_state, sizeof(IcpDev), hipMemcpyDeviceToHost, g->stream));
+    ER_HIP_TRY(hipMemcpyAsync(g->h_info, g->d_info, kAcc * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    ER_HIP_TRY(hipStreamSynchronize(g->stream));
+    if (rows < row_capacity) {
+      memcpy(totals + (size_t)rows * 29, g->h_info, 29 * sizeof(double));
+      memcpy(fin + (size_t)rows * 16, st.fin, 16 * sizeof(float));
+      memcpy(delta + (size_t)rows * 16, st.delta, 16 * sizeof(float));
+      state[3 * rows] = st.iter;
+      state[3 * rows + 1] = st.done;
+      state[3 * rows + 2] = st.conv;
+      prev_mse[rows] = st.prev_mse;
+    }
+    rows++;
+  }
+  *n_rows = rows;
+  memcpy(out, st.fin, 16 * sizeof(float));
+  if (iterations) *iterations = st.iter;
+  if (converged) *converged = st.conv ? 1 : 0;
+  return 0;
 }
 
 int er_ransac_fitness_batch(er_cloud_t src, er_cloud_t tgt, int n_hyp, const float* M, float corr_dist_threshold, int* inliers,

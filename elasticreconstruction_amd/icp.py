@@ -131,6 +131,25 @@ def icp_align(src, tgt, guess, max_dist=0.03, max_iter=20, eps=1e-6, stop_rule=0
     return out.reshape(4, 4), it.value, bool(cv.value), (fit.value if want_fitness else None)
 
 
+def icp_align_trace(src, tgt, guess, max_dist=0.03, max_iter=20, eps=1e-6, stop_rule=0, pts=1, capacity=64):
+    """er_icp_align_trace (test hook): icp_align with one iteration per host visit.  Returns dict(totals float64 [rows, 29], fin / delta
+    float32 [rows, 4, 4], iter / done / conv int [rows], prev_mse float64 [rows], fx_scale float64 [29], n_rows, T, iterations, converged);
+    rows = min(n_rows, capacity)."""
+    g = np.ascontiguousarray(guess, np.float32).reshape(16)
+    cap = int(capacity)
+    tot, fin, dlt = np.zeros((cap, 29), np.float64), np.zeros((cap, 16), np.float32), np.zeros((cap, 16), np.float32)
+    state, mse, fx = np.zeros((cap, 3), np.int32), np.zeros(cap, np.float64), np.zeros(29, np.float64)
+    out = np.empty(16, np.float32)
+    rows, it, cv = C.c_int(0), C.c_int(0), C.c_int(0)
+    _ffi.check(src._lib.er_icp_align_trace(src._h, tgt._h, _ffi.ptr(g), float(max_dist), int(max_iter), float(eps), int(stop_rule), int(pts), cap,
+                                           _ffi.ptr(tot), _ffi.ptr(fin), _ffi.ptr(dlt), _ffi.ptr(state), _ffi.ptr(mse), _ffi.ptr(fx), C.byref(rows),
+                                           _ffi.ptr(out), C.byref(it), C.byref(cv)), "er_icp_align_trace")
+    r = min(rows.value, cap)
+    return dict(totals=tot[:r], fin=fin[:r].reshape(r, 4, 4), delta=dlt[:r].reshape(r, 4, 4), iter=state[:r, 0].copy(), done=state[:r, 1].copy(),
+                conv=state[:r, 2].copy(), prev_mse=mse[:r], fx_scale=fx, n_rows=rows.value, T=out.reshape(4, 4), iterations=it.value,
+                converged=bool(cv.value))
+
+
 def find_correspondence(src, tgt, T, dist, normal_cos=0.8660, want_info=False):
     """FindCorrespondence (CorresApp.cpp:144-161,186-208).  Returns (pairs int32 [m,2] = (tgt idx, src idx), info 6x6 or None)."""
     Tm = np.ascontiguousarray(T, np.float64).reshape(16)

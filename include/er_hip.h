@@ -369,6 +369,17 @@ int er_find_correspondence(er_cloud_t src, er_cloud_t tgt, const double T[16], d
  * Internally a whole group of pairs runs through every stage in one launch; the ICP loop's solve and stop rule stay on the device.
  * The single-pair functions above are the n == 1 case of these.  Clouds are immutable: any number of host threads
  * may use the same cloud concurrently (each call borrows its workspaces from a per-device pool). */
+/* Test hook (tests/test_icp_shapes_gpu.py): er_icp_align for one pair with ONE iteration per host visit -- the same kernels, solve and stop rule
+ * -- and what every iteration computed.  pts = slices of 256 source points per workgroup, 1..2 (the library's own choice depends on the size of
+ * the list); anything else is refused.  Row r (r < row_capacity; *n_rows = rows the loop produced, which may exceed the capacity) holds, after
+ * iteration r's decision: totals[29 r ..] the 29 sums exactly as the decision received them (0..20 upper triangle of A^T A row by row, 21..26
+ * A^T b, 27 sum of squared distances, 28 correspondence count), fin / delta [16 r ..] the accumulated transform and the last increment,
+ * state[3 r ..] = {iterations so far, done, converged}, prev_mse[r].  fx_scale[29] (nullable): the pair's fixed-point scales.  out, iterations,
+ * converged as er_icp_align returns them, bit for bit. */
+int er_icp_align_trace(er_cloud_t src, er_cloud_t tgt, const float guess[16], double max_dist, int max_iter, double transformation_epsilon,
+                       int stop_rule, int pts, int row_capacity, double* totals, float* fin, float* delta, int* state, double* prev_mse,
+                       double* fx_scale, int* n_rows, float out[16], int* iterations, int* converged);
+
 int er_icp_count_inliers_batch(int n, const er_cloud_t* src, const er_cloud_t* tgt, const double* T, double max_dist, int* counts);
 int er_icp_align_batch(int n, const er_cloud_t* src, const er_cloud_t* tgt, const float* guess, double max_dist, int max_iter,
                        double transformation_epsilon, int stop_rule, float* out, int* iterations, int* converged,
