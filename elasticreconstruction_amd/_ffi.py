@@ -19,6 +19,7 @@ SYMBOLS = [
     "er_tsdf_unit_count", "er_tsdf_unit_keys", "er_tsdf_read_unit", "er_tsdf_sum_weight",
     "er_tsdf_extract_world", "er_tsdf_extract_surface", "er_tsdf_extract_oriented", "er_tsdf_extract_mesh", "er_mc_table", "er_tsdf_extract_mesh_indexed", "er_tsdf_import_world", "er_raycast_params_default", "er_tsdf_raycast", "er_tsdf_raycast_batch", "er_tsdf_export_weighted", "er_tsdf_import_weighted",
     "er_tsdf_export_raw", "er_tsdf_import_raw",
+    "er_tsdf_color_enable", "er_tsdf_read_unit_color", "er_tsdf_write_unit_color", "er_tsdf_color_frames", "er_tsdf_reproject_color", "er_tsdf_sample_colors",
     "er_tsdf_band_sizes", "er_tsdf_export_band", "er_tsdf_merge_band", "er_tsdf_import_band", "er_tsdf_drop_units",
     "er_tsdf_set_profiling", "er_tsdf_get_profile",
     "er_comm_unique_id", "er_comm_create", "er_comm_create_local", "er_comm_create_loopback", "er_comm_destroy", "er_comm_rank", "er_comm_world",
@@ -148,6 +149,13 @@ def lib():
         L.er_frag_build.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]
         L.er_frag_count.argtypes = [vp, ip]
         L.er_frag_read.argtypes = [vp, C.c_int, vp, vp, C.c_long, C.POINTER(C.c_long)]
+    if hasattr(L, "er_tsdf_color_enable"):                      # (absent from an older build selected with ER_HIP_LIB)
+        L.er_tsdf_color_enable.argtypes = [vp]
+        L.er_tsdf_read_unit_color.argtypes = [vp, C.c_int, vp]
+        L.er_tsdf_write_unit_color.argtypes = [vp, C.c_int, vp]
+        L.er_tsdf_color_frames.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.POINTER(ErWarp), vp]
+        L.er_tsdf_sample_colors.argtypes = [vp, vp, C.c_long, vp, vp]
+        L.er_tsdf_reproject_color.argtypes = [vp, vp, vp, vp, C.c_int, C.c_float, vp, vp]
     L.er_request_hw_queues.argtypes = [C.c_int]
     L.er_tsdf_export_weighted.argtypes = [vp, vp, C.c_int, vp]
     L.er_tsdf_import_weighted.argtypes = [vp, vp, C.c_int, vp]

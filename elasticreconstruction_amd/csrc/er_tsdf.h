@@ -184,6 +184,12 @@ struct er_tsdf_s {
   std::vector<int> dropped;                         // sorted
   void* band_scratch = nullptr;
   size_t band_scratch_cap = 0;
+  // colour (er_tsdf_color.hip): per voxel two 64-bit words (r | g << 32), (b | n << 32) = uint32 r_sum, g_sum, b_sum, n; indexed like the pool, by the
+  // unit's slot.  nullptr until er_tsdf_color_enable: a volume that never enables colour allocates nothing.  color_scratch: the grow-only device
+  // staging of the colour calls' inputs (frames, points), their own so that no pre-pass buffer is shared.
+  unsigned long long* color = nullptr;
+  void* color_scratch = nullptr;
+  size_t color_scratch_cap = 0;
 };
 
 // ---- er_tsdf.hip: host functions the other files call (hidden: not part of the library's interface) ----
@@ -194,4 +200,10 @@ __attribute__((visibility("hidden"))) int check_flags(er_tsdf_t h);
 __attribute__((visibility("hidden"))) int resolve_slots(er_tsdf_t h, const int* keys_host, int n, bool allocate);
 // The units this GPU holds (without the ones handed to their owner), in ascending key order: keys and pool slots.  Calls check_flags.
 __attribute__((visibility("hidden"))) int sorted_units(er_tsdf_t h, std::vector<int>& keys, std::vector<int>& slots);
+// One frame (RA.n_frames == 1) reprojected on stream X into RA.zbuf and on into z_dev, 16-bit depth; zbuf, lastzero, zfix and the flag words are
+// left as they were found (all-empty / 0).
+__attribute__((visibility("hidden"))) int reproject_single(er_tsdf_t h, const ReprojArgs& RA, uint16_t* z_dev, hipStream_t X);
+// ---- er_tsdf_color.hip ----
+// Zeroes the colour accumulators of the n units whose slots stand in h->slot_scratch (behind resolve_slots, on h->stream); nothing without colour.
+__attribute__((visibility("hidden"))) int color_zero_slots(er_tsdf_t h, int n);
 }  // namespace er_tsdf_k

@@ -648,7 +648,7 @@ int er_tsdf_destroy(er_tsdf_t h) {
     if (h->aux_stream[a]) (void)hipStreamSynchronize(h->aux_stream[a]);
   std::vector<void*> ptrs = {h->pool, h->ht_key, h->ht_slot, h->unit_key, h->counters, h->stats, h->lambda, h->T12, h->seg12, h->madj12,
                              h->grid_index, h->dsum, h->ctr_dev[0], h->ctr_dev[1], h->key_scratch,
-                             h->slot_scratch, h->band_scratch};
+                             h->slot_scratch, h->band_scratch, h->color, h->color_scratch};
   for (int q = 0; q < kDepth; q++)
     for (void* x : {(void*)h->ht_mask[q], (void*)h->batch[q], (void*)h->scaled[q], (void*)h->depth_stage[q], h->dstage[q], (void*)h->tile_max[q], (void*)h->tile_lo[q], (void*)h->tile_lo_fine[q],
                     (void*)h->plan_rec[q], (void*)h->plan[q]})
@@ -878,6 +878,7 @@ int er_tsdf_reset(er_tsdf_t h) {
   n = std::min(std::max(n, 0), h->max_units);
   hipStream_t s = h->stream;
   if (n > 0) ER_HIP_TRY(hipMemsetAsync(h->pool, 0, (size_t)n * er::kUnitVox * sizeof(float2), s));   // only the units ever handed out
+  if (n > 0 && h->color) ER_HIP_TRY(hipMemsetAsync(h->color, 0, (size_t)n * er::kUnitVox * 16, s));
   ER_HIP_TRY(hipMemsetAsync(h->ht_key, 0xFF, (size_t)h->ht_cap * sizeof(int), s));
   ER_HIP_TRY(hipMemsetAsync(h->ht_slot, 0xFF, (size_t)h->ht_cap * sizeof(int), s));
   for (int q = 0; q < kDepth; q++) ER_HIP_TRY(hipMemsetAsync(h->ht_mask[q], 0, (size_t)h->ht_cap * sizeof(unsigned long long), s));
@@ -999,3 +1000,19 @@ int er_tsdf_get_profile(er_tsdf_t h, double* integrate_ms_total, long* integrate
 
 
 }  // extern "C"
+
+namespace er_tsdf_k {
+
+// er_tsdf_reproject's device part for the colour calls (er_tsdf_color.hip): frame 0 of RA through k_reproject_scatter and k_reproject_fix into
+// RA.zbuf, then k_zbuf_to_depth into z_dev, which re-arms the three buffers; the flag words are cleared behind it.
+int reproject_single(er_tsdf_t h, const ReprojArgs& RA, uint16_t* z_dev, hipStream_t X) {
+  if (launch_reproject(h, RA, 1, X)) return 1;
+  const long total = (long)RA.cols * RA.rows;
+  hipLaunchKernelGGL(k_zbuf_to_depth, dim3((int)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, X, RA.zbuf, z_dev, total, RA.lastzero, RA.zfix,
+                     RA.zero_flag);
+  ER_HIP_TRY(hipGetLastError());
+  ER_HIP_TRY(hipMemsetAsync(RA.zero_flag, 0, 2 * sizeof(int), X));
+  return 0;
+}
+
+}  // namespace er_tsdf_k

@@ -383,6 +383,7 @@ int er_tsdf_drop_units(er_tsdf_t h, const int* keys_host, int n) {
   if (resolve_slots(h, keys_host, n, false)) return 1;
   hipLaunchKernelGGL(k_zero_units, dim3(kUnitVox / 2 / 256, n), dim3(256), 0, h->stream, h->pool, h->slot_scratch);
   ER_HIP_TRY(hipGetLastError());
+  if (color_zero_slots(h, n)) return 1;
   ER_HIP_TRY(hipStreamSynchronize(h->stream));
   h->dropped.insert(h->dropped.end(), keys_host, keys_host + n);
   std::sort(h->dropped.begin(), h->dropped.end());

@@ -24,6 +24,11 @@
 //                         (er_tsdf_extract_oriented, inside the cube [0, length)); single-GPU runs only
 //   --save_mesh <file.ply>   after the run also write the volume's marching-cubes mesh: indexed, with normals, binary PLY
 //                         (er_tsdf_extract_mesh_indexed; bin/MeshOutput makes the same kind of file from world.pcd); single-GPU runs only
+//   --color_raw <file> | --color_list <txt>   the colour stream registered to the depth stream: raw 640x480x3 bytes per frame,
+//                         or one 8-bit RGB / RGBA PNG per line, line i = frame i, inflated ahead like the depth PNGs.  The colour of each
+//                         batch of frames is splatted into the volume after the batch is integrated (er_tsdf_color_frames) and --save_mesh
+//                         then writes a coloured PLY (er_tsdf_sample_colors).  Refused: with --gpus N > 1, without --save_mesh, and a
+//                         colour source whose frame count or image size differs from the depth source's
 //   --force_merge         with --gpus 1: run the frame-split merge anyway (exercises the RCCL path on a 1-GPU box)
 //
 // Control flow = CIntegrateApp::StartMainLoop/Execute: 1-based frame ids, frame_ == -1 skips a frame,
@@ -74,55 +79,71 @@ int print_help() {
   std::cout << "    --device <gpu> (0)  --max_units <n> (2048)  --batch <frames> (64)" << std::endl;
   std::cout << "    --save_fragment <pcd_file> [--fragment_length <m> (3.0)] : also write the volume's surface points with normals, cloud_bin-style (single GPU only)" << std::endl;
   std::cout << "    --save_mesh <ply_file>          : also write the volume's marching-cubes mesh, indexed, with normals, binary PLY (single GPU only)" << std::endl;
+  std::cout << "    --color_raw <raw_file> | --color_list <txt> : 640x480x3 bytes per frame | 8-bit RGB PNG per line; needs --save_mesh, which then writes colours (single GPU only)" << std::endl;
   std::cout << "    --gpus <N> (1)  --shard frame|unit (frame: frame blocks + the merge by unit owner over RCCL; unit: bit-exact, no collective)  --merge_root <g>  --force_merge" << std::endl;
   return 0;
 }
 
-struct DepthSource {
-  virtual ~DepthSource() {}
-  virtual bool next(std::vector<uint16_t>& frame, int& frame_id) = 0;
+// A stream of frames of P: uint16_t = depth (one element a pixel), uint8_t = colour (three a pixel).
+template <typename P>
+struct FrameSource {
+  virtual ~FrameSource() {}
+  virtual bool next(std::vector<P>& frame, int& frame_id) = 0;
 };
+using DepthSource = FrameSource<uint16_t>;
+using ColorSource = FrameSource<uint8_t>;
 
-struct RawStream : DepthSource {
+// px = elements of P per frame
+template <typename P>
+struct RawStreamT : FrameSource<P> {
   FILE* f = nullptr;
   int id = 0;
   size_t px;
-  RawStream(const std::string& p, size_t pixels, long first_id = 1) : px(pixels) {
+  RawStreamT(const std::string& p, size_t elements, long first_id = 1) : px(elements) {
     f = fopen(p.c_str(), "rb");
-    if (f && first_id > 1) { fseek(f, (long)((first_id - 1) * (long)(px * sizeof(uint16_t))), SEEK_SET); id = (int)first_id - 1; }
+    if (f && first_id > 1) { fseek(f, (long)((first_id - 1) * (long)(px * sizeof(P))), SEEK_SET); id = (int)first_id - 1; }
   }
-  static long count(const std::string& p, size_t pixels) {
+  static long bytes(const std::string& p) {
     FILE* g = fopen(p.c_str(), "rb");
-    if (!g) return 0;
+    if (!g) return -1;
     fseek(g, 0, SEEK_END);
-    const long n = ftell(g) / (long)(pixels * sizeof(uint16_t));
+    const long n = ftell(g);
     fclose(g);
     return n;
   }
-  ~RawStream() { if (f) fclose(f); }
-  bool next(std::vector<uint16_t>& frame, int& frame_id) override {
+  static long count(const std::string& p, size_t elements) { return std::max(0L, bytes(p)) / (long)(elements * sizeof(P)); }
+  ~RawStreamT() override { if (f) fclose(f); }
+  bool next(std::vector<P>& frame, int& frame_id) override {
     frame.resize(px);
-    if (!f || fread(frame.data(), sizeof(uint16_t), px, f) != px) return false;
+    if (!f || fread(frame.data(), sizeof(P), px, f) != px) return false;
     frame_id = ++id;
     return true;
   }
 };
+using RawStream = RawStreamT<uint16_t>;
+
+inline bool load_png_frame(const std::string& p, int& w, int& h, std::vector<uint16_t>& px) { return erfmt::load_png16(p, w, h, px); }
+inline bool load_png_frame(const std::string& p, int& w, int& h, std::vector<uint8_t>& px) { return erfmt::load_png_rgb8(p, w, h, px); }
+inline const char* png_kind(const uint16_t*) { return "16-bit depth PNG"; }
+inline const char* png_kind(const uint8_t*) { return "8-bit RGB PNG"; }
 
 // 16-bit PNG list.  Inflating one 640 x 480 frame takes a host core 3-5 ms -- two orders of magnitude more than the GPU needs to integrate it -- so the
 // files are decoded AHEAD by a few host threads (--decode_threads): thread-safe claim of the next file, a ring of finished frames, next()
-// hands them out strictly in list order (the frame ids and their order are the reference's, IntegrateApp.cpp:190-226).
-struct PngList : DepthSource {
+// hands them out strictly in list order (the frame ids and their order are the reference's, IntegrateApp.cpp:190-226).  The colour list
+// (--color_list, P = uint8_t) is decoded by threads of the same kind.
+template <typename P>
+struct PngListT : FrameSource<P> {
   std::vector<std::string> files;
   size_t at = 0;
   int cols, rows, nthreads;
-  struct Slot { std::vector<uint16_t> px; long idx = -1; bool ready = false, ok = false; };
+  struct Slot { std::vector<P> px; long idx = -1; bool ready = false, ok = false; };
   std::vector<Slot> ring;
   std::vector<std::thread> workers;
   std::mutex m;
   std::condition_variable cv_ready, cv_free;
   size_t next_claim = 0;
   bool stop = false, started = false;
-  PngList(const std::string& list, int c, int r, long first_id = 1, int threads = 8) : cols(c), rows(r), nthreads(std::max(1, std::min(threads, 64))) {
+  PngListT(const std::string& list, int c, int r, long first_id = 1, int threads = 8) : cols(c), rows(r), nthreads(std::max(1, std::min(threads, 64))) {
     at = first_id > 1 ? (size_t)(first_id - 1) : 0;
     FILE* f = fopen(list.c_str(), "r");
     if (!f) return;
@@ -138,7 +159,7 @@ struct PngList : DepthSource {
     }
     fclose(f);
   }
-  ~PngList() override {
+  ~PngListT() override {
     {
       std::lock_guard<std::mutex> lk(m);
       stop = true;
@@ -152,7 +173,7 @@ struct PngList : DepthSource {
     ring.resize((size_t)nthreads * 2);
     for (int t = 0; t < nthreads; t++)
       workers.emplace_back([this] {
-        std::vector<uint16_t> px;
+        std::vector<P> px;
         for (;;) {
           size_t i;
           {
@@ -164,7 +185,7 @@ struct PngList : DepthSource {
             if (next_claim >= files.size()) cv_free.notify_all();   // (the others can leave)
           }
           int w = 0, h = 0;
-          const bool ok = erfmt::load_png16(files[i], w, h, px) && w == cols && h == rows;
+          const bool ok = load_png_frame(files[i], w, h, px) && w == cols && h == rows;
           {
             std::lock_guard<std::mutex> lk(m);
             Slot& s = ring[i % ring.size()];
@@ -176,7 +197,7 @@ struct PngList : DepthSource {
         }
       });
   }
-  bool next(std::vector<uint16_t>& frame, int& frame_id) override {
+  bool next(std::vector<P>& frame, int& frame_id) override {
     if (at >= files.size()) return false;
     if (!started) start();
     bool ok;
@@ -191,13 +212,14 @@ struct PngList : DepthSource {
     }
     cv_free.notify_all();
     if (!ok) {
-      fprintf(stderr, "Cannot read %dx%d 16-bit depth PNG %s\n", cols, rows, files[at].c_str());
+      fprintf(stderr, "Cannot read %dx%d %s %s\n", cols, rows, png_kind((const P*)nullptr), files[at].c_str());
       return false;
     }
     frame_id = (int)++at;
     return true;
   }
 };
+using PngList = PngListT<uint16_t>;
 
 struct App {
   // CIntegrateApp members (IntegrateApp.h:36-77), same names
@@ -216,6 +238,8 @@ struct App {
   int rank_ = 0, gpus_ = 1;                                            // this worker / number of workers (--gpus)
   bool unit_shard_ = false;                                            // --shard unit
   std::vector<uint16_t> q_depth_;
+  bool color_ = false;                                                 // --color_raw / --color_list: q_rgb_ holds the colour of the queued frames
+  std::vector<uint8_t> q_rgb_;
   std::vector<double> q_T_, q_seg_, q_madj_;
   std::vector<int> q_gi_;
   long frames_integrated_ = 0;
@@ -255,6 +279,10 @@ struct App {
       fprintf(stderr, "Integrate: %s\n", er_last_error());
       return false;
     }
+    if (color_ && er_tsdf_color_enable(volume_) != 0) {
+      fprintf(stderr, "Integrate: %s\n", er_last_error());
+      return false;
+    }
     return true;
   }
 
@@ -277,8 +305,13 @@ struct App {
       fprintf(stderr, "Integrate: %s\n", er_last_error());
       return false;
     }
+    // the colour of the batch, behind its integration: the units its pixels fall into exist now
+    if (color_ && er_tsdf_color_frames(volume_, n, q_depth_.data(), q_rgb_.data(), 0, q_T_.data(), wp, nullptr) != 0) {
+      fprintf(stderr, "Integrate: %s\n", er_last_error());
+      return false;
+    }
     frames_integrated_ += n;
-    q_depth_.clear(); q_T_.clear(); q_seg_.clear(); q_madj_.clear(); q_gi_.clear();
+    q_depth_.clear(); q_rgb_.clear(); q_T_.clear(); q_seg_.clear(); q_madj_.clear(); q_gi_.clear();
     return CheckStatus(false);
   }
 
@@ -298,7 +331,7 @@ struct App {
     return true;
   }
 
-  bool Execute(const std::vector<uint16_t>& depth) {                   // IntegrateApp.cpp:190-226
+  bool Execute(const std::vector<uint16_t>& depth, const std::vector<uint8_t>* rgb = nullptr) {   // IntegrateApp.cpp:190-226
     if (frame_id_ - 1 < 0 || frame_id_ - 1 >= (int)traj_.size()) {    // the reference reads out of bounds here
       exit_ = true;
       return true;
@@ -329,6 +362,7 @@ struct App {
       q_gi_.push_back(0);
     }
     q_depth_.insert(q_depth_.end(), depth.begin(), depth.end());
+    if (color_) q_rgb_.insert(q_rgb_.end(), rgb->begin(), rgb->end());
     q_T_.insert(q_T_.end(), T, T + 16);
     if ((int)q_gi_.size() >= batch_) return Flush();
     return true;
@@ -378,7 +412,11 @@ struct App {
     std::vector<int> tris((size_t)nt * 3);
     if (nv > 0 && er_tsdf_extract_mesh_indexed(volume_, verts.data(), nrm.data(), nv, tris.data(), nt, &nv, &nt) != 0) { fprintf(stderr, "Integrate: %s\n", er_last_error()); return false; }
     static const float none[4] = {0.f, 0.f, 0.f, 0.f};                 // (an empty mesh still declares nx ny nz)
-    if (!erfmt::save_ply(filename, verts.data(), 4, nv > 0 ? nrm.data() : none, 4, (size_t)nv, tris.data(), (size_t)nt, true)) { fprintf(stderr, "Integrate: cannot write %s\n", filename.c_str()); return false; }
+    std::vector<uint8_t> rgba((size_t)nv * 4 + 4);                      // with colour: er_tsdf_sample_colors at the vertices
+    long levels[2] = {0, 0};
+    if (color_ && er_tsdf_sample_colors(volume_, verts.data(), nv, rgba.data(), levels) != 0) { fprintf(stderr, "Integrate: %s\n", er_last_error()); return false; }
+    if (color_) printf("%ld vertices coloured from their nearest voxel, %ld from its neighbourhood, %ld left without colour.\n", levels[0], levels[1], nv - levels[0] - levels[1]);
+    if (!erfmt::save_ply(filename, verts.data(), 4, nv > 0 ? nrm.data() : none, 4, (size_t)nv, tris.data(), (size_t)nt, true, color_ ? rgba.data() : nullptr)) { fprintf(stderr, "Integrate: cannot write %s\n", filename.c_str()); return false; }
     printf("%ld mesh vertices and %ld triangles have been written.\n", nv, nt);
     return true;
   }
@@ -482,6 +520,10 @@ int main(int argc, char* argv[]) {
   parse_argument(argc, argv, "--fragment_length", fragment_length);
   std::string mesh_file;                                                // --save_mesh <file.ply>: the indexed mesh of the volume
   parse_argument(argc, argv, "--save_mesh", mesh_file);
+  std::string color_raw, color_list;                                    // --color_raw <file> | --color_list <txt>: the colour stream
+  parse_argument(argc, argv, "--color_raw", color_raw);
+  parse_argument(argc, argv, "--color_list", color_list);
+  const bool color = !color_raw.empty() || !color_list.empty();
   const bool force_merge = find_switch(argc, argv, "--force_merge");
   int merge_root = ER_MERGE_DISTRIBUTED;                                // --merge_root <g>: gather the merged volume on worker g before SaveWorld
   parse_argument(argc, argv, "--merge_root", merge_root);
@@ -494,6 +536,7 @@ int main(int argc, char* argv[]) {
   if (gpus < 1) gpus = 1;
   if (shard != "frame" && shard != "unit") { fprintf(stderr, "Integrate: --shard must be frame or unit\n"); return 1; }
   if (merge_root != ER_MERGE_DISTRIBUTED && (merge_root < 0 || merge_root >= gpus)) { fprintf(stderr, "Integrate: --merge_root must name one of the %d workers\n", gpus); return 1; }
+  if (color && gpus > 1) { fprintf(stderr, "Integrate: colour is not carried across GPUs; --color_raw / --color_list are not available with --gpus %d\n", gpus); return 1; }
   if (!fragment_file.empty() && gpus > 1) {
     fprintf(stderr, "Integrate: --save_fragment needs the whole volume on one GPU; it is not available with --gpus %d\n", gpus);
     return 1;
@@ -502,6 +545,38 @@ int main(int argc, char* argv[]) {
     fprintf(stderr, "Integrate: --save_mesh needs the whole volume on one GPU; it is not available with --gpus %d\n", gpus);
     return 1;
   }
+  if (color) {
+    if (!color_raw.empty() && !color_list.empty()) { fprintf(stderr, "Integrate: give --color_raw or --color_list, not both\n"); return 1; }
+    if (mesh_file.empty()) { fprintf(stderr, "Integrate: --color_raw / --color_list need --save_mesh (world.pcd has no field for colour)\n"); return 1; }
+    long color_frames = 0;
+    if (!color_raw.empty()) {
+      const long bytes = RawStreamT<uint8_t>::bytes(color_raw);
+      if (bytes < 0) { fprintf(stderr, "Integrate: cannot open the colour source %s\n", color_raw.c_str()); return 1; }
+      if (bytes % (long)(px * 3) != 0) {
+        fprintf(stderr, "Integrate: the colour source %s holds %ld bytes, no whole number of %dx%dx3 frames (another image size?)\n", color_raw.c_str(), bytes, app.cols_, app.rows_);
+        return 1;
+      }
+      color_frames = bytes / (long)(px * 3);
+    } else {
+      PngListT<uint8_t> probe(color_list, app.cols_, app.rows_);
+      color_frames = (long)probe.files.size();
+      int w = 0, h = 0;
+      std::vector<uint8_t> first;
+      if (color_frames > 0 && (!erfmt::load_png_rgb8(probe.files[0], w, h, first) || w != app.cols_ || h != app.rows_)) {
+        fprintf(stderr, "Integrate: the colour source's first image %s is no %dx%d 8-bit RGB PNG\n", probe.files[0].c_str(), app.cols_, app.rows_);
+        return 1;
+      }
+    }
+    if (color_frames != source_frames) {
+      fprintf(stderr, "Integrate: the colour source has %ld frames, the depth source %ld\n", color_frames, source_frames);
+      return 1;
+    }
+    app.color_ = true;
+  }
+  auto open_color = [&](long first_id) -> std::unique_ptr<ColorSource> {
+    if (!color_list.empty()) return std::unique_ptr<ColorSource>(new PngListT<uint8_t>(color_list, app.cols_, app.rows_, first_id, decode_threads));
+    return std::unique_ptr<ColorSource>(new RawStreamT<uint8_t>(color_raw, px * 3, first_id));
+  };
   const bool unit_shard = shard == "unit";
   if (same_device && !unit_shard && gpus > 16) { fprintf(stderr, "Integrate: --same_device --shard frame takes at most 16 workers\n"); return 1; }
   if (!same_device && gpus > 1 && er_device_count() > 0 && app.device_ + gpus > er_device_count()) {
@@ -549,13 +624,20 @@ int main(int argc, char* argv[]) {
       hi_id = first + hi - 1;
     }
     std::unique_ptr<DepthSource> source = open_source(lo_id);
+    std::unique_ptr<ColorSource> csource = color ? open_color(lo_id) : std::unique_ptr<ColorSource>();
     std::vector<uint16_t> frame;
+    std::vector<uint8_t> cframe;
     while (!w.exit_) {
-      int id = 0;
+      int id = 0, cid = 0;
       if (!source->next(frame, id)) break;                             // end of stream (reference: ten timeouts, :125)
       if (id > hi_id) break;
+      if (color && (!csource->next(cframe, cid) || cid != id)) {       // line i / frame i of the colour source goes with depth frame i
+        fprintf(stderr, "Integrate: the colour source ends or fails at frame %d\n", id);
+        wrc[(size_t)g] = 1;
+        break;
+      }
       w.frame_id_ = id;
-      if (!w.Execute(frame)) { wrc[(size_t)g] = 1; break; }
+      if (!w.Execute(frame, color ? &cframe : nullptr)) { wrc[(size_t)g] = 1; break; }
     }
     if (wrc[(size_t)g] == 0 && !w.Flush()) wrc[(size_t)g] = 1;
     if (wrc[(size_t)g] == 0 && (er_tsdf_synchronize(w.volume_) != 0 || !w.CheckStatus(true))) wrc[(size_t)g] = 1;

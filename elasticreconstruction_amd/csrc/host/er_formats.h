@@ -326,17 +326,19 @@ inline bool save_pcd_xyzn(const std::string& path, const float* rows, size_t n) 
 // A triangle mesh as PLY, byte for byte what formats.save_ply writes: verts = nv rows of vstride >= 3 floats (x y z first -- the rows of
 // er_tsdf_extract_mesh_indexed have 4), normals = nullptr or nv rows of nstride >= 3 floats, tris = nt x 3 int32.  A normal with a NaN
 // component is written as 0 0 0 (the ABI's "no normal"; a viewer chokes on NaN).  binary: little-endian float32 rows, then uchar 3 + int32
-// rows; ascii: %.9g floats, one space between columns.
+// rows; ascii: %.9g floats, one space between columns.  colors = nullptr or nv x 4 bytes red green blue alpha (er_tsdf_sample_colors), written as
+// four uchar properties behind the normals: in a binary row the four bytes follow the row's floats, in ascii they are integers.
 inline bool save_ply(const std::string& path, const float* verts, int vstride, const float* normals, int nstride, size_t nv, const int32_t* tris,
-                     size_t nt, bool binary) {
+                     size_t nt, bool binary, const uint8_t* colors = nullptr) {
   FILE* f = fopen(path.c_str(), "wb");
   if (!f) return false;
-  fprintf(f, "ply\nformat %s 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n%s"
+  fprintf(f, "ply\nformat %s 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n%s%s"
              "element face %zu\nproperty list uchar int vertex_indices\nend_header\n",
-          binary ? "binary_little_endian" : "ascii", nv, normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "", nt);
+          binary ? "binary_little_endian" : "ascii", nv, normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "",
+          colors ? "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\n" : "", nt);
   const int k = normals ? 6 : 3;
   std::vector<uint8_t> buf;
-  if (binary) buf.reserve(std::max(nv * (size_t)k * 4, nt * 13));
+  if (binary) buf.reserve(std::max(nv * ((size_t)k * 4 + (colors ? 4 : 0)), nt * 13));
   for (size_t i = 0; i < nv; i++) {
     float r[6] = {verts[i * vstride], verts[i * vstride + 1], verts[i * vstride + 2], 0.f, 0.f, 0.f};
     if (normals) {
@@ -345,8 +347,10 @@ inline bool save_ply(const std::string& path, const float* verts, int vstride, c
     }
     if (binary) {
       buf.insert(buf.end(), (const uint8_t*)r, (const uint8_t*)r + 4 * k);       // (little-endian hosts only, like the PCD writers)
+      if (colors) buf.insert(buf.end(), colors + 4 * i, colors + 4 * i + 4);
     } else {
       for (int c = 0; c < k; c++) fprintf(f, c ? " %.9g" : "%.9g", (double)r[c]);
+      if (colors) fprintf(f, " %d %d %d %d", colors[4 * i], colors[4 * i + 1], colors[4 * i + 2], colors[4 * i + 3]);
       fputc('\n', f);
     }
   }
@@ -497,6 +501,80 @@ inline bool load_png16(const std::string& path, int& w, int& h, std::vector<uint
     }
     for (int x = 0; x < w; x++)
       px[(size_t)y * w + x] = depth == 16 ? (uint16_t)((cur[2 * x] << 8) | cur[2 * x + 1]) : (uint16_t)cur[x];
+    prev.swap(cur);
+  }
+  return true;
+}
+
+// 8-bit colour PNG (the pipeline's colour images): non-interlaced, bit depth 8, colour type 2 (RGB) or 6 (RGBA, the alpha dropped), all five
+// filter types; px = w * h * 3 bytes.  The same bounds on untrusted input as load_png16; everything else is refused.
+inline bool load_png_rgb8(const std::string& path, int& w, int& h, std::vector<uint8_t>& px) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) return false;
+  std::vector<uint8_t> raw;
+  fseek(f, 0, SEEK_END);
+  long sz = ftell(f);
+  fseek(f, 0, SEEK_SET);
+  raw.resize((size_t)(sz > 0 ? sz : 0));
+  if (sz > 0 && fread(raw.data(), 1, (size_t)sz, f) != (size_t)sz) { fclose(f); return false; }
+  fclose(f);
+  static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
+  if (raw.size() < 8 || memcmp(raw.data(), sig, 8) != 0) return false;
+  auto be32 = [&](size_t o) { return ((uint32_t)raw[o] << 24) | ((uint32_t)raw[o + 1] << 16) | ((uint32_t)raw[o + 2] << 8) | raw[o + 3]; };
+  size_t pos = 8;
+  int depth = 0, ctype = 0, interlace = 0;
+  bool ended = false;
+  std::vector<uint8_t> idat;
+  w = h = 0;
+  while (pos + 12 <= raw.size()) {
+    uint32_t len = be32(pos);
+    std::string type((const char*)&raw[pos + 4], 4);
+    if (pos + 12 + (size_t)len > raw.size()) return false;
+    const uint8_t* d = &raw[pos + 8];
+    if (type == "IHDR") {
+      if (len != 13) return false;                                      // untrusted input: a short IHDR would be read past its end
+      const uint32_t uw = be32(pos + 8), uh = be32(pos + 12);
+      if (uw == 0 || uh == 0 || uw > 16384u || uh > 16384u) return false;   // bound the allocation below
+      w = (int)uw;
+      h = (int)uh;
+      depth = d[8]; ctype = d[9]; interlace = d[12];
+    } else if (type == "IDAT") {
+      idat.insert(idat.end(), d, d + len);
+    } else if (type == "IEND") {
+      ended = true;
+      break;
+    }
+    pos += 12 + len;
+  }
+  if (!ended || w <= 0 || h <= 0 || (ctype != 2 && ctype != 6) || interlace != 0 || depth != 8) return false;
+  const size_t bpp = ctype == 6 ? 4 : 3, stride = (size_t)w * bpp;
+  std::vector<uint8_t> img((stride + 1) * (size_t)h);
+  uLongf out_len = (uLongf)img.size();
+  if (uncompress(img.data(), &out_len, idat.data(), (uLong)idat.size()) != Z_OK || out_len != img.size()) return false;
+  px.assign((size_t)w * h * 3, 0);
+  std::vector<uint8_t> prev(stride, 0), cur(stride);
+  for (int y = 0; y < h; y++) {
+    const uint8_t* line = &img[(stride + 1) * (size_t)y];
+    const int ft = line[0];
+    if (ft < 0 || ft > 4) return false;
+    for (size_t i = 0; i < stride; i++) {
+      const int a = i >= bpp ? cur[i - bpp] : 0, b = prev[i], c = i >= bpp ? prev[i - bpp] : 0;
+      int v = line[1 + i];
+      switch (ft) {
+        case 0: break;
+        case 1: v += a; break;
+        case 2: v += b; break;
+        case 3: v += (a + b) / 2; break;
+        default: {
+          const int p = a + b - c, pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
+          v += (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
+          break;
+        }
+      }
+      cur[i] = (uint8_t)v;
+    }
+    for (int x = 0; x < w; x++)
+      for (int ch = 0; ch < 3; ch++) px[((size_t)y * w + x) * 3 + ch] = cur[(size_t)x * bpp + ch];
     prev.swap(cur);
   }
   return true;

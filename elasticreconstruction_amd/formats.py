@@ -349,19 +349,22 @@ def save_pcd_xyzn(path, xyz, normals, binary=True):
             f.write(s.getvalue().encode("ascii"))
 
 
-def _ply_header(n, m, normals, binary):
-    return ("ply\nformat %s 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n%s"
+def _ply_header(n, m, normals, binary, colors=False):
+    return ("ply\nformat %s 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n%s%s"
             "element face %d\nproperty list uchar int vertex_indices\nend_header\n"
             % ("binary_little_endian" if binary else "ascii", n,
-               "property float nx\nproperty float ny\nproperty float nz\n" if normals else "", m))
+               "property float nx\nproperty float ny\nproperty float nz\n" if normals else "",
+               "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\n" if colors else "", m))
 
 
-def save_ply(path, verts, tris, normals=None, binary=True):
+def save_ply(path, verts, tris, normals=None, binary=True, colors=None):
     """A triangle mesh as PLY (what kinfu's mesh output leaves for a viewer; csrc/host/er_formats.h's save_ply writes the same bytes).
     verts: float32[n, 3] -- or [n, 4], TSDFVolume.extract_indexed_mesh's x y z axis rows: the fourth column is not written; tris: int32[m, 3];
     normals: float32[n, 3] or None.  A normal with a NaN component is written as 0 0 0: the ABI keeps the NaN ("no normal"), a viewer chokes
-    on it, and a zero vector is what mesh tools take for "unset".  binary: little-endian float32 / uchar 3 + int32 rows; ascii: %.9g floats,
-    one space between columns."""
+    on it, and a zero vector is what mesh tools take for "unset".  colors: uint8[n, 4] = red green blue alpha (TSDFVolume.sample_colors) or None,
+    written as four uchar properties behind the normals.  binary: little-endian float32 / uchar 3 + int32 rows, a vertex row with colours the
+    packed floats followed by its four bytes; ascii: %.9g floats, the colours as integers, one space between columns.  With colors = None the
+    file is byte for byte what it was before colour existed."""
     v = np.asarray(verts, np.float32)
     if v.ndim != 2 or v.shape[1] not in (3, 4):
         raise ValueError("save_ply: verts must be [n, 3] or [n, 4], not %s" % (v.shape,))
@@ -375,31 +378,46 @@ def save_ply(path, verts, tris, normals=None, binary=True):
         nr[np.isnan(nr).any(axis=1)] = 0.0
         cols.append(nr)
     a = np.ascontiguousarray(np.concatenate(cols, axis=1))
+    c = None
+    if colors is not None:
+        c = np.ascontiguousarray(colors, dtype=np.uint8).reshape(-1, 4)
+        if c.shape[0] != v.shape[0]:
+            raise ValueError("save_ply: %d colours for %d vertices" % (c.shape[0], v.shape[0]))
     with open(path, "wb") as f:
-        f.write(_ply_header(v.shape[0], t.shape[0], normals is not None, binary).encode("ascii"))
+        f.write(_ply_header(v.shape[0], t.shape[0], normals is not None, binary, c is not None).encode("ascii"))
         if binary:
-            f.write(a.astype("<f4").tobytes())
+            if c is None:
+                f.write(a.astype("<f4").tobytes())
+            else:
+                row = np.empty(v.shape[0], np.dtype([("f", "<f4", (a.shape[1],)), ("c", "u1", (4,))]))
+                row["f"] = a
+                row["c"] = c
+                f.write(row.tobytes())
             face = np.empty(t.shape[0], np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
             face["n"] = 3
             face["i"] = t
             f.write(face.tobytes())
         else:
             s = io.StringIO()
-            np.savetxt(s, a, fmt="%.9g")
+            if c is None:
+                np.savetxt(s, a, fmt="%.9g")
+            else:
+                np.savetxt(s, np.concatenate([a.astype(np.float64), c.astype(np.float64)], axis=1), fmt=["%.9g"] * a.shape[1] + ["%d"] * 4)
             np.savetxt(s, np.concatenate([np.full((t.shape[0], 1), 3, np.int32), t], axis=1), fmt="%d")
             f.write(s.getvalue().encode("ascii"))
 
 
-def load_ply(path):
-    """Reads what save_ply writes (and any PLY of that shape: float x y z, optionally nx ny nz, faces as list uchar int, triangles only).
-    Returns (verts float32[n, 3], tris int32[m, 3], normals float32[n, 3] or None)."""
+_PLY_COLOR_PROPS = ["red", "green", "blue", "alpha"]
+
+
+def _load_ply(path):
     with open(path, "rb") as f:
         raw = f.read()
     end = raw.index(b"end_header\n") + len(b"end_header\n")
     lines = raw[:end].decode("ascii").split("\n")
     if lines[0] != "ply":
         raise ValueError("%s is not a PLY file" % path)
-    mode, n, m, props, cur = None, 0, 0, [], None
+    mode, n, m, props, types, cur = None, 0, 0, [], [], None
     for line in lines[1:]:
         w = line.split()
         if not w or w[0] == "comment":
@@ -413,30 +431,53 @@ def load_ply(path):
             elif cur == "face":
                 m = int(w[2])
         elif w[0] == "property" and cur == "vertex":
-            if w[1] != "float":
-                raise ValueError("load_ply: vertex property %s is not a float" % w[-1])
+            if w[1] != ("uchar" if w[2] in _PLY_COLOR_PROPS else "float"):
+                raise ValueError("load_ply: vertex property %s is not a %s" % (w[-1], "uchar" if w[2] in _PLY_COLOR_PROPS else "float"))
             props.append(w[2])
         elif w[0] == "property" and cur == "face" and w[1:4] != ["list", "uchar", "int"]:
             raise ValueError("load_ply: faces must be 'list uchar int'")
-    if props not in (["x", "y", "z"], ["x", "y", "z", "nx", "ny", "nz"]):
+    has_c = props[-4:] == _PLY_COLOR_PROPS
+    fprops = props[:-4] if has_c else props
+    if fprops not in (["x", "y", "z"], ["x", "y", "z", "nx", "ny", "nz"]):
         raise ValueError("load_ply: vertex properties %s" % props)
-    k = len(props)
+    k = len(fprops)
+    c = None
     if mode == "binary_little_endian":
-        a = np.frombuffer(raw, "<f4", n * k, end).reshape(n, k).astype(np.float32)
-        face = np.frombuffer(raw, np.dtype([("n", "u1"), ("i", "<i4", (3,))]), m, end + 4 * n * k)
+        if has_c:
+            row = np.frombuffer(raw, np.dtype([("f", "<f4", (k,)), ("c", "u1", (4,))]), n, end)
+            a, c, vbytes = row["f"].astype(np.float32).reshape(n, k), np.ascontiguousarray(row["c"]).reshape(n, 4), (4 * k + 4) * n
+        else:
+            a, vbytes = np.frombuffer(raw, "<f4", n * k, end).reshape(n, k).astype(np.float32), 4 * n * k
+        face = np.frombuffer(raw, np.dtype([("n", "u1"), ("i", "<i4", (3,))]), m, end + vbytes)
         if m and (face["n"] != 3).any():
             raise ValueError("load_ply: a face is not a triangle")
         t = face["i"].astype(np.int32).reshape(m, 3)
     elif mode == "ascii":
         tok = raw[end:].decode("ascii").split()
-        a = np.array(tok[:n * k], dtype=np.float32).reshape(n, k)
-        ft = np.array(tok[n * k:n * k + 4 * m], dtype=np.int64).reshape(m, 4)
+        kk = k + (4 if has_c else 0)
+        rows = np.array(tok[:n * kk], dtype=object).reshape(n, kk)
+        a = rows[:, :k].astype(np.float32).reshape(n, k)
+        if has_c:
+            c = rows[:, k:].astype(np.int64).astype(np.uint8).reshape(n, 4)
+        ft = np.array(tok[n * kk:n * kk + 4 * m], dtype=np.int64).reshape(m, 4)
         if m and (ft[:, 0] != 3).any():
             raise ValueError("load_ply: a face is not a triangle")
         t = ft[:, 1:].astype(np.int32)
     else:
         raise ValueError("load_ply: unsupported format %r" % mode)
-    return np.ascontiguousarray(a[:, :3]), np.ascontiguousarray(t), (np.ascontiguousarray(a[:, 3:]) if k == 6 else None)
+    return np.ascontiguousarray(a[:, :3]), np.ascontiguousarray(t), (np.ascontiguousarray(a[:, 3:]) if k == 6 else None), c
+
+
+def load_ply(path):
+    """Reads what save_ply writes (and any PLY of that shape: float x y z, optionally nx ny nz, optionally uchar red green blue alpha, faces as
+    list uchar int, triangles only).  Returns (verts float32[n, 3], tris int32[m, 3], normals float32[n, 3] or None); the colours of a coloured
+    file come from load_ply_colors."""
+    return _load_ply(path)[:3]
+
+
+def load_ply_colors(path):
+    """load_ply with the per-vertex colours: (verts, tris, normals or None, colors uint8[n, 4] or None)."""
+    return _load_ply(path)
 
 
 # GlobalRegistration's alignment.config (helper.h's Configuration): key=value lines.  The defaults are the values of the file the reference ships.

@@ -88,6 +88,79 @@ def render_depth(poses, cols=640, rows=480, cam=CAM, lo=ROOM_LO, hi=ROOM_HI, sph
     return out.to(torch.uint16) if hasattr(torch, "uint16") else out.to(torch.int16)
 
 
+# Frequencies (cycles per metre) of the colour texture's triangle waves, per channel and axis; amplitude and offset in 8-bit levels.
+TEXTURE_FREQ = ((2.0, 1.5, 1.25), (1.25, 2.0, 1.5), (1.5, 1.25, 2.0))
+TEXTURE_AMP, TEXTURE_BASE = 66.0, 30.0
+TEXTURE_G = 369.0                          # levels per metre: the bound on the texture's gradient, see texture()
+
+
+def texture(xyz):
+    """The procedural colour of a world point: xyz [..., 3] float64 (numpy array or torch tensor) -> [..., 3] unrounded 8-bit levels in [30, 228].
+    Channel c = 30 + 66 ((tri(f_c0 x) + tri(f_c1 y)) + tri(f_c2 z)) with the triangle wave tri(s) = 2 |s - floor(s) - 0.5| in [0, 1] and the
+    frequencies TEXTURE_FREQ: only + - x floor abs on float64, so the values are bit-reproducible.  tri has slope +-2, so the gradient of a
+    channel is 132 (+-f_c0, +-f_c1, +-f_c2) wherever it exists, of norm 132 sqrt(2^2 + 1.5^2 + 1.25^2) = 368.96 for every channel: the texture
+    is Lipschitz with G = TEXTURE_G = 369 levels per metre."""
+    tens = torch.is_tensor(xyz)
+    fl = torch.floor if tens else np.floor
+    ab = torch.abs if tens else np.abs
+    out = []
+    for fc in TEXTURE_FREQ:
+        tri = []
+        for a in range(3):
+            s = xyz[..., a] * fc[a]
+            tri.append(2.0 * ab((s - fl(s)) - 0.5))
+        out.append(TEXTURE_BASE + TEXTURE_AMP * ((tri[0] + tri[1]) + tri[2]))
+    return torch.stack(out, dim=-1) if tens else np.stack(out, axis=-1)
+
+
+def render_rgbd(poses, cols=640, rows=480, cam=CAM, lo=ROOM_LO, hi=ROOM_HI, sphere=True, max_depth=4.0,
+                device="cpu", chunk=64):
+    """render_depth's ray cast with a colour per hit: (depth uint16 [n, rows*cols] -- render_depth's image bit for bit --, rgb uint8
+    [n, rows*cols, 3]), torch tensors on `device`.  The colour of a pixel is floor(texture(hit point) + 0.5) with the hit point o + t d in
+    float64, and 0 0 0 where the depth is 0.  Elementwise float64 operations in a fixed order only: bit-reproducible like the depth."""
+    fx, fy, cx, cy = cam
+    P = torch.as_tensor(np.asarray(poses, np.float64), dtype=torch.float64, device=device).reshape(-1, 4, 4)
+    n = P.shape[0]
+    u = torch.arange(cols, dtype=torch.float64, device=device)
+    v = torch.arange(rows, dtype=torch.float64, device=device)
+    dx = ((u - cx) / fx).repeat(rows)                      # row-major pixel order
+    dy = ((v - cy) / fy).repeat_interleave(cols)
+    out = torch.empty((n, rows * cols), dtype=torch.int32, device=device)
+    rgb = torch.empty((n, rows * cols, 3), dtype=torch.uint8, device=device)
+    inf = float("inf")
+    for s in range(0, n, chunk):
+        # (render_depth's operations in render_depth's order)
+        R = P[s:s + chunk, :3, :3]
+        o = P[s:s + chunk, :3, 3]                                       # [b,3]
+        d = [(R[:, a, 0:1] * dx[None, :] + R[:, a, 1:2] * dy[None, :]) + R[:, a, 2:3] for a in range(3)]   # camera z = 1 -> t == depth
+        t = torch.full_like(d[0], inf)
+        for a in range(3):
+            da = d[a]
+            wall = torch.where(da > 0, torch.full_like(da, hi), torch.full_like(da, lo))
+            ta = (wall - o[:, a:a + 1]) / da
+            ta = torch.where(da.abs() < 1e-12, torch.full_like(ta, inf), ta)
+            t = torch.minimum(t, torch.where(ta > 0, ta, torch.full_like(ta, inf)))
+        if sphere:
+            oc = [o[:, a:a + 1] - SPHERE_C[a] for a in range(3)]        # [b,1] each
+            A = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]
+            B = 2.0 * ((d[0] * oc[0] + d[1] * oc[1]) + d[2] * oc[2])
+            Cc = ((oc[0] * oc[0] + oc[1] * oc[1]) + oc[2] * oc[2]) - SPHERE_R * SPHERE_R
+            disc = B * B - 4.0 * A * Cc
+            sq = torch.sqrt(disc.clamp(min=0))
+            ts = (-B - sq) / (2.0 * A)
+            ts = torch.where((disc > 0) & (ts > 1e-6), ts, torch.full_like(ts, inf))
+            t = torch.minimum(t, ts)
+        mm = torch.floor(t * 1000.0 + 0.5)
+        mm = torch.where(torch.isfinite(mm) & (t <= max_depth) & (mm < 65535.5), mm, torch.zeros_like(mm))
+        out[s:s + chunk] = mm.to(torch.int32)
+        hit = mm > 0
+        ts_ = torch.where(hit, t, torch.zeros_like(t))                  # (no inf * 0 below)
+        xyz = torch.stack([o[:, a:a + 1] + ts_ * d[a] for a in range(3)], dim=-1)
+        col = torch.floor(texture(xyz) + 0.5)
+        rgb[s:s + chunk] = torch.where(hit[..., None], col, torch.zeros_like(col)).to(torch.uint8)
+    return (out.to(torch.uint16) if hasattr(torch, "uint16") else out.to(torch.int16)), rgb
+
+
 def to_numpy_u16(t):
     """torch uint16/int16 tensor -> numpy uint16 (host)."""
     a = t.cpu()

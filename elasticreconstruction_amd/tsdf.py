@@ -44,6 +44,7 @@ class TSDFVolume:
                                             self.camera_.ctypes.data_as(C.POINTER(C.c_float)),
                                             self.max_units, self.device, C.byref(h)), "er_tsdf_create")
         self._h = h
+        self.color_enabled_ = False
 
     def close(self):
         if getattr(self, "_h", None):
@@ -106,27 +107,30 @@ class TSDFVolume:
         T = np.ascontiguousarray(transformation, dtype=np.float64).reshape(16)
         _ffi.check(self._lib.er_tsdf_integrate(self._h, _ffi.ptr(d), _ffi.ptr(T)), "er_tsdf_integrate")
 
+    @staticmethod
+    def _warp_ref(warp, n):
+        """The warp dict of IntegrateFrames as (byref(er_warp) or None, the arrays it points into)."""
+        if warp is None:
+            return None, []
+        ctr = np.ascontiguousarray(warp["ctr"], dtype=np.float32)
+        gi = np.ascontiguousarray(warp["grid_index"], dtype=np.int32).reshape(-1)
+        seg = np.ascontiguousarray(warp["seg"], dtype=np.float64).reshape(-1, 16)
+        madj = np.ascontiguousarray(warp["madj"], dtype=np.float64).reshape(-1, 16)
+        assert gi.size == n and seg.shape[0] == n and madj.shape[0] == n
+        res = int(warp["resolution"])
+        num = ctr.size // (3 * (res + 1) ** 3)
+        w = _ffi.ErWarp(ctr.ctypes.data_as(C.POINTER(C.c_float)), num, res, C.c_float(warp["length"]),
+                        gi.ctypes.data_as(C.POINTER(C.c_int)), seg.ctypes.data_as(C.POINTER(C.c_double)),
+                        madj.ctypes.data_as(C.POINTER(C.c_double)))
+        return C.byref(w), [ctr, gi, seg, madj, w]
+
     def IntegrateFrames(self, depth, transformations, warp=None, device_ptr=None):
         """n frames in order.  depth: uint16[n, rows*cols] on the host, or device_ptr = address of the same
         layout in HBM.  warp = dict(ctr=float32[num, verts, 3], resolution, length, grid_index=int[n],
         seg=float64[n,4,4], madj=float64[n,4,4]) or None."""
         T = np.ascontiguousarray(transformations, dtype=np.float64).reshape(-1, 16)
         n = T.shape[0]
-        w_ref = None
-        keep = []
-        if warp is not None:
-            ctr = np.ascontiguousarray(warp["ctr"], dtype=np.float32)
-            gi = np.ascontiguousarray(warp["grid_index"], dtype=np.int32).reshape(-1)
-            seg = np.ascontiguousarray(warp["seg"], dtype=np.float64).reshape(-1, 16)
-            madj = np.ascontiguousarray(warp["madj"], dtype=np.float64).reshape(-1, 16)
-            assert gi.size == n and seg.shape[0] == n and madj.shape[0] == n
-            res = int(warp["resolution"])
-            num = ctr.size // (3 * (res + 1) ** 3)
-            w = _ffi.ErWarp(ctr.ctypes.data_as(C.POINTER(C.c_float)), num, res, C.c_float(warp["length"]),
-                            gi.ctypes.data_as(C.POINTER(C.c_int)), seg.ctypes.data_as(C.POINTER(C.c_double)),
-                            madj.ctypes.data_as(C.POINTER(C.c_double)))
-            keep = [ctr, gi, seg, madj, w]
-            w_ref = C.byref(w)
+        w_ref, keep = self._warp_ref(warp, n)
         if device_ptr is not None:
             _ffi.check(self._lib.er_tsdf_integrate_frames(self._h, n, C.c_void_p(device_ptr), 1, _ffi.ptr(T), w_ref),
                        "er_tsdf_integrate_frames")
@@ -252,10 +256,11 @@ class TSDFVolume:
         formats.save_pcd_xyzi(filename, pts)
         return pts.shape[0]
 
-    def extract_indexed_mesh(self):
+    def extract_indexed_mesh(self, colors=False):
         """extract_mesh's triangles as an indexed mesh (er_tsdf_extract_mesh_indexed): (verts float32[n, 4] = x y z axis, normals float32[n, 3],
         tris int32[m, 3]).  A vertex is a lattice edge that a triangle uses, in extract_surface's order; verts[tris][..., :3] is extract_mesh's
-        soup bit for bit; a normal is extract_oriented's rule at the vertex, NaN where it gives none."""
+        soup bit for bit; a normal is extract_oriented's rule at the vertex, NaN where it gives none.  colors = True appends sample_colors(verts),
+        uint8[n, 4]."""
         nv, nt = C.c_long(0), C.c_long(0)
         _ffi.check(self._lib.er_tsdf_extract_mesh_indexed(self._h, None, None, 0, None, 0, C.byref(nv), C.byref(nt)), "er_tsdf_extract_mesh_indexed")
         verts = np.empty((nv.value, 4), dtype=np.float32)
@@ -264,13 +269,85 @@ class TSDFVolume:
         if nv.value:
             _ffi.check(self._lib.er_tsdf_extract_mesh_indexed(self._h, _ffi.ptr(verts), _ffi.ptr(nrm), nv.value, _ffi.ptr(tris), nt.value,
                                                               C.byref(nv), C.byref(nt)), "er_tsdf_extract_mesh_indexed")
+        if colors:
+            return verts, np.ascontiguousarray(nrm[:, :3]), tris, self.sample_colors(verts)
         return verts, np.ascontiguousarray(nrm[:, :3]), tris
 
-    def SaveMesh(self, filename, normals=True, binary=True):
-        """The indexed mesh of the resident volume as PLY (formats.save_ply; NaN normals become 0 0 0).  Returns (vertices, triangles)."""
-        verts, nrm, tris = self.extract_indexed_mesh()
-        formats.save_ply(filename, verts, tris, nrm if normals else None, binary)
+    def SaveMesh(self, filename, normals=True, binary=True, colors=None):
+        """The indexed mesh of the resident volume as PLY (formats.save_ply; NaN normals become 0 0 0).  colors = None: per-vertex colours iff
+        colour is enabled on the volume; False suppresses them; True demands them.  Returns (vertices, triangles)."""
+        if colors is None:
+            colors = self.color_enabled_
+        if colors:
+            verts, nrm, tris, rgba = self.extract_indexed_mesh(colors=True)
+        else:
+            (verts, nrm, tris), rgba = self.extract_indexed_mesh(), None
+        formats.save_ply(filename, verts, tris, nrm if normals else None, binary, colors=rgba)
         return verts.shape[0], tris.shape[0]
+
+    # -- colour (DESIGN.md 7.16) -----------------------------------------------------------------
+    def enable_color(self):
+        """er_tsdf_color_enable: allocates the per-voxel colour accumulators (4 MiB per unit of max_units).  Idempotent."""
+        _ffi.check(self._lib.er_tsdf_color_enable(self._h), "er_tsdf_color_enable")
+        self.color_enabled_ = True
+
+    def ColorFrames(self, depth, rgb, transformations, warp=None, device_ptrs=None):
+        """er_tsdf_color_frames: splats the colour of n frames -- IntegrateFrames' depth, transformations and warp of the same frames, which are
+        meant to have been integrated already -- into the accumulators.  depth: uint16[n, rows*cols], rgb: uint8[n, rows*cols, 3] on the host, or
+        device_ptrs = (depth address, rgb address) of the same layouts in HBM.  Returns (added, no_unit, out_of_range) pixels."""
+        T = np.ascontiguousarray(transformations, dtype=np.float64).reshape(-1, 16)
+        n = T.shape[0]
+        w_ref, keep = self._warp_ref(warp, n)
+        st = (C.c_long * 3)(0, 0, 0)
+        if device_ptrs is not None:
+            dp, cp, on_dev = C.c_void_p(device_ptrs[0]), C.c_void_p(device_ptrs[1]), 1
+        else:
+            d = np.ascontiguousarray(depth, dtype=np.uint16).reshape(-1)
+            c = np.ascontiguousarray(rgb, dtype=np.uint8).reshape(-1)
+            if d.size != n * self.cols_ * self.rows_ or c.size != 3 * d.size:
+                raise ValueError("ColorFrames: %d depth pixels and %d colour bytes are not %d frames of a %d x %d image"
+                                 % (d.size, c.size, n, self.cols_, self.rows_))
+            dp, cp, on_dev = _ffi.ptr(d), _ffi.ptr(c), 0
+        _ffi.check(self._lib.er_tsdf_color_frames(self._h, n, dp, cp, on_dev, _ffi.ptr(T), w_ref, st), "er_tsdf_color_frames")
+        del keep
+        return st[0], st[1], st[2]
+
+    def ReprojectColor(self, depth, rgb, ctr, resolution, length, seg, madj):
+        """Reproject with the colour image (er_tsdf_reproject_color) for one frame; returns (the new depth, the new colour uint8[rows*cols, 3])."""
+        d = np.array(depth, dtype=np.uint16).reshape(-1)
+        c = np.array(rgb, dtype=np.uint8).reshape(-1, 3)
+        assert d.size == self.cols_ * self.rows_ and c.shape[0] == d.size
+        g = np.ascontiguousarray(ctr, dtype=np.float32).reshape(-1)
+        s = np.ascontiguousarray(seg, dtype=np.float64).reshape(16)
+        m = np.ascontiguousarray(madj, dtype=np.float64).reshape(16)
+        _ffi.check(self._lib.er_tsdf_reproject_color(self._h, _ffi.ptr(d), _ffi.ptr(c), _ffi.ptr(g), int(resolution), C.c_float(length),
+                                                     _ffi.ptr(s), _ffi.ptr(m)), "er_tsdf_reproject_color")
+        return d, c
+
+    def read_unit_color(self, key):
+        """The accumulators of one unit: uint32[64^3, 4] = r_sum, g_sum, b_sum, n per voxel, in read_unit's voxel order."""
+        a = np.empty((UNIT_VOX, 4), dtype=np.uint32)
+        _ffi.check(self._lib.er_tsdf_read_unit_color(self._h, int(key), _ffi.ptr(a)), "er_tsdf_read_unit_color")
+        return a
+
+    def write_unit_color(self, key, rgbn):
+        a = np.ascontiguousarray(rgbn, dtype=np.uint32).reshape(UNIT_VOX, 4)
+        _ffi.check(self._lib.er_tsdf_write_unit_color(self._h, int(key), _ffi.ptr(a)), "er_tsdf_write_unit_color")
+
+    def sample_colors(self, points, counts=False):
+        """er_tsdf_sample_colors: uint8[n, 4] = r g b a for points float32[n, 3] or [n, 4] (x y z in metres; a fourth column is ignored), a = 255
+        where the nearest voxel (level 0) or its 3 x 3 x 3 neighbourhood (level 1) holds a sample, 0 0 0 0 elsewhere.  counts = True: also
+        (points coloured at level 0, at level 1)."""
+        p = np.asarray(points, np.float32)
+        if p.ndim != 2 or p.shape[1] not in (3, 4):
+            raise ValueError("sample_colors: points must be [n, 3] or [n, 4], not %s" % (p.shape,))
+        if p.shape[1] == 3:
+            p = np.concatenate([p, np.zeros((p.shape[0], 1), np.float32)], axis=1)
+        p = np.ascontiguousarray(p)
+        out = np.zeros((p.shape[0], 4), dtype=np.uint8)
+        ct = (C.c_long * 2)(0, 0)
+        _ffi.check(self._lib.er_tsdf_sample_colors(self._h, _ffi.ptr(p), p.shape[0], _ffi.ptr(out), ct), "er_tsdf_sample_colors")
+        return (out, (ct[0], ct[1])) if counts else out
 
     def LoadWorld(self, path_or_array):
         """SaveWorld's inverse (er_tsdf_import_world) into this EMPTY volume: a world.pcd path, or float32[n, 4] = x y z intensity rows as
@@ -414,6 +491,7 @@ class IntegrateApp:
         self.volume_ = None
         self._max_units, self._device, self._batch = max_units, device, int(batch)
         self._q_depth, self._q_T, self._q_gi, self._q_seg, self._q_madj = [], [], [], [], []
+        self._q_color = []
         self.frames_integrated = 0
 
     def Init(self):
@@ -438,8 +516,10 @@ class IntegrateApp:
                         self.traj_.append(formats.FramedTransformation(
                             idx, idx, idx + 1, mat4_mul(self.pose_traj_[i].T, self.seg_traj_[idx].T)))
 
-    def Execute(self, frame_id, depth):
-        """One main-loop turn with data (IntegrateApp.cpp:190-226); frame_id is 1-based."""
+    def Execute(self, frame_id, depth, color=None):
+        """One main-loop turn with data (IntegrateApp.cpp:190-226); frame_id is 1-based.  color: the frame's registered colour image,
+        uint8[rows, cols, 3], or None -- with colour, every frame of the run must carry one; the colour of each batch is splatted behind
+        its integration (bin/Integrate --color_raw / --color_list)."""
         self.frame_id_ = frame_id
         if self.traj_[frame_id - 1].frame == -1:
             return
@@ -461,6 +541,8 @@ class IntegrateApp:
             self._q_seg.append(self.seg_traj_[frame_id - 1].T.copy())
             self._q_madj.append(madj)
         self._q_depth.append(np.ascontiguousarray(depth, dtype=np.uint16).reshape(-1))
+        if color is not None:
+            self._q_color.append(np.ascontiguousarray(color, dtype=np.uint8).reshape(-1, 3))
         self._q_T.append(T.copy())
         if len(self._q_depth) >= self._batch:
             self.Flush()
@@ -473,8 +555,14 @@ class IntegrateApp:
             warp = dict(ctr=self.grids_, resolution=self.ctr_resolution_, length=np.float32(self.ctr_length_),
                         grid_index=np.array(self._q_gi, np.int32), seg=np.array(self._q_seg), madj=np.array(self._q_madj))
         self.volume_.IntegrateFrames(np.stack(self._q_depth), np.array(self._q_T), warp)
+        if self._q_color:
+            if len(self._q_color) != len(self._q_depth):
+                raise ValueError("IntegrateApp: %d of the %d queued frames carry colour" % (len(self._q_color), len(self._q_depth)))
+            self.volume_.enable_color()
+            self.volume_.ColorFrames(np.stack(self._q_depth), np.stack(self._q_color), np.array(self._q_T), warp)
         self.frames_integrated += len(self._q_depth)
         self._q_depth, self._q_T, self._q_gi, self._q_seg, self._q_madj = [], [], [], [], []
+        self._q_color = []
 
     def Finish(self, save=True):
         self.Flush()

@@ -191,6 +191,55 @@ int er_tsdf_extract_mesh_indexed(er_tsdf_t h, float* verts_host, float* normals_
  * n == 0 succeeds with no units. */
 int er_tsdf_import_world(er_tsdf_t h, const float* xyzi_host, long n, int* n_units);
 
+/* Colour: registered RGB frames splatted into per-voxel integer accumulators, and the colour of a point read back from them.
+ * The reference has no colour code: these entries restate tests/color_restatement.py bit for bit.  Everything is integer arithmetic on sums of
+ * bytes, so the accumulators hold the same bits whatever the batch split, the frame order, the stream or the run.
+ *
+ * er_tsdf_color_enable allocates and zero-fills max_units x 64^3 records of uint32 r_sum, g_sum, b_sum, n (16 bytes a voxel, 4 MiB a unit), indexed
+ * by the unit's pool slot, voxel (i * 64 + j) * 64 + k as the sdf.  Idempotent.  A failed allocation is a refusal that names the bytes.  A volume
+ * that never enables colour allocates nothing and behaves as before.  er_tsdf_reset zeroes the accumulators, er_tsdf_drop_units those of the
+ * dropped units.  Band, raw and weighted export / import do not carry colour, and every colour entry is refused while er_tsdf_set_unit_shard
+ * has world > 1.  A record is added to as two 64-bit words (r | g << 32), (b | n << 32): below 2^24 samples per voxel no field carries into its
+ * neighbour; beyond that the sums are wrong and nothing checks it.
+ * All other colour entries are refused before er_tsdf_color_enable. */
+int er_tsdf_color_enable(er_tsdf_t h);
+
+/* The 64^3 x 4 accumulator words of one EXISTING unit to / from host memory; a key without a unit is refused. */
+int er_tsdf_read_unit_color(er_tsdf_t h, int key, uint32_t* rgbn_host);
+int er_tsdf_write_unit_color(er_tsdf_t h, int key, const uint32_t* rgbn_host);
+
+/* The splat.  depth: n x rows x cols uint16; rgb: n x rows x cols x 3 bytes, registered to the depth image and of its size; both in host memory or
+ * (on_device != 0) both complete in device memory; T: er_tsdf_integrate_frames' poses of the same frames.  The frames are meant to have been
+ * integrated already, so that their units exist; nothing enforces it.  Pixel (u, v) of a frame contributes iff
+ *   1. d = depth != 0, and
+ *   2. scale_depth(d, u, v) > 0.001f: the pixels TSDFVolume::IntegrateVolumeUnit uses (TSDFVolume.cpp:29, 82; beyond integration_trunc it is 0);
+ *   3. its world point -- TSDFVolume::UVD2XYZ, then ((T0 x + T1 y) + T2 z) + T3 in float64, the chain behind the unit keys -- gives the voxel
+ *      g_a = floor(p_a / unit length + 0.5) per axis; a g_a outside [-16384, 16384) sends the pixel to out_of_range;
+ *   4. the unit (g_a + 16384) / 64 exists; otherwise the pixel goes to no_unit;
+ *   5. then (r, g, b, 1) is added to voxel (g_a + 16384) & 63 of that unit.
+ * stats (nullable): pixels added, no_unit, out_of_range, of this call.  n == 0 succeeds.  Two calls accumulate.  The call runs on the handle's
+ * stream behind the voxel passes and returns when the device work is done.
+ * warp (nullable): er_tsdf_integrate_frames' warp of the same frames.  Depth and colour are first warped into the frame's virtual camera -- per
+ * frame (Z, C') of er_tsdf_reproject_color below -- and steps 1 to 5 then run on (Z, C'); after that everything is rigid. */
+int er_tsdf_color_frames(er_tsdf_t h, int n, const uint16_t* depth, const uint8_t* rgb, int on_device, const double* T, const er_warp* warp,
+                         long stats[3]);
+
+/* er_tsdf_reproject with the colour image, for ONE frame in place on host memory (colour need not be enabled).  Afterwards depth holds Z, exactly
+ * what er_tsdf_reproject returns, and rgb holds C': C'[c] = C[winner(c)] where winner(c) is the LOWEST source pixel index p with depth[p] != 0
+ * whose reprojection succeeds with cell c and a 16-bit depth equal to Z[c] != 0; 0 0 0 where Z[c] == 0.  The rule is a definition and does not
+ * depend on any order: where the reference's replay of zero-depth writes would have erased an equal-depth earlier write, the colour may come
+ * from that pixel. */
+int er_tsdf_reproject_color(er_tsdf_t h, uint16_t* depth_inout_host, uint8_t* rgb_inout_host, const float* ctr_host, int resolution, float length,
+                            const double seg[16], const double madj[16]);
+
+/* Colour at n points of host memory, 4 floats per row (x y z in metres, the 4th ignored: er_tsdf_extract_surface's, er_tsdf_extract_oriented's and
+ * er_tsdf_extract_mesh_indexed's vertex layout) -> rgba_host, 4 bytes per point.  v = rint((double)p / unit length) per component, half to even
+ * (er_tsdf_extract_oriented's nearest voxel).  Level 0: voxel v, if its unit exists and its n > 0.  Level 1 otherwise: the 64-bit sums over the
+ * 27 voxels v + {-1, 0, 1}^3 that lie on the lattice in existing units, across unit borders.  Channel = (2 sum + n) / (2 n) in integer division
+ * (round half up), a = 255.  No sample, a non-finite coordinate or a v off the lattice gives 0 0 0 0.  counts (nullable): points coloured at
+ * level 0 and at level 1. */
+int er_tsdf_sample_colors(er_tsdf_t h, const float* points_host, long n, uint8_t* rgba_host, long counts[2]);
+
 /* The resident volume ray-cast from a pose: the model side of frame-to-model tracking (er_odom_align_model below) and a
  * direct picture of what er_tsdf_integrate_frames built.  The reference tree has no ray caster (KinFu's lives in the author's PCL fork):
  * this entry restates tests/raycast_restatement.py, the numpy statement of csrc/er_raycast_math.h, bit for bit, and NOTHING here is checked
