@@ -78,9 +78,12 @@ constexpr int kLoShift = 4;
 constexpr int kLoSub = kTile >> kLoShift;               // tile_lo tiles per side of a 32 x 32 k_prepare tile: 2
 constexpr int kTileKeys = 96;
 
-constexpr int kPrepThreads = 256;                       // 32 x 8 threads, 4 pixel rows each
+constexpr int kPrepThreads = 256;                       // 8 column groups x 32 rows of threads, kPrepPix adjacent pixels of one row each
 constexpr int kPrepPix = kTile * kTile / kPrepThreads;  // pixels per thread
 
+// kWide: one 16-byte access per array and thread (8-byte for the 16-bit depth) behind one bounds test; needs cols % 4 == 0 and an 8-byte
+// aligned depth pointer (run_batch chooses; er_tsdf_pre.hip)
+template <bool kWide>
 __global__ __launch_bounds__(kPrepThreads) void k_prepare(
     const uint16_t* __restrict__ depth, uint32_t* __restrict__ zbuf, int n_frames, int cols, int rows,
     Camera cam, CameraInv cami, const float* __restrict__ lambda, const double* __restrict__ T12, float* __restrict__ scaled,
@@ -88,6 +91,8 @@ __global__ __launch_bounds__(kPrepThreads) void k_prepare(
     int hash_shift, int* __restrict__ batch, int* __restrict__ nbatch,
     int* __restrict__ counters, float* __restrict__ tile_max, float* __restrict__ tile_lo, float* __restrict__ tile_lo_fine, int2 shard,
     uint32_t* __restrict__ lastzero, uint32_t* __restrict__ zfix, const int* __restrict__ zero_flag);
+extern template __global__ void k_prepare<true>(const uint16_t* __restrict__, uint32_t* __restrict__, int, int, int, Camera, CameraInv, const float* __restrict__, const double* __restrict__, float* __restrict__, int* __restrict__, int* __restrict__, unsigned long long* __restrict__, int, int, int* __restrict__, int* __restrict__, int* __restrict__, float* __restrict__, float* __restrict__, float* __restrict__, int2, uint32_t* __restrict__, uint32_t* __restrict__, const int* __restrict__);
+extern template __global__ void k_prepare<false>(const uint16_t* __restrict__, uint32_t* __restrict__, int, int, int, Camera, CameraInv, const float* __restrict__, const double* __restrict__, float* __restrict__, int* __restrict__, int* __restrict__, unsigned long long* __restrict__, int, int, int* __restrict__, int* __restrict__, int* __restrict__, float* __restrict__, float* __restrict__, float* __restrict__, int2, uint32_t* __restrict__, uint32_t* __restrict__, const int* __restrict__);
 
 // k_plan's records and k_integrate's work items
 constexpr int kRows = 4;                  // register rows per lane of k_integrate: a wave owns an 8 x 4 x 8 box of voxels (2 x 4 x 8 lanes x 4 rows)

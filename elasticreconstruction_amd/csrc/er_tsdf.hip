@@ -473,7 +473,11 @@ int run_batch(er_tsdf_t h, int n, const uint16_t* depth_dev, const double* T, co
     zsrc = h->zbuf[a];
   }
 
-  hipLaunchKernelGGL(k_prepare, dim3((h->cols + kTile - 1) / kTile, (h->rows + kTile - 1) / kTile, n), dim3(kPrepThreads), 0, X,
+  // wide accesses (16 bytes per array and thread, 8 for the 16-bit depth): every frame base must be a multiple of four elements -- cols % 4 == 0
+  // gives that for the handle's own buffers -- and a caller's device depth, which may sit at any 2-byte boundary, 8-byte aligned (the warped
+  // path reads the z-buffer instead)
+  const bool wide = h->cols % 4 == 0 && (zsrc || reinterpret_cast<uintptr_t>(depth_dev) % 8 == 0);
+  hipLaunchKernelGGL(wide ? k_prepare<true> : k_prepare<false>, dim3((h->cols + kTile - 1) / kTile, (h->rows + kTile - 1) / kTile, n), dim3(kPrepThreads), 0, X,
                      depth_dev, zsrc, n, h->cols, h->rows, h->cam, h->cami, h->lambda, dev_t12, h->scaled[p], h->ht_key, h->ht_slot,
                      h->ht_mask[p], h->ht_cap - 1, h->ht_shift, h->batch[p], nbatch, h->counters,
                      h->tile_max[p], h->tile_lo[p], h->tile_lo_fine[p], make_int2(h->shard_rank, h->shard_world), h->lastzero[a], h->zfix[a],
@@ -859,6 +863,42 @@ int er_tsdf_integrate_frames(er_tsdf_t h, int n, const uint16_t* depth, int dept
 
 int er_tsdf_integrate(er_tsdf_t h, const uint16_t* depth_host, const double T[16]) {
   return er_tsdf_integrate_frames(h, 1, depth_host, 0, T, nullptr);
+}
+
+// Test hook (include/er_hip.h).  Nothing of the batch's pipeline slot is overwritten before the slot's next batch: k_reset (flushed by sync_all)
+// clears the hash map's frame masks and the list length, not plan_rec, which holds the {key, slot, mask} records k_integrate read.
+int er_tsdf_prepass_trace(er_tsdf_t h, int n, const uint16_t* depth, int depth_on_device, const double* T, const er_warp* warp,
+                          float* scaled, int* scaled_pad, float* tile_max, float* tile_lo, float* tile_lo_fine,
+                          int* keys, unsigned long long* masks, int keys_cap, int* n_keys) {
+  if (!h) return er::fail("er_tsdf_prepass_trace: NULL handle");
+  if (n < 1 || n > ER_MAX_BATCH) return er::fail("er_tsdf_prepass_trace: %d frames outside 1..%d (one batch)", n, ER_MAX_BATCH);
+  ER_HIP_TRY(hipSetDevice(h->device));
+  if (sync_all(h)) return 1;
+  const int p = (int)(h->batch_no % kDepth);
+  if (er_tsdf_integrate_frames(h, n, depth, depth_on_device, T, warp)) return 1;
+  if (sync_all(h)) return 1;
+  const size_t B = ER_MAX_BATCH, px = (size_t)h->pixels;
+  const size_t tiles = (size_t)((h->cols + kTile - 1) / kTile) * ((h->rows + kTile - 1) / kTile);
+  const size_t fine = (size_t)((h->cols + (1 << kLoShift) - 1) >> kLoShift) * ((h->rows + (1 << kLoShift) - 1) >> kLoShift);
+  if (scaled_pad) *scaled_pad = kScaledPad;
+  if (scaled) ER_HIP_TRY(hipMemcpy(scaled, h->scaled[p], (size_t)n * (px + kScaledPad) * sizeof(float), hipMemcpyDeviceToHost));
+  if (tile_max) ER_HIP_TRY(hipMemcpy(tile_max, h->tile_max[p], tiles * B * sizeof(float), hipMemcpyDeviceToHost));
+  if (tile_lo) ER_HIP_TRY(hipMemcpy(tile_lo, h->tile_lo[p], tiles * B * sizeof(float), hipMemcpyDeviceToHost));
+  if (tile_lo_fine) ER_HIP_TRY(hipMemcpy(tile_lo_fine, h->tile_lo_fine[p], fine * B * sizeof(float), hipMemcpyDeviceToHost));
+  Plan plan{};
+  ER_HIP_TRY(hipMemcpy(&plan, h->plan[p], sizeof plan, hipMemcpyDeviceToHost));
+  if (plan.n_units < 0 || plan.n_units > h->ht_cap) return er::fail("er_tsdf_prepass_trace: the batch lists %d units", plan.n_units);
+  if (n_keys) *n_keys = plan.n_units;
+  if (keys || masks) {
+    std::vector<PlanRec> rec((size_t)plan.n_units);
+    if (plan.n_units > 0) ER_HIP_TRY(hipMemcpy(rec.data(), h->plan_rec[p], rec.size() * sizeof(PlanRec), hipMemcpyDeviceToHost));
+    std::sort(rec.begin(), rec.end(), [](const PlanRec& a, const PlanRec& b) { return a.key < b.key; });
+    for (int i = 0; i < plan.n_units && i < keys_cap; i++) {
+      if (keys) keys[i] = rec[(size_t)i].key;
+      if (masks) masks[i] = rec[(size_t)i].mask;
+    }
+  }
+  return 0;
 }
 
 int er_tsdf_wait_event(er_tsdf_t h, void* hip_event) {

@@ -141,6 +141,38 @@ class TSDFVolume:
                        "er_tsdf_integrate_frames")
         del keep
 
+    def prepass_trace(self, depth, transformations, warp=None, device_ptr=None):
+        """er_tsdf_prepass_trace (test hook): IntegrateFrames of ONE batch (<= 64 frames) on a quiet volume, then what its voxel pass was
+        given.  Returns dict(scaled float32 [n, pixels + pad], pad, tile_max / tile_lo float32 [tiles_y, tiles_x, n] (32-pixel tiles),
+        tile_lo_fine float32 [fine_y, fine_x, n] (16-pixel tiles), keys int32 [k] ascending, masks uint64 [k])."""
+        T = np.ascontiguousarray(transformations, dtype=np.float64).reshape(-1, 16)
+        n = T.shape[0]
+        w_ref, keep = self._warp_ref(warp, n)
+        px = self.cols_ * self.rows_
+        if device_ptr is not None:
+            src, on_dev = C.c_void_p(device_ptr), 1
+        else:
+            d = np.ascontiguousarray(depth, dtype=np.uint16).reshape(n, -1)
+            assert d.shape[1] == px
+            src, on_dev = _ffi.ptr(d), 0
+        B = 64                                                  # ER_MAX_BATCH
+        tx, ty = (self.cols_ + 31) // 32, (self.rows_ + 31) // 32
+        fx, fy = (self.cols_ + 15) // 16, (self.rows_ + 15) // 16
+        pad, nk = C.c_int(0), C.c_int(0)
+        pad_floats = 64                                       # kScaledPad; checked against the library's answer below
+        scaled = np.empty((n, px + pad_floats), np.float32)
+        tmax, tlo = np.empty((ty, tx, B), np.float32), np.empty((ty, tx, B), np.float32)
+        fine = np.empty((fy, fx, B), np.float32)
+        cap = 1 << 16
+        keys, masks = np.empty(cap, np.int32), np.empty(cap, np.uint64)
+        _ffi.check(self._lib.er_tsdf_prepass_trace(self._h, n, src, on_dev, _ffi.ptr(T), w_ref, _ffi.ptr(scaled), C.byref(pad), _ffi.ptr(tmax),
+                                                   _ffi.ptr(tlo), _ffi.ptr(fine), _ffi.ptr(keys), _ffi.ptr(masks), cap, C.byref(nk)),
+                   "er_tsdf_prepass_trace")
+        del keep
+        assert pad.value == pad_floats and nk.value <= cap
+        return dict(scaled=scaled, pad=pad.value, tile_max=tmax[:, :, :n].copy(), tile_lo=tlo[:, :, :n].copy(),
+                    tile_lo_fine=fine[:, :, :n].copy(), keys=keys[:nk.value].copy(), masks=masks[:nk.value].copy())
+
     # -- data_ access ---------------------------------------------------------------------------
     def unit_count(self):
         n = C.c_int(0)

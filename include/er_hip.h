@@ -107,6 +107,19 @@ int er_tsdf_integrate(er_tsdf_t h, const uint16_t* depth_host, const double T[16
 int er_tsdf_integrate_frames(er_tsdf_t h, int n, const uint16_t* depth, int depth_on_device, const double* T,
                              const er_warp* warp);
 
+/* Test hook: ONE batch (1 <= n <= ER_MAX_BATCH frames; arguments as er_tsdf_integrate_frames) through the ordinary pipeline on a quiet handle
+ * -- it is integrated into the volume like any other -- and then what the batch's voxel pass was given by the pre-pass, copied to the host:
+ *   scaled        float[n * (rows*cols + *scaled_pad)]: the scaled depth of each frame followed by the frame's pad;
+ *   tile_max/lo   float[tiles32 * ER_MAX_BATCH] each, [tile][frame], tiles32 = ceil(cols/32) * ceil(rows/32), row-major (columns of frames >= n
+ *                 hold whatever earlier batches left);
+ *   tile_lo_fine  float[tiles16 * ER_MAX_BATCH], [tile][frame], tiles16 = ceil(cols/16) * ceil(rows/16);
+ *   keys, masks   the batch's units in ascending key order and the frames that touch each (bit f = frame f); at most keys_cap are
+ *                 written, *n_keys is the number the batch has.
+ * Any output pointer may be NULL.  The kernels are the ones every batch runs: the hook adds no argument and no branch to them. */
+int er_tsdf_prepass_trace(er_tsdf_t h, int n, const uint16_t* depth, int depth_on_device, const double* T, const er_warp* warp,
+                          float* scaled, int* scaled_pad, float* tile_max, float* tile_lo, float* tile_lo_fine,
+                          int* keys, unsigned long long* masks, int keys_cap, int* n_keys);
+
 /* Device depth produced asynchronously: the pre-passes of the NEXT er_tsdf_integrate_frames calls (both internal pre-pass
  * streams) wait for this hipEvent_t (recorded by the caller after the producer of the depth buffer) instead of requiring a
  * synchronised stream.  (Host depth needs no event: it is read by the copy inside the call.) */
