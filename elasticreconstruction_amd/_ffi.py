@@ -15,7 +15,7 @@ SYMBOLS = [
     "er_last_error", "er_device_count", "er_abi_version", "er_request_hw_queues", "er_host_alloc", "er_host_free", "er_host_copy_h2d", "er_device_alloc", "er_device_free", "er_device_copy_d2h",
     "er_tsdf_create", "er_tsdf_destroy", "er_tsdf_set_stream", "er_tsdf_synchronize",
     "er_tsdf_wait_event", "er_tsdf_reset", "er_tsdf_status", "er_tsdf_set_unit_shard", "er_unit_owner",
-    "er_tsdf_scale_depth", "er_tsdf_reproject", "er_tsdf_integrate", "er_tsdf_integrate_frames", "er_tsdf_prepass_trace",
+    "er_tsdf_scale_depth", "er_tsdf_reproject", "er_tsdf_integrate", "er_tsdf_integrate_frames", "er_tsdf_prepass_trace", "er_tsdf_set_zbuf_epoch",
     "er_tsdf_unit_count", "er_tsdf_unit_keys", "er_tsdf_read_unit", "er_tsdf_sum_weight",
     "er_tsdf_extract_world", "er_tsdf_extract_surface", "er_tsdf_extract_oriented", "er_tsdf_extract_mesh", "er_mc_table", "er_tsdf_extract_mesh_indexed", "er_tsdf_import_world", "er_raycast_params_default", "er_tsdf_raycast", "er_tsdf_raycast_batch", "er_tsdf_export_weighted", "er_tsdf_import_weighted",
     "er_tsdf_export_raw", "er_tsdf_import_raw",
@@ -125,6 +125,8 @@ def lib():
     L.er_tsdf_integrate_frames.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.POINTER(ErWarp)]
     if hasattr(L, "er_tsdf_prepass_trace"):                     # (absent from an older build selected with ER_HIP_LIB)
         L.er_tsdf_prepass_trace.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.POINTER(ErWarp), vp, ip, vp, vp, vp, vp, vp, C.c_int, ip]
+    if hasattr(L, "er_tsdf_set_zbuf_epoch"):                    # (absent from an older build selected with ER_HIP_LIB)
+        L.er_tsdf_set_zbuf_epoch.argtypes = [vp, C.c_int, C.c_uint]
     L.er_tsdf_unit_count.argtypes = [vp, ip]
     L.er_tsdf_unit_keys.argtypes = [vp, vp]
     L.er_tsdf_read_unit.argtypes = [vp, C.c_int, vp, vp]

@@ -25,6 +25,11 @@ using namespace er;
 constexpr int kBlock = 256;
 constexpr int kEmptyKey = -1;
 constexpr uint32_t kZEmpty = 0xFFFFFFFFu;
+// A z-buffer cell is (0xFFFF - epoch) << 16 | depth, epoch = the buffer's use counter (1 .. kZEpochMax; the handle advances it once per batch or
+// single frame that scatters into the buffer).  A newer use's values compare below everything older uses left behind, so the scatter's atomicMin
+// overwrites stale cells, and the consumer takes a cell as empty unless its upper half carries the current tag: nobody re-arms the buffer.  It is
+// filled with 0xFF (= epoch 0, which no scatter uses) at create, at er_tsdf_reset and when the counter would wrap.
+constexpr uint32_t kZEpochMax = 0xFFFFu;
 
 // counters[] slots
 enum { C_NUNITS = 0, C_NBATCH = 1 /* and 6, 7: one per pipeline slot */, C_POOL_OVERFLOW = 2, C_TABLE_FULL = 3, C_OUT_OF_RANGE = 4,
@@ -33,6 +38,7 @@ enum { C_NUNITS = 0, C_NBATCH = 1 /* and 6, 7: one per pipeline slot */, C_POOL_
 constexpr int kDepth = 3;                // batches in flight: voxel pass of n, pre-passes of n+1 and n+2 (depth 2 with one pre-pass
 constexpr int kAux = 2;                  // stream = the round-1 pipeline: profiles/r02n_ab_pipeline_depth_hw_queues.txt); pre-pass streams:
                                          // batch b runs on stream b mod kAux
+constexpr int kZColor = kAux;            // index of the colour calls' z-buffer counter in er_tsdf_s::zepoch, behind the kAux pre-pass buffers'
 
 // ------------------------------------------------------------------------------------------------
 // Reproject, IntegrateApp.cpp:247-268: every source pixel is warped through its fragment's control
@@ -58,6 +64,7 @@ struct ReprojArgs {
   uint32_t* lastzero;
   uint32_t* zfix;                        // the replay's z-buffer (all-empty outside a replay; re-armed by the consumer)
   int* zero_flag;                        // int[2], bit f: frame f of the batch saw a write of dd == 0 (one pair per pre-pass stream)
+  uint32_t ztag;                         // (0xFFFF - epoch) << 16 of this use of zbuf (next_ztag)
 };
 __global__ void k_reproject_scatter(ReprojArgs A);
 
@@ -90,9 +97,9 @@ __global__ __launch_bounds__(kPrepThreads) void k_prepare(
     int* __restrict__ ht_key, int* __restrict__ ht_slot, unsigned long long* __restrict__ ht_mask, int cap_mask,
     int hash_shift, int* __restrict__ batch, int* __restrict__ nbatch,
     int* __restrict__ counters, float* __restrict__ tile_max, float* __restrict__ tile_lo, float* __restrict__ tile_lo_fine, int2 shard,
-    uint32_t* __restrict__ lastzero, uint32_t* __restrict__ zfix, const int* __restrict__ zero_flag);
-extern template __global__ void k_prepare<true>(const uint16_t* __restrict__, uint32_t* __restrict__, int, int, int, Camera, CameraInv, const float* __restrict__, const double* __restrict__, float* __restrict__, int* __restrict__, int* __restrict__, unsigned long long* __restrict__, int, int, int* __restrict__, int* __restrict__, int* __restrict__, float* __restrict__, float* __restrict__, float* __restrict__, int2, uint32_t* __restrict__, uint32_t* __restrict__, const int* __restrict__);
-extern template __global__ void k_prepare<false>(const uint16_t* __restrict__, uint32_t* __restrict__, int, int, int, Camera, CameraInv, const float* __restrict__, const double* __restrict__, float* __restrict__, int* __restrict__, int* __restrict__, unsigned long long* __restrict__, int, int, int* __restrict__, int* __restrict__, int* __restrict__, float* __restrict__, float* __restrict__, float* __restrict__, int2, uint32_t* __restrict__, uint32_t* __restrict__, const int* __restrict__);
+    uint32_t* __restrict__ lastzero, uint32_t* __restrict__ zfix, const int* __restrict__ zero_flag, uint32_t ztag);
+extern template __global__ void k_prepare<true>(const uint16_t* __restrict__, uint32_t* __restrict__, int, int, int, Camera, CameraInv, const float* __restrict__, const double* __restrict__, float* __restrict__, int* __restrict__, int* __restrict__, unsigned long long* __restrict__, int, int, int* __restrict__, int* __restrict__, int* __restrict__, float* __restrict__, float* __restrict__, float* __restrict__, int2, uint32_t* __restrict__, uint32_t* __restrict__, const int* __restrict__, uint32_t);
+extern template __global__ void k_prepare<false>(const uint16_t* __restrict__, uint32_t* __restrict__, int, int, int, Camera, CameraInv, const float* __restrict__, const double* __restrict__, float* __restrict__, int* __restrict__, int* __restrict__, unsigned long long* __restrict__, int, int, int* __restrict__, int* __restrict__, int* __restrict__, float* __restrict__, float* __restrict__, float* __restrict__, int2, uint32_t* __restrict__, uint32_t* __restrict__, const int* __restrict__, uint32_t);
 
 // k_plan's records and k_integrate's work items
 constexpr int kRows = 4;                  // register rows per lane of k_integrate: a wave owns an 8 x 4 x 8 box of voxels (2 x 4 x 8 lanes x 4 rows)
@@ -172,11 +179,11 @@ struct er_tsdf_s {
   int ctr_parity = 0, ctr_cur = 0;
   uint16_t* depth_stage[er_tsdf_k::kDepth] = {};              // host frames of the batch in flight, by pipeline slot
   uint32_t *zbuf[er_tsdf_k::kAux] = {}, *lastzero[er_tsdf_k::kAux] = {}, *zfix[er_tsdf_k::kAux] = {};  // Reproject's z-buffer and replay state, one per pre-pass stream
+  uint32_t zepoch[er_tsdf_k::kAux + 1] = {};              // use counters of zbuf[0], zbuf[1] and of the colour calls' z-buffer (kZColor); next_ztag advances them
   double *T12 = nullptr, *seg12 = nullptr, *madj12 = nullptr, *dsum = nullptr;
   int *grid_index = nullptr, *key_scratch = nullptr, *slot_scratch = nullptr;
   er_tsdf_k::PlanRec* plan_rec[er_tsdf_k::kDepth] = {};
   er_tsdf_k::Plan* plan[er_tsdf_k::kDepth] = {};
-  bool reset_pending[er_tsdf_k::kDepth] = {};                  // k_reset of the slot's last batch has not been launched yet
   size_t key_scratch_cap = 0;
   // profiling
   int prof_stride = 0;                              // 0 = off, n = time every n-th k_integrate launch
@@ -205,8 +212,11 @@ __attribute__((visibility("hidden"))) int check_flags(er_tsdf_t h);
 __attribute__((visibility("hidden"))) int resolve_slots(er_tsdf_t h, const int* keys_host, int n, bool allocate);
 // The units this GPU holds (without the ones handed to their owner), in ascending key order: keys and pool slots.  Calls check_flags.
 __attribute__((visibility("hidden"))) int sorted_units(er_tsdf_t h, std::vector<int>& keys, std::vector<int>& slots);
-// One frame (RA.n_frames == 1) reprojected on stream X into RA.zbuf and on into z_dev, 16-bit depth; zbuf, lastzero, zfix and the flag words are
-// left as they were found (all-empty / 0).
+// Advances the use counter `which` of the z-buffer zbuf (cells uint32) for one more scatter on stream X -- behind a fill with 0xFF on X when the
+// counter would wrap -- and returns the tag of this use in *ztag (ReprojArgs::ztag, k_prepare, k_zbuf_to_depth).
+__attribute__((visibility("hidden"))) int next_ztag(er_tsdf_t h, int which, uint32_t* zbuf, size_t cells, hipStream_t X, uint32_t* ztag);
+// One frame (RA.n_frames == 1) reprojected on stream X into RA.zbuf and on into z_dev, 16-bit depth; lastzero, zfix and the flag words are
+// left as they were found (all-empty / 0), zbuf holds stale cells of RA.ztag's epoch.
 __attribute__((visibility("hidden"))) int reproject_single(er_tsdf_t h, const ReprojArgs& RA, uint16_t* z_dev, hipStream_t X);
 // ---- er_tsdf_color.hip ----
 // Zeroes the colour accumulators of the n units whose slots stand in h->slot_scratch (behind resolve_slots, on h->stream); nothing without colour.

@@ -11,16 +11,17 @@
 //                                             twin of TSDFVolume::data_ (TSDFVolume.h:27)
 //   lambda    float[rows*cols]                ScaleDepth's per-pixel ray-length factor (camera constant)
 //   scaled    float[64][rows*cols]            scaled depth of every frame of the batch in flight
-//   zbuf      uint32[64][rows*cols]           Reproject's z-buffer (atomicMin; 0xFFFFFFFF = empty); lastzero / zfix: its replay state
+//   zbuf      uint32[64][rows*cols]           Reproject's z-buffer (atomicMin of epoch tag | depth, er_tsdf.h: kZEpochMax; a cell without the
+//                                             current tag is empty); lastzero / zfix: its replay state
 //
 // Launch sequence for a batch of <= 64 frames (er_tsdf_integrate_frames); three batches are in flight (run_batch):
 //  pre-pass stream (batch b on stream b mod 2):
-//   k_reset        clears the frame masks of the slot's previous batch (deferred from the main stream)
 //   [k_reproject_scatter -> k_reproject_fix]          per SOURCE pixel: warp + scatter-min   (A6/A7)
 //   k_prepare      per pixel: ScaleDepth + unit key; marks bit f in the unit's frame mask,   (A3/A5)
 //                  appends the unit to the batch list
 //   k_plan         hands new units their pool slots, writes one record {key, slot, frame mask} per unit of the batch in cost order
-//                  (frames in the mask) and resets the work queue k_integrate claims its items from
+//                  (frames in the mask) and resets the work queue k_integrate claims its items from; clears the frame masks and
+//                  the list behind its copies
 //  main stream:
 //   k_integrate    per wave an 8 x 4 x 8 box of a unit: each voxel is loaded ONCE, run against every (A4)
 //                  frame whose bit is set IN FRAME ORDER, stored once -> bit-identical to the reference's
@@ -57,7 +58,7 @@ __global__ void k_scale_depth(const uint16_t* __restrict__ depth, const float* _
 // The order-dependent case (a write of dd == 0 resets the cell: "0 means empty"), replayed exactly.  ONE launch of kFixBlocks
 // single-wave workgroups that return at once unless a frame of the batch is flagged -- practically never -- and otherwise share the
 // pixels of the flagged frames: every source pixel is warped again and scattered into zfix under the replay rule.  One phase, no
-// ordering between workgroups; the consumer merges (take_z, er_tsdf_dev.h) and re-arms lastzero / zfix, k_plan (or the single-frame entry
+// ordering between workgroups; the consumer merges (take_z, er_tsdf_dev.h) and re-arms lastzero / zfix (plain depths, no epoch tag), k_plan (or the single-frame entry
 // point) clears the flag words.  Single-wave workgroups with a capped register budget: they find a free wave slot at once next to the
 // persistent k_integrate workgroups (a 256-thread workgroup waited 46 us on average for four slots on one CU).
 __global__ __launch_bounds__(kFixThreads) __attribute__((amdgpu_num_vgpr(48))) void k_reproject_fix(ReprojArgs A) {
@@ -70,12 +71,11 @@ __global__ __launch_bounds__(kFixThreads) __attribute__((amdgpu_num_vgpr(48))) v
   }
 }
 
-__global__ void k_zbuf_to_depth(uint32_t* __restrict__ zbuf, uint16_t* __restrict__ depth, long total, uint32_t* __restrict__ lastzero,
-                                uint32_t* __restrict__ zfix, const int* __restrict__ zero_flag) {
+__global__ void k_zbuf_to_depth(const uint32_t* __restrict__ zbuf, uint16_t* __restrict__ depth, long total, uint32_t* __restrict__ lastzero,
+                                uint32_t* __restrict__ zfix, const int* __restrict__ zero_flag, uint32_t ztag) {
   long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= total) return;
-  uint32_t z = zbuf[t];
-  zbuf[t] = kZEmpty;                                                    // leave the z-buffer re-armed
+  uint32_t z = z_of_epoch(zbuf[t], ztag);                               // (the z-buffer is not re-armed: its next use has another tag)
   if (zero_flag[0] & 1) z = take_z(z, (size_t)t, lastzero, zfix);       // (single frame: bit 0)
   depth[t] = (z == kZEmpty) ? (uint16_t)0 : (uint16_t)z;
 }
@@ -118,11 +118,15 @@ __device__ int unit_slot_acquire(int e, int key, int* __restrict__ ht_slot, int*
   return slot;
 }
 
-__global__ __launch_bounds__(256) void k_plan(const int* __restrict__ batch, const int* __restrict__ nbatch,
-                                              const unsigned long long* __restrict__ ht_mask, const int* __restrict__ ht_key,
+//
+// The launch is also the last reader of the slot's frame masks, unit list and list length (k_integrate works from the copies in plan_rec), so it
+// hands them back empty to the slot's next k_prepare: each mask is cleared behind its copy, the unit visits (sum of popcounts) are accounted in
+// stats[0], and the length is zeroed behind the last barrier, when every thread has read it.
+__global__ __launch_bounds__(256) void k_plan(const int* __restrict__ batch, int* nbatch,
+                                              unsigned long long* __restrict__ ht_mask, const int* __restrict__ ht_key,
                                               int* __restrict__ ht_slot, int* __restrict__ unit_key, int max_units,
                                               int* __restrict__ counters, PlanRec* __restrict__ plan_rec, Plan* __restrict__ plan,
-                                              int* __restrict__ zero_flag) {
+                                              int* __restrict__ zero_flag, unsigned long long* __restrict__ stats) {
   __shared__ int hist[65];
   __shared__ int start[66];
   const int n = *nbatch;                            // <= hash capacity = size of plan_rec
@@ -141,9 +145,13 @@ __global__ __launch_bounds__(256) void k_plan(const int* __restrict__ batch, con
     if (zero_flag) zero_flag[0] = zero_flag[1] = 0;     // Reproject's replay flags of this batch: consumed by the k_prepare in front of this launch
   }
   __syncthreads();
+  if (threadIdx.x == 0) *nbatch = 0;
+  unsigned long long visits = 0;
   for (int t = threadIdx.x; t < n; t += blockDim.x) {
     const int e = batch[t];
     const unsigned long long mask = ht_mask[e];
+    ht_mask[e] = 0ull;                                                  // (a unit stands once in the list: nobody reads this mask again)
+    visits += (unsigned long long)__popcll(mask);
     const int key = ht_key[e];
     PlanRec r;
     r.key = key;
@@ -151,21 +159,7 @@ __global__ __launch_bounds__(256) void k_plan(const int* __restrict__ batch, con
     r.mask = mask;
     plan_rec[atomicAdd(&start[__popcll(mask)], 1)] = r;                 // position in descending cost order
   }
-}
-
-// Clears the frame masks of the batch list and accounts unit visits (sum of popcounts).
-__global__ void k_reset(const int* __restrict__ batch, int* __restrict__ nbatch, unsigned long long* __restrict__ ht_mask,
-                        unsigned long long* __restrict__ stats) {
-  const int n = *nbatch;
-  unsigned long long visits = 0;
-  for (int t = threadIdx.x; t < n; t += blockDim.x) {
-    const int e = batch[t];
-    visits += (unsigned long long)__popcll(ht_mask[e]);
-    ht_mask[e] = 0ull;
-  }
   if (visits) atomicAdd(&stats[0], visits);
-  __syncthreads();
-  if (threadIdx.x == 0) *nbatch = 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -246,9 +240,9 @@ int drain_events(er_tsdf_t h) {
   return 0;
 }
 
-// The voxel passes run on own_stream (run_batch).  Whoever is about to use h->stream for the volume -- check_flags, resolve_slots,
-// flush_resets, sync_all: every entry point passes one of them before it touches the pool or the tables -- first makes a caller's
-// stream wait for the last voxel pass.  Lazily, not at the end of er_tsdf_integrate_frames: a wait parked in the caller's stream
+// The voxel passes run on own_stream (run_batch).  Whoever is about to use h->stream for the volume or its accounts -- check_flags,
+// resolve_slots, the profile calls; sync_all waits for every stream: every entry point passes one of them before it touches the pool or
+// the tables -- first makes a caller's stream wait for the last voxel pass, and with it for every pre-pass in front of it.  Lazily, not at the end of er_tsdf_integrate_frames: a wait parked in the caller's stream
 // would hold up whatever shares its hardware queue, and the next call's "own_stream behind the caller's stream" would wait behind
 // it for nothing (-1.4 % with 8 queues, profiles/r07a_timeline_queues.txt).
 int join_voxel(er_tsdf_t h) {
@@ -283,6 +277,16 @@ int check_flags(er_tsdf_t h) {
   if (c[C_POOL_OVERFLOW])
     return er::fail("TSDF unit pool exhausted: %d units requested, capacity %d (raise max_units)", c[C_NUNITS], h->max_units);
   if (c[C_TABLE_FULL]) return er::fail("TSDF unit hash table full (capacity %d)", h->ht_cap);
+  return 0;
+}
+
+int next_ztag(er_tsdf_t h, int which, uint32_t* zbuf, size_t cells, hipStream_t X, uint32_t* ztag) {
+  if (h->zepoch[which] >= kZEpochMax) {                                 // the next tag would fall below nothing: start over from an empty buffer
+    ER_HIP_TRY(hipMemsetAsync(zbuf, 0xFF, cells * sizeof(uint32_t), X));
+    h->zepoch[which] = 0;
+  }
+  h->zepoch[which]++;
+  *ztag = (kZEpochMax - h->zepoch[which]) << 16;
   return 0;
 }
 
@@ -333,23 +337,7 @@ struct Staging {
   int gi[ER_MAX_BATCH];
 };
 
-// k_reset of a batch (clears the frame masks of its unit list, accounts the unit visits) is deferred: it runs on the pre-pass
-// stream of the batch that reuses the slot, off the main stream, whose per-batch chain is then ONE kernel.  Whoever needs the
-// accounts or leaves the pipeline (synchronise, profile read-out) flushes the pending ones on the main stream.
-int flush_resets(er_tsdf_t h) {
-  if (join_voxel(h)) return 1;                                          // (k_reset stands behind the slot's k_integrate)
-  for (int q = 0; q < kDepth; q++)
-    if (h->reset_pending[q]) {
-      hipLaunchKernelGGL(k_reset, dim3(1), dim3(kBlock), 0, h->stream, h->batch[q], h->counters + kNbatchSlot[q], h->ht_mask[q], h->stats);
-      ER_HIP_TRY(hipGetLastError());
-      ER_HIP_TRY(hipEventRecord(h->int_done[q], h->stream));            // the slot's next user waits for this reset as well
-      h->reset_pending[q] = false;
-    }
-  return 0;
-}
-
 int sync_all(er_tsdf_t h) {
-  if (flush_resets(h)) return 1;
   if (h->copy_stream) ER_HIP_TRY(hipStreamSynchronize(h->copy_stream));
   for (int a = 0; a < kAux; a++) ER_HIP_TRY(hipStreamSynchronize(h->aux_stream[a]));
   if (h->stream != h->own_stream) ER_HIP_TRY(hipStreamSynchronize(h->own_stream));
@@ -362,7 +350,7 @@ int sync_all(er_tsdf_t h) {
 // pre-passes run on the handle's auxiliary streams, which do not wait for the caller's stream).
 // Pipeline over three in-order streams.  Batch b owns pipeline slot p = b mod 3 and pre-pass stream X(b) = aux_stream[b mod 2]; V is
 // the voxel stream (own_stream):
-//   X(b): wait int_done[p] -> [k_reset(p) of batch b-3] -> H2D constants(p) -> [k_reproject_scatter -> k_reproject_fix] -> k_prepare(p) -> k_plan(p) -> event pre_done[p]
+//   X(b): wait int_done[p] -> H2D constants(p) -> [k_reproject_scatter -> k_reproject_fix] -> k_prepare(p) -> k_plan(p) -> event pre_done[p]
 //   V   : wait pre_done[p] -> k_integrate(p) -> event int_done[p]                          (ONE kernel per batch: it is the critical path)
 // so the pre-passes of batches b+1 and b+2 (latency / float64 bound, each a serial chain of launches) overlap each other and
 // k_integrate of batch b (float32 VALU bound): the two chains run staggered, one stream's scatter next to the other's k_prepare.
@@ -375,14 +363,17 @@ int sync_all(er_tsdf_t h) {
 //   pinned[p]            (host)     the host, batch b                 H2D constants(b) on X(b)             host waits consts_done[p] before batch b+3
 //   dstage[p] = frames[p], t12,     H2D constants(b) on X(b), behind  scatter, fix, k_prepare(b) on X(b);  X(b+3) waits int_done[p] of b: recorded on V behind
 //     seg, madj, gi                 int_done[p] of b-3                k_integrate(b) on V                  k_integrate(b), itself behind pre_done[p] of b
-//   zbuf / lastzero / zfix [b mod   scatter(b), fix(b); re-armed by   k_prepare(b), all on X(b)            the next writer is scatter(b+2) on the same
-//     2], zero-flag words [b mod 2] k_prepare(b), cleared by k_plan(b)                                     stream, behind k_plan(b): stream order
+//   zbuf / lastzero / zfix [b mod   scatter(b), fix(b); lastzero and  k_prepare(b), all on X(b)            the next writer is scatter(b+2) on the same
+//     2], zero-flag words [b mod 2] zfix re-armed by k_prepare(b),                                         stream, behind k_plan(b): stream order; zbuf is
+//                                   the flags cleared by k_plan(b)                                         not re-armed: scatter(b+2) writes under the next
+//                                                                                                          epoch's tag (next_ztag; a fill on X when it wraps)
 //   depth_stage[p] (host frames)    frame copy(b) on the copy stream  scatter(b), k_prepare(b) on X(b),    copy(b+3) waits pre_done[p] of batch b, which
 //                                   behind pre_done[p] of batch b-3   behind copy_done[p]                  k_plan(b) records behind both readers
-//   ht_mask[p], batch[p], nbatch[p] k_prepare(b); cleared by the      k_plan(b) on X(b)                    k_reset stands behind int_done[p] of b, hence
-//                                   k_reset on X(b+3) (or on          (k_integrate reads the mask from     behind k_plan(b); k_prepare(b+3) behind k_reset
-//                                   h->stream: flush_resets, which    plan_rec)                            in stream order, or behind the int_done[p] that
-//                                   re-records int_done[p] behind it)                                      flush_resets recorded
+//   ht_mask[p], batch[p], nbatch[p] k_prepare(b); cleared by          k_plan(b) on X(b), nobody else       k_prepare(b+3) on X(b+3) behind int_done[p] of b,
+//                                   k_plan(b), its only reader        (k_integrate reads the mask from     hence behind k_plan(b)
+//                                                                     plan_rec)
+//   stats[0] (unit visits)          k_plan(b), atomically             er_tsdf_get_profile; cleared by      both on h->stream behind join_voxel: the last voxel
+//                                                                     er_tsdf_set_profiling                pass stands behind every k_plan launched so far
 //   scaled[p], tile_max / tile_lo   k_prepare(b) on X(b)              k_integrate(b) on V, behind          k_prepare(b+3) on X(b+3) behind int_done[p] of b
 //     / tile_lo_fine [p]                                              pre_done[p]
 //   plan_rec[p], plan[p]            k_plan(b); the queue head by      k_integrate(b)                       k_plan(b+3) on X(b+3) behind int_done[p] of b
@@ -455,20 +446,17 @@ int run_batch(er_tsdf_t h, int n, const uint16_t* depth_dev, const double* T, co
     }
   }
   // all per-batch constants travel in ONE copy (every launch or copy on this stream costs ~5 us of the pre-pass chain)
-  if (h->used[p]) ER_HIP_TRY(hipStreamWaitEvent(X, h->int_done[p], 0));     // k_integrate of batch n-3 still reads dstage[p] / scaled[p] / masks[p]
-  if (h->reset_pending[p]) {
-    hipLaunchKernelGGL(k_reset, dim3(1), dim3(kBlock), 0, X, h->batch[p], nbatch, h->ht_mask[p], h->stats);
-    ER_HIP_TRY(hipGetLastError());
-    h->reset_pending[p] = false;
-  }
+  if (h->used[p]) ER_HIP_TRY(hipStreamWaitEvent(X, h->int_done[p], 0));     // k_integrate of batch n-3 still reads dstage[p] / scaled[p] / plan_rec[p]
   ER_HIP_TRY(hipMemcpyAsync(h->dstage[p], st, sizeof(Staging), hipMemcpyHostToDevice, X));
   ER_HIP_TRY(hipEventRecord(h->consts_done[p], X));
+  uint32_t ztag = 0;
   if (warp) {
-    // zbuf is all-empty here: filled at create, re-armed by its consumer (k_prepare / k_zbuf_to_depth)
+    // every cell of zbuf is empty under this batch's tag: what earlier batches left carries theirs
+    if (next_ztag(h, a, h->zbuf[a], (size_t)ER_MAX_BATCH * (size_t)h->pixels, X, &ztag)) return 1;
     const int verts = (warp->resolution + 1) * (warp->resolution + 1) * (warp->resolution + 1);
     const float grid_ul = warp->length / (float)warp->resolution;       // ControlGrid.cpp:19
     const ReprojArgs RA{depth_dev, n, h->cols, h->rows, h->cam, h->cami, dev_seg, dev_madj, dev_gi, h->ctr, warp->resolution, grid_ul,
-                        verts * 3, h->zbuf[a], h->lastzero[a], h->zfix[a], h->counters + kZeroFlagSlot[a]};
+                        verts * 3, h->zbuf[a], h->lastzero[a], h->zfix[a], h->counters + kZeroFlagSlot[a], ztag};
     if (launch_reproject(h, RA, n, X)) return 1;
     zsrc = h->zbuf[a];
   }
@@ -481,9 +469,9 @@ int run_batch(er_tsdf_t h, int n, const uint16_t* depth_dev, const double* T, co
                      depth_dev, zsrc, n, h->cols, h->rows, h->cam, h->cami, h->lambda, dev_t12, h->scaled[p], h->ht_key, h->ht_slot,
                      h->ht_mask[p], h->ht_cap - 1, h->ht_shift, h->batch[p], nbatch, h->counters,
                      h->tile_max[p], h->tile_lo[p], h->tile_lo_fine[p], make_int2(h->shard_rank, h->shard_world), h->lastzero[a], h->zfix[a],
-                     h->counters + kZeroFlagSlot[a]);
+                     h->counters + kZeroFlagSlot[a], ztag);
   hipLaunchKernelGGL(k_plan, dim3(1), dim3(256), 0, X, h->batch[p], nbatch, h->ht_mask[p], h->ht_key, h->ht_slot, h->unit_key, h->max_units,
-                     h->counters, h->plan_rec[p], h->plan[p], warp ? h->counters + kZeroFlagSlot[a] : (int*)nullptr);
+                     h->counters, h->plan_rec[p], h->plan[p], warp ? h->counters + kZeroFlagSlot[a] : (int*)nullptr, h->stats);
   ER_HIP_TRY(hipGetLastError());
   ER_HIP_TRY(hipEventRecord(h->pre_done[p], X));
 
@@ -505,7 +493,6 @@ int run_batch(er_tsdf_t h, int n, const uint16_t* depth_dev, const double* T, co
   }
   ER_HIP_TRY(hipGetLastError());
   ER_HIP_TRY(hipEventRecord(h->int_done[p], S));
-  h->reset_pending[p] = true;                               // (launched by the slot's next user, or by flush_resets)
   h->used[p] = true;
   h->frames_done += n;
   return 0;
@@ -794,11 +781,13 @@ int er_tsdf_reproject(er_tsdf_t h, uint16_t* depth_inout_host, const float* ctr_
   ER_HIP_TRY(hipMemcpyAsync(h->grid_index, &gi, sizeof(int), hipMemcpyHostToDevice, h->stream));
   const float grid_ul = length / (float)resolution;
   const long total = (long)px;
+  uint32_t ztag = 0;                                   // (every stream is idle: the fill of a wrapping counter may run on this one)
+  if (next_ztag(h, 0, h->zbuf[0], (size_t)ER_MAX_BATCH * px, h->stream, &ztag)) return 1;
   const ReprojArgs RA{h->depth_stage[0], 1, h->cols, h->rows, h->cam, h->cami, h->seg12, h->madj12, h->grid_index, h->ctr, resolution, grid_ul,
-                      verts * 3, h->zbuf[0], h->lastzero[0], h->zfix[0], h->counters + kZeroFlagSlot[0]};
+                      verts * 3, h->zbuf[0], h->lastzero[0], h->zfix[0], h->counters + kZeroFlagSlot[0], ztag};
   if (launch_reproject(h, RA, 1, h->stream)) return 1;
   hipLaunchKernelGGL(k_zbuf_to_depth, dim3((int)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, h->zbuf[0],
-                     h->depth_stage[0], total, h->lastzero[0], h->zfix[0], h->counters + kZeroFlagSlot[0]);
+                     h->depth_stage[0], total, h->lastzero[0], h->zfix[0], h->counters + kZeroFlagSlot[0], ztag);
   ER_HIP_TRY(hipGetLastError());
   ER_HIP_TRY(hipMemsetAsync(h->counters + kZeroFlagSlot[0], 0, 2 * sizeof(int), h->stream));
   ER_HIP_TRY(hipMemcpyAsync(depth_inout_host, h->depth_stage[0], px * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
@@ -865,8 +854,8 @@ int er_tsdf_integrate(er_tsdf_t h, const uint16_t* depth_host, const double T[16
   return er_tsdf_integrate_frames(h, 1, depth_host, 0, T, nullptr);
 }
 
-// Test hook (include/er_hip.h).  Nothing of the batch's pipeline slot is overwritten before the slot's next batch: k_reset (flushed by sync_all)
-// clears the hash map's frame masks and the list length, not plan_rec, which holds the {key, slot, mask} records k_integrate read.
+// Test hook (include/er_hip.h).  Nothing of the batch's pipeline slot that k_integrate read is overwritten before the slot's next batch: k_plan
+// clears the hash map's frame masks and the list length, not plan_rec, which holds the {key, slot, mask} records, nor plan->n_units.
 int er_tsdf_prepass_trace(er_tsdf_t h, int n, const uint16_t* depth, int depth_on_device, const double* T, const er_warp* warp,
                           float* scaled, int* scaled_pad, float* tile_max, float* tile_lo, float* tile_lo_fine,
                           int* keys, unsigned long long* masks, int keys_cap, int* n_keys) {
@@ -901,6 +890,22 @@ int er_tsdf_prepass_trace(er_tsdf_t h, int n, const uint16_t* depth, int depth_o
   return 0;
 }
 
+// Test hook (include/er_hip.h): the counter is only ever advanced, so that what earlier uses left in the buffer stays above the tags to come; a
+// smaller value is reached through a fill, like a wrap.
+int er_tsdf_set_zbuf_epoch(er_tsdf_t h, int which, unsigned epoch) {
+  if (!h) return er::fail("er_tsdf_set_zbuf_epoch: NULL handle");
+  if (which < 0 || which > kZColor) return er::fail("er_tsdf_set_zbuf_epoch: no z-buffer %d (0, 1: the pre-pass streams'; %d: the colour calls')", which, kZColor);
+  if (epoch > kZEpochMax) return er::fail("er_tsdf_set_zbuf_epoch: epoch %u above %u", epoch, kZEpochMax);
+  ER_HIP_TRY(hipSetDevice(h->device));
+  if (sync_all(h)) return 1;
+  if (which < kAux && epoch < h->zepoch[which]) {            // (the colour calls fill their buffer at every call)
+    ER_HIP_TRY(hipMemsetAsync(h->zbuf[which], 0xFF, (size_t)ER_MAX_BATCH * (size_t)h->pixels * sizeof(uint32_t), h->stream));
+    ER_HIP_TRY(hipStreamSynchronize(h->stream));
+  }
+  h->zepoch[which] = epoch;
+  return 0;
+}
+
 int er_tsdf_wait_event(er_tsdf_t h, void* hip_event) {
   if (!h || !hip_event) return er::fail("er_tsdf_wait_event: NULL argument");
   ER_HIP_TRY(hipSetDevice(h->device));
@@ -923,8 +928,12 @@ int er_tsdf_reset(er_tsdf_t h) {
   ER_HIP_TRY(hipMemsetAsync(h->ht_slot, 0xFF, (size_t)h->ht_cap * sizeof(int), s));
   for (int q = 0; q < kDepth; q++) ER_HIP_TRY(hipMemsetAsync(h->ht_mask[q], 0, (size_t)h->ht_cap * sizeof(unsigned long long), s));
   ER_HIP_TRY(hipMemsetAsync(h->counters, 0, C_COUNT * sizeof(int), s));
+  for (int q = 0; q < kAux; q++) {
+    ER_HIP_TRY(hipMemsetAsync(h->zbuf[q], 0xFF, (size_t)ER_MAX_BATCH * (size_t)h->pixels * sizeof(uint32_t), s));
+    h->zepoch[q] = 0;
+  }
   ER_HIP_TRY(hipStreamSynchronize(s));
-  for (int q = 0; q < kDepth; q++) h->used[q] = h->reset_pending[q] = false;
+  for (int q = 0; q < kDepth; q++) h->used[q] = false;
   h->batch_no = 0;
   h->dropped.clear();
   return 0;
@@ -1012,7 +1021,7 @@ int er_tsdf_sum_weight(er_tsdf_t h, double* sum) {
 int er_tsdf_set_profiling(er_tsdf_t h, int enable) {
   if (!h) return er::fail("er_tsdf_set_profiling: NULL handle");
   ER_HIP_TRY(hipSetDevice(h->device));
-  if (flush_resets(h) || drain_events(h)) return 1;         // (pending resets would add their unit visits after the counters are cleared)
+  if (join_voxel(h) || drain_events(h)) return 1;           // (behind every k_plan launched so far: their unit visits belong to the old account)
   h->prof_stride = enable > 0 ? enable : 0;
   h->prof_tick = 0;
   h->ms_total = 0.0;
@@ -1026,7 +1035,7 @@ int er_tsdf_get_profile(er_tsdf_t h, double* integrate_ms_total, long* integrate
                         long* unit_visits) {
   if (!h) return er::fail("er_tsdf_get_profile: NULL handle");
   ER_HIP_TRY(hipSetDevice(h->device));
-  if (flush_resets(h)) return 1;
+  if (join_voxel(h)) return 1;                              // (the last voxel pass stands behind every k_plan, which account the unit visits)
   ER_HIP_TRY(hipStreamSynchronize(h->stream));
   if (drain_events(h)) return 1;
   unsigned long long st[4] = {0, 0, 0, 0};
@@ -1044,12 +1053,12 @@ int er_tsdf_get_profile(er_tsdf_t h, double* integrate_ms_total, long* integrate
 namespace er_tsdf_k {
 
 // er_tsdf_reproject's device part for the colour calls (er_tsdf_color.hip): frame 0 of RA through k_reproject_scatter and k_reproject_fix into
-// RA.zbuf, then k_zbuf_to_depth into z_dev, which re-arms the three buffers; the flag words are cleared behind it.
+// RA.zbuf, then k_zbuf_to_depth into z_dev, which re-arms the two replay buffers; the flag words are cleared behind it.
 int reproject_single(er_tsdf_t h, const ReprojArgs& RA, uint16_t* z_dev, hipStream_t X) {
   if (launch_reproject(h, RA, 1, X)) return 1;
   const long total = (long)RA.cols * RA.rows;
   hipLaunchKernelGGL(k_zbuf_to_depth, dim3((int)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, X, RA.zbuf, z_dev, total, RA.lastzero, RA.zfix,
-                     RA.zero_flag);
+                     RA.zero_flag, RA.ztag);
   ER_HIP_TRY(hipGetLastError());
   ER_HIP_TRY(hipMemsetAsync(RA.zero_flag, 0, 2 * sizeof(int), X));
   return 0;

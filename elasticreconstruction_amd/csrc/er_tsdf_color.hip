@@ -215,7 +215,7 @@ int unit_slot(er_tsdf_t h, const char* who, int key, int* slot) {
 // The frames of a colour call: staged (host frames, kColorBatch at a time), warped into the virtual camera if there is a warp, and splatted --
 // or, for the single-frame hook er_tsdf_reproject_color (z_host, c_host != NULL; no T), the warped pair copied back instead.
 // Everything the warp needs lives in the colour scratch: its own copy of the lattices and per-frame matrices, and its own z-buffer, replay
-// buffers, flag words and winner words, armed here and re-armed by their consumers.  So a pre-pass stream that still works for a later batch
+// buffers, flag words and winner words, armed here and re-armed by their consumers (the z-buffer: emptied by the next frame's epoch tag).  So a pre-pass stream that still works for a later batch
 // shares nothing with it.
 int color_run(er_tsdf_t h, const char* who, int n, const uint16_t* depth, const uint8_t* rgb, int on_device, const double* T, const er_warp* warp,
               uint16_t* z_host, uint8_t* c_host, long stats[3]) {
@@ -260,7 +260,7 @@ int color_run(er_tsdf_t h, const char* who, int n, const uint16_t* depth, const 
     ER_HIP_TRY(hipMemcpyAsync(S + o_gi, warp->grid_index, (size_t)n * sizeof(int), hipMemcpyHostToDevice, X));
     ER_HIP_TRY(hipMemcpyAsync(S + o_ctr, warp->ctr, ctr_floats * sizeof(float), hipMemcpyHostToDevice, X));
     ER_HIP_TRY(hipMemsetAsync(S + o_flag, 0, 2 * sizeof(int), X));
-    ER_HIP_TRY(hipMemsetAsync(S + o_zbuf, 0xFF, px * 4, X));            // kZEmpty
+    ER_HIP_TRY(hipMemsetAsync(S + o_zbuf, 0xFF, px * 4, X));            // kZEmpty: above every epoch's tag (the scratch moves from call to call)
     ER_HIP_TRY(hipMemsetAsync(S + o_lz, 0, px * 4, X));
     ER_HIP_TRY(hipMemsetAsync(S + o_zfix, 0xFF, px * 4, X));
     ER_HIP_TRY(hipMemsetAsync(S + o_win, 0xFF, px * 4, X));
@@ -288,11 +288,13 @@ int color_run(er_tsdf_t h, const char* who, int n, const uint16_t* depth, const 
     uint32_t* win = reinterpret_cast<uint32_t*>(S + o_win);
     for (int f = 0; f < nb; f++) {                   // one frame at a time through the single-frame z-buffer
       const size_t F = (size_t)(start + f);
+      uint32_t ztag = 0;                             // the frame's own epoch: the z-buffer is not re-armed between frames (er_tsdf.h: kZEpochMax)
+      if (next_ztag(h, kZColor, reinterpret_cast<uint32_t*>(S + o_zbuf), px, X, &ztag)) return 1;
       const ReprojArgs RA{dd + (size_t)f * px, 1, h->cols, h->rows, h->cam, h->cami, reinterpret_cast<const double*>(S + o_seg) + F * 16,
                           reinterpret_cast<const double*>(S + o_madj) + F * 12, reinterpret_cast<const int*>(S + o_gi) + F,
                           reinterpret_cast<const float*>(S + o_ctr), warp->resolution, warp->length / (float)warp->resolution, (int)(verts * 3),
                           reinterpret_cast<uint32_t*>(S + o_zbuf), reinterpret_cast<uint32_t*>(S + o_lz), reinterpret_cast<uint32_t*>(S + o_zfix),
-                          reinterpret_cast<int*>(S + o_flag)};
+                          reinterpret_cast<int*>(S + o_flag), ztag};
       if (reproject_single(h, RA, Z, X)) return 1;
       hipLaunchKernelGGL(k_color_warp, dim3(blocks), dim3(kBlock), 0, X, RA, Z, win);
       hipLaunchKernelGGL(k_color_gather, dim3(blocks), dim3(kBlock), 0, X, dc + (size_t)f * px * 3, win, Cw, h->pixels);

@@ -42,7 +42,7 @@ __device__ __forceinline__ void scatter_px(const ReprojArgs& A, int f, int p, in
   const size_t o = (size_t)f * ((size_t)A.cols * A.rows) + cell;
   if (!replay) {
     if (dd != 0) {
-      atomicMin(&A.zbuf[o], (uint32_t)dd);
+      atomicMin(&A.zbuf[o], A.ztag | (uint32_t)dd);                    // below every cell of an older epoch (er_tsdf.h: kZEpochMax)
     } else {
       atomicMax(&A.lastzero[o], (uint32_t)p + 1u);
       atomicOr(&A.zero_flag[f >> 5], 1 << (f & 31));
@@ -66,6 +66,13 @@ __device__ __forceinline__ void reproject_scatter_px(const ReprojArgs& A, int f,
                     A.ctr + (size_t)A.grid_index[f] * A.floats_per_grid, A.res, A.grid_ul, cell, dd))
     return;
   scatter_px(A, f, p, cell, dd, replay);
+}
+
+// The consumer's reading of z-buffer cell z under the tag of the current epoch: the depth, or kZEmpty for a cell that this epoch's scatter did not
+// write (whatever an older one left there).
+__device__ __forceinline__ uint32_t z_of_epoch(uint32_t z, uint32_t ztag) {
+  const uint32_t x = z ^ ztag;
+  return x < 0x10000u ? x : kZEmpty;
 }
 
 // The consumer's half of the replay: the value of z-buffer cell o of a FLAGGED frame (z = what the plain scatter-min left there);

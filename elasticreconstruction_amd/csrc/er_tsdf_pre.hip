@@ -130,7 +130,7 @@ __global__ __launch_bounds__(kPrepThreads) void k_prepare(
     int* __restrict__ ht_key, int* __restrict__ ht_slot, unsigned long long* __restrict__ ht_mask, int cap_mask,
     int hash_shift, int* __restrict__ batch, int* __restrict__ nbatch,
     int* __restrict__ counters, float* __restrict__ tile_max, float* __restrict__ tile_lo, float* __restrict__ tile_lo_fine, int2 shard,
-    uint32_t* __restrict__ lastzero, uint32_t* __restrict__ zfix, const int* __restrict__ zero_flag) {
+    uint32_t* __restrict__ lastzero, uint32_t* __restrict__ zfix, const int* __restrict__ zero_flag, uint32_t ztag) {
   __shared__ int s_keys[kTileKeys];
   __shared__ int s_n;
   __shared__ float s_wmax[kPrepThreads / 64], s_wlo[kLoSub][kLoSub][kPrepSubWaves];
@@ -157,9 +157,8 @@ __global__ __launch_bounds__(kPrepThreads) void k_prepare(
   if constexpr (kWide) {
     if (in[0]) {
       if (zbuf) {
-        const uint4 zv = *reinterpret_cast<const uint4*>(zbuf + o);
-        *reinterpret_cast<uint4*>(zbuf + o) = make_uint4(kZEmpty, kZEmpty, kZEmpty, kZEmpty);   // re-arm the z-buffer for the next batch
-        uint32_t z[kPrepPix] = {zv.x, zv.y, zv.z, zv.w};
+        const uint4 zv = *reinterpret_cast<const uint4*>(zbuf + o);      // (read only: the next batch's epoch makes these cells empty)
+        uint32_t z[kPrepPix] = {z_of_epoch(zv.x, ztag), z_of_epoch(zv.y, ztag), z_of_epoch(zv.z, ztag), z_of_epoch(zv.w, ztag)};
         if (replayed) {
 #pragma unroll
           for (int j = 0; j < kPrepPix; j++) z[j] = take_z(z[j], o + j, lastzero, zfix);
@@ -185,8 +184,7 @@ __global__ __launch_bounds__(kPrepThreads) void k_prepare(
     for (int j = 0; j < kPrepPix; j++) {
       if (in[j]) {
         if (zbuf) {
-          uint32_t z = zbuf[o + j];
-          zbuf[o + j] = kZEmpty;                                        // re-arm the z-buffer for the next batch
+          uint32_t z = z_of_epoch(zbuf[o + j], ztag);
           if (replayed) z = take_z(z, o + j, lastzero, zfix);
           d[j] = (z == kZEmpty) ? (uint16_t)0 : (uint16_t)z;
         } else {
@@ -270,7 +268,7 @@ __global__ __launch_bounds__(kPrepThreads) void k_prepare(
                                         const double* __restrict__, float* __restrict__, int* __restrict__, int* __restrict__,                             \
                                         unsigned long long* __restrict__, int, int, int* __restrict__, int* __restrict__, int* __restrict__,               \
                                         float* __restrict__, float* __restrict__, float* __restrict__, int2, uint32_t* __restrict__,                       \
-                                        uint32_t* __restrict__, const int* __restrict__);
+                                        uint32_t* __restrict__, const int* __restrict__, uint32_t);
 ER_PREPARE_INST(true)
 ER_PREPARE_INST(false)
 #undef ER_PREPARE_INST

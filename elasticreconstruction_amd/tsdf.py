@@ -173,6 +173,11 @@ class TSDFVolume:
         return dict(scaled=scaled, pad=pad.value, tile_max=tmax[:, :, :n].copy(), tile_lo=tlo[:, :, :n].copy(),
                     tile_lo_fine=fine[:, :, :n].copy(), keys=keys[:nk.value].copy(), masks=masks[:nk.value].copy())
 
+    def set_zbuf_epoch(self, which, epoch):
+        """er_tsdf_set_zbuf_epoch (test hook): the use counter of reprojection z-buffer `which` (0, 1: batch b scatters into b mod 2, Reproject into
+        0; 2: the colour calls') as the next use finds it; the buffer refills itself when the counter would pass 0xFFFF."""
+        _ffi.check(self._lib.er_tsdf_set_zbuf_epoch(self._h, int(which), int(epoch)), "er_tsdf_set_zbuf_epoch")
+
     # -- data_ access ---------------------------------------------------------------------------
     def unit_count(self):
         n = C.c_int(0)

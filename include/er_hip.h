@@ -120,6 +120,12 @@ int er_tsdf_prepass_trace(er_tsdf_t h, int n, const uint16_t* depth, int depth_o
                           float* scaled, int* scaled_pad, float* tile_max, float* tile_lo, float* tile_lo_fine,
                           int* keys, unsigned long long* masks, int keys_cap, int* n_keys);
 
+/* Test hook: sets the use counter of one of the handle's reprojection z-buffers on a quiet handle -- which = 0, 1: the buffers of the two pre-pass
+ * streams (batch b of the handle scatters into buffer b mod 2; er_tsdf_reproject into buffer 0), 2: the buffer of the colour calls.  A cell of
+ * such a buffer holds (0xFFFF - counter) << 16 | depth; the counter advances once per batch or frame that scatters into the buffer and the
+ * buffer is refilled when it would pass 0xFFFF.  epoch <= 0xFFFF is the value the NEXT use advances from. */
+int er_tsdf_set_zbuf_epoch(er_tsdf_t h, int which, unsigned epoch);
+
 /* Device depth produced asynchronously: the pre-passes of the NEXT er_tsdf_integrate_frames calls (both internal pre-pass
  * streams) wait for this hipEvent_t (recorded by the caller after the producer of the depth buffer) instead of requiring a
  * synchronised stream.  (Host depth needs no event: it is read by the copy inside the call.) */
