@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <functional>
 #include <utility>
 #include <vector>
 
@@ -218,6 +219,29 @@ __attribute__((visibility("hidden"))) int next_ztag(er_tsdf_t h, int which, uint
 // One frame (RA.n_frames == 1) reprojected on stream X into RA.zbuf and on into z_dev, 16-bit depth; lastzero, zfix and the flag words are
 // left as they were found (all-empty / 0), zbuf holds stale cells of RA.ztag's epoch.
 __attribute__((visibility("hidden"))) int reproject_single(er_tsdf_t h, const ReprojArgs& RA, uint16_t* z_dev, hipStream_t X);
+// ---- er_tsdf_extract.hip, for er_mesh_cc.hip ----
+// The indexed mesh of er_tsdf_extract_mesh_indexed in device memory: nv float4 vertices, nv float4 normals, ntri x 3 int32 indices (each NULL
+// when it was not asked for or the mesh is empty).  `owned` is every device allocation of the call, the three arrays included; the kernels that
+// fill them may still be in flight on the handle's stream when mesh_indexed_on_device returns, hipFree waits for them.
+struct DeviceMesh {
+  long nv = 0, ntri = 0;
+  float4 *d_verts = nullptr, *d_nrm = nullptr;
+  int* d_tri = nullptr;
+  std::vector<void*> owned;
+  DeviceMesh() = default;
+  DeviceMesh(const DeviceMesh&) = delete;
+  DeviceMesh& operator=(const DeviceMesh&) = delete;
+  ~DeviceMesh() {
+    for (void* p : owned) (void)hipFree(p);
+  }
+};
+// Lists the units (*n_vertices = *n_triangles = 0 from then on), counts the mesh of the resident volume, sets the two counts, calls
+// counted(nv, ntri) -- which refuses what the caller has to refuse, reporting it (non-zero ends the call with 1) -- and then enqueues on
+// h->stream the kernels that write the arrays asked for (normals need want_v).  An empty volume returns 0 without calling counted.
+// Failures are reported under `who`.
+__attribute__((visibility("hidden"))) int mesh_indexed_on_device(er_tsdf_t h, const char* who, bool want_v, bool want_n, bool want_t,
+                                                                 long* n_vertices, long* n_triangles, const std::function<int(long, long)>& counted,
+                                                                 DeviceMesh* m);
 // ---- er_tsdf_color.hip ----
 // Zeroes the colour accumulators of the n units whose slots stand in h->slot_scratch (behind resolve_slots, on h->stream); nothing without colour.
 __attribute__((visibility("hidden"))) int color_zero_slots(er_tsdf_t h, int n);

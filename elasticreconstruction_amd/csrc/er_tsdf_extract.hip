@@ -812,19 +812,40 @@ int er_tsdf_extract_mesh_indexed(er_tsdf_t h, float* verts_host, float* normals_
   const char* who = "er_tsdf_extract_mesh_indexed";
   if (!h || !n_vertices || !n_triangles) return er::fail("er_tsdf_extract_mesh_indexed: NULL argument");
   ER_HIP_TRY(hipSetDevice(h->device));
+  const bool want_v = verts_host || normals_host;
+  DeviceMesh m;
+  auto counted = [&](long nv, long ntri) {
+    if (nv > (long)INT_MAX) return er::fail("er_tsdf_extract_mesh_indexed: %ld vertices; the limit is 2^31 - 1 (int32 indices)", nv);
+    if (want_v && capacity_vertices < nv) return er::fail("er_tsdf_extract_mesh_indexed: capacity %ld < %ld vertices", capacity_vertices, nv);
+    if (tri_host && capacity_triangles < ntri) return er::fail("er_tsdf_extract_mesh_indexed: capacity %ld < %ld triangles", capacity_triangles, ntri);
+    return 0;                                                // (nothing has been written to the host)
+  };
+  if (mesh_indexed_on_device(h, who, want_v, normals_host != nullptr, tri_host != nullptr, n_vertices, n_triangles, counted, &m)) return 1;
+  if (m.d_verts && verts_host) ER_W(who, hipMemcpyAsync(verts_host, m.d_verts, (size_t)m.nv * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
+  if (m.d_nrm) ER_W(who, hipMemcpyAsync(normals_host, m.d_nrm, (size_t)m.nv * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
+  if (m.d_tri) ER_W(who, hipMemcpyAsync(tri_host, m.d_tri, (size_t)m.ntri * 3 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (m.d_verts || m.d_tri) ER_W(who, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+}  // extern "C"
+
+// The indexed mesh left ON THE DEVICE (er_tsdf.h): the body of er_tsdf_extract_mesh_indexed, which copies the three arrays back, and the
+// first stage of er_tsdf_extract_mesh_cleaned (er_mesh_cc.hip), which goes on working on them in HBM.
+int er_tsdf_k::mesh_indexed_on_device(er_tsdf_t h, const char* who, bool want_v, bool want_n, bool want_t,
+                                      long* n_vertices, long* n_triangles, const std::function<int(long, long)>& counted, DeviceMesh* m) {
   std::vector<int> keys, slots;
   if (sorted_units(h, keys, slots)) return 1;
   const int n = (int)keys.size();
   *n_vertices = *n_triangles = 0;
-  if (n == 0) return 0;
+  if (n == 0) return 0;                                     // (an empty volume: 0 and 0)
   const int nslab = n * 64;
   const size_t nrow = (size_t)nslab * 64;
   SlabPass t;
   unsigned char* d_tab = nullptr;
   unsigned long long* d_bm = nullptr;     // [row][axis]: the edge bitmap
-  int *d_rank = nullptr, *d_rowoff = nullptr, *d_tri = nullptr;
+  int *d_rank = nullptr, *d_rowoff = nullptr;
   long *d_vcnt = nullptr, *d_voff = nullptr;
-  float4 *d_verts = nullptr, *d_nrm = nullptr;
   std::vector<int> rank((size_t)h->max_units, -1);           // pool slot -> position in the key order; -1: a dropped unit's slot
   for (int r = 0; r < n; r++) rank[(size_t)slots[(size_t)r]] = r;
   long ntri = 0, nv = 0;
@@ -859,36 +880,37 @@ int er_tsdf_extract_mesh_indexed(er_tsdf_t h, float* verts_host, float* normals_
     vcnt[(size_t)s] = nv;                                    // (now the slab's offset)
     nv += c;
   }
-  *n_vertices = nv;
-  *n_triangles = ntri;
-  if (nv > (long)INT_MAX) return er::fail("er_tsdf_extract_mesh_indexed: %ld vertices; the limit is 2^31 - 1 (int32 indices)", nv);
-  const bool want_v = verts_host || normals_host;
-  if (want_v && capacity_vertices < nv) return er::fail("er_tsdf_extract_mesh_indexed: capacity %ld < %ld vertices", capacity_vertices, nv);
-  if (tri_host && capacity_triangles < ntri) return er::fail("er_tsdf_extract_mesh_indexed: capacity %ld < %ld triangles", capacity_triangles, ntri);
-  if (nv == 0 || (!want_v && !tri_host)) return 0;           // (nothing has been written to the host)
+  *n_vertices = m->nv = nv;
+  *n_triangles = m->ntri = ntri;
+  if (counted(nv, ntri)) return 1;
+  if (nv == 0 || (!want_v && !want_t)) return 0;
   ER_W(who, hipMemcpyAsync(d_voff, vcnt.data(), (size_t)nslab * sizeof(long), hipMemcpyHostToDevice, h->stream));
   if (want_v) {
-    ER_W_OWNED(who, t, &d_verts, (size_t)nv * sizeof(float4));
+    ER_W_OWNED(who, t, &m->d_verts, (size_t)nv * sizeof(float4));
     hipLaunchKernelGGL(k_mesh_verts, dim3(nslab), dim3(64), 0, h->stream, h->pool, t.d_slots, t.d_keys, h->ht_key, h->ht_slot, h->ht_cap - 1, h->ht_shift,
-                       d_bm, d_rowoff, d_voff, d_verts);
+                       d_bm, d_rowoff, d_voff, m->d_verts);
     ER_W(who, hipGetLastError());
-    if (verts_host) ER_W(who, hipMemcpyAsync(verts_host, d_verts, (size_t)nv * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
-    if (normals_host) {
-      ER_W_OWNED(who, t, &d_nrm, (size_t)nv * sizeof(float4));
+    if (want_n) {
+      ER_W_OWNED(who, t, &m->d_nrm, (size_t)nv * sizeof(float4));
       hipLaunchKernelGGL(k_surface_normals, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, h->stream, h->pool, h->ht_key, h->ht_slot, h->ht_cap - 1,
-                         h->ht_shift, d_verts, nv, d_nrm);
+                         h->ht_shift, m->d_verts, nv, m->d_nrm);
       ER_W(who, hipGetLastError());
-      ER_W(who, hipMemcpyAsync(normals_host, d_nrm, (size_t)nv * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
     }
   }
-  if (tri_host) {
-    ER_W_OWNED(who, t, &d_tri, (size_t)ntri * 3 * sizeof(int));
-    if (t.upload_offsets(h, who) || launch(d_tri, 1)) return 1;
-    ER_W(who, hipMemcpyAsync(tri_host, d_tri, (size_t)ntri * 3 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (want_t) {
+    ER_W_OWNED(who, t, &m->d_tri, (size_t)ntri * 3 * sizeof(int));
+    if (t.upload_offsets(h, who) || launch(m->d_tri, 1)) return 1;
   }
-  ER_W(who, hipStreamSynchronize(h->stream));
+  // the kernels are still in flight on h->stream: everything they read or write now belongs to the caller's DeviceMesh
+  for (void* p : {(void*)t.d_keys, (void*)t.d_slots, (void*)t.d_cnt, (void*)t.d_off}) m->owned.push_back(p);
+  m->owned.insert(m->owned.end(), t.more.begin(), t.more.end());
+  t.d_keys = t.d_slots = nullptr;
+  t.d_cnt = t.d_off = nullptr;
+  t.more.clear();
   return 0;
 }
+
+extern "C" {
 
 int er_tsdf_import_world(er_tsdf_t h, const float* xyzi_host, long n, int* n_units) {
   const char* who = "er_tsdf_import_world";

@@ -24,6 +24,8 @@
 //                         (er_tsdf_extract_oriented, inside the cube [0, length)); single-GPU runs only
 //   --save_mesh <file.ply>   after the run also write the volume's marching-cubes mesh: indexed, with normals, binary PLY
 //                         (er_tsdf_extract_mesh_indexed; bin/MeshOutput makes the same kind of file from world.pcd); single-GPU runs only
+//   --mesh_min_triangles <n>, --mesh_largest_only   with --save_mesh: the mesh without the connected components that have fewer than n
+//                         triangles / without all but the largest (er_tsdf_extract_mesh_cleaned); refused without --save_mesh
 //   --color_raw <file> | --color_list <txt>   the colour stream registered to the depth stream: raw 640x480x3 bytes per frame,
 //                         or one 8-bit RGB / RGBA PNG per line, line i = frame i, inflated ahead like the depth PNGs.  The colour of each
 //                         batch of frames is splatted into the volume after the batch is integrated (er_tsdf_color_frames) and --save_mesh
@@ -79,6 +81,8 @@ int print_help() {
   std::cout << "    --device <gpu> (0)  --max_units <n> (2048)  --batch <frames> (64)" << std::endl;
   std::cout << "    --save_fragment <pcd_file> [--fragment_length <m> (3.0)] : also write the volume's surface points with normals, cloud_bin-style (single GPU only)" << std::endl;
   std::cout << "    --save_mesh <ply_file>          : also write the volume's marching-cubes mesh, indexed, with normals, binary PLY (single GPU only)" << std::endl;
+  std::cout << "    --mesh_min_triangles <n>        : with --save_mesh: drop the connected components of the mesh that have fewer than n triangles" << std::endl;
+  std::cout << "    --mesh_largest_only             : with --save_mesh: keep only the connected component with the most triangles" << std::endl;
   std::cout << "    --color_raw <raw_file> | --color_list <txt> : 640x480x3 bytes per frame | 8-bit RGB PNG per line; needs --save_mesh, which then writes colours (single GPU only)" << std::endl;
   std::cout << "    --gpus <N> (1)  --shard frame|unit (frame: frame blocks + the merge by unit owner over RCCL; unit: bit-exact, no collective)  --merge_root <g>  --force_merge" << std::endl;
   return 0;
@@ -405,12 +409,22 @@ struct App {
 
   // --save_mesh: the indexed marching-cubes mesh of the resident volume as binary PLY with normals (er_tsdf_extract_mesh_indexed) -- what
   // bin/MeshOutput makes of world.pcd, without the file in between and from the voxels SaveWorld's filter drops as well
-  bool SaveMesh(const std::string& filename) {
-    long nv = 0, nt = 0;
-    if (er_tsdf_extract_mesh_indexed(volume_, nullptr, nullptr, 0, nullptr, 0, &nv, &nt) != 0) { fprintf(stderr, "Integrate: %s\n", er_last_error()); return false; }
+  // min_triangles > 1 or largest_only: without its small connected components (er_tsdf_extract_mesh_cleaned; the unfiltered mesh stays on the device)
+  bool SaveMesh(const std::string& filename, long min_triangles = 0, bool largest_only = false) {
+    long nv = 0, nt = 0, stats[4] = {0, 0, 0, 0};
+    const bool clean = min_triangles > 1 || largest_only;
+    auto extract = [&](float* v, float* q, int* t) {
+      return clean ? er_tsdf_extract_mesh_cleaned(volume_, min_triangles, largest_only ? 1 : 0, v, q, nullptr, nv, t, nt, &nv, &nt, stats)
+                   : er_tsdf_extract_mesh_indexed(volume_, v, q, nv, t, nt, &nv, &nt);
+    };
+    if (extract(nullptr, nullptr, nullptr) != 0) { fprintf(stderr, "Integrate: %s\n", er_last_error()); return false; }
     std::vector<float> verts((size_t)nv * 4), nrm((size_t)nv * 4);
     std::vector<int> tris((size_t)nt * 3);
-    if (nv > 0 && er_tsdf_extract_mesh_indexed(volume_, verts.data(), nrm.data(), nv, tris.data(), nt, &nv, &nt) != 0) { fprintf(stderr, "Integrate: %s\n", er_last_error()); return false; }
+    if (nv > 0 && extract(verts.data(), nrm.data(), tris.data()) != 0) { fprintf(stderr, "Integrate: %s\n", er_last_error()); return false; }
+    if (clean) {
+      erfmt::stage_done("mesh cleaning (er_tsdf_extract_mesh_cleaned)");
+      printf("%ld of %ld mesh components kept, %ld vertices and %ld triangles dropped.\n", stats[1], stats[0], stats[2], stats[3]);
+    }
     static const float none[4] = {0.f, 0.f, 0.f, 0.f};                 // (an empty mesh still declares nx ny nz)
     std::vector<uint8_t> rgba((size_t)nv * 4 + 4);                      // with colour: er_tsdf_sample_colors at the vertices
     long levels[2] = {0, 0};
@@ -520,6 +534,10 @@ int main(int argc, char* argv[]) {
   parse_argument(argc, argv, "--fragment_length", fragment_length);
   std::string mesh_file;                                                // --save_mesh <file.ply>: the indexed mesh of the volume
   parse_argument(argc, argv, "--save_mesh", mesh_file);
+  int mesh_min_triangles = 0;                                           // --mesh_min_triangles N, --mesh_largest_only: the mesh without its small components
+  parse_argument(argc, argv, "--mesh_min_triangles", mesh_min_triangles);
+  const bool mesh_largest_only = find_switch(argc, argv, "--mesh_largest_only");
+  const bool mesh_clean_given = mesh_largest_only || find_argument(argc, argv, "--mesh_min_triangles") > 0;
   std::string color_raw, color_list;                                    // --color_raw <file> | --color_list <txt>: the colour stream
   parse_argument(argc, argv, "--color_raw", color_raw);
   parse_argument(argc, argv, "--color_list", color_list);
@@ -545,6 +563,8 @@ int main(int argc, char* argv[]) {
     fprintf(stderr, "Integrate: --save_mesh needs the whole volume on one GPU; it is not available with --gpus %d\n", gpus);
     return 1;
   }
+  if (mesh_clean_given && mesh_file.empty()) { fprintf(stderr, "Integrate: --mesh_min_triangles / --mesh_largest_only need --save_mesh\n"); return 1; }
+  if (mesh_min_triangles < 0) { fprintf(stderr, "Integrate: --mesh_min_triangles must not be negative\n"); return 1; }
   if (color) {
     if (!color_raw.empty() && !color_list.empty()) { fprintf(stderr, "Integrate: give --color_raw or --color_list, not both\n"); return 1; }
     if (mesh_file.empty()) { fprintf(stderr, "Integrate: --color_raw / --color_list need --save_mesh (world.pcd has no field for colour)\n"); return 1; }
@@ -681,7 +701,7 @@ int main(int argc, char* argv[]) {
     stage_done("SaveFragment");
   }
   if (rc == 0 && !mesh_file.empty()) {
-    if (!apps[0].SaveMesh(mesh_file)) rc = 1;
+    if (!apps[0].SaveMesh(mesh_file, mesh_min_triangles, mesh_largest_only)) rc = 1;
     stage_done("SaveMesh");
   }
   std::cout << "Total " << last_id << " frames processed." << std::endl;

@@ -1,14 +1,16 @@
 // MeshOutput -- the last box of the reference workflow (README.txt:100-103: "pcl_kinfu_largeScale_mesh_output world.pcd", a tool of the
 // author's PCL fork, outside the reference tree): world.pcd in, a triangle mesh out, with the numeric core on MI355X through liber_hip.so.
 //
-//   MeshOutput <world.pcd> [--save_to mesh.ply] [--ascii] [--no_normals] [--device D]
+//   MeshOutput <world.pcd> [--save_to mesh.ply] [--ascii] [--no_normals] [--min_triangles N] [--largest_only] [--device D]
 //
 // world.pcd is TSDFVolume::SaveWorld's voxel list (FIELDS x y z intensity; ascii, binary or binary_compressed): integer voxel indices and
 // the sdf.  The list goes back into a volume sized from its own unit keys (er_tsdf_import_world: every listed voxel observed with weight 1),
 // the volume's marching-cubes mesh comes out indexed with a normal per vertex (er_tsdf_extract_mesh_indexed), and the mesh is written as
 // PLY (binary little endian unless --ascii; nx ny nz unless --no_normals; a vertex without a normal gets 0 0 0).  The mesh is the one of the
 // voxels the file holds: SaveWorld drops |sdf| >= 0.98 and unobserved voxels, so cells next to those are missing here and present in
-// `Integrate --save_mesh`, which reads the resident volume.  ER_TIMING=1 prints the stages.
+// `Integrate --save_mesh`, which reads the resident volume.  --min_triangles N drops the connected components of the mesh that have fewer than
+// N triangles, --largest_only all but the one with the most (er_tsdf_extract_mesh_cleaned: the unfiltered mesh never leaves the device);
+// without the two the file is the unfiltered mesh.  ER_TIMING=1 prints the stages.
 #include <cmath>
 #include <cstdio>
 #include <string>
@@ -27,6 +29,8 @@ int print_help() {
          "  --save_to <file> (=mesh.ply)  the mesh: indexed triangles, PLY\n"
          "  --ascii                   write an ascii PLY (default: binary_little_endian)\n"
          "  --no_normals              leave out the per-vertex normals nx ny nz\n"
+         "  --min_triangles <n> (=0)  drop the connected components of the mesh that have fewer than n triangles\n"
+         "  --largest_only            keep only the connected component with the most triangles\n"
          "  --device <gpu> (=0)\n"
          "  -h [ --help ]             print this message\n");
   return 0;
@@ -43,6 +47,13 @@ int main(int argc, char** argv) {
   parse_argument(argc, argv, "--save_to", out_file);
   parse_argument(argc, argv, "--device", device);
   const bool ascii = find_switch(argc, argv, "--ascii"), no_normals = find_switch(argc, argv, "--no_normals");
+  int min_triangles = 0;
+  parse_argument(argc, argv, "--min_triangles", min_triangles);
+  const bool largest_only = find_switch(argc, argv, "--largest_only"), clean = min_triangles > 1 || largest_only;
+  if (min_triangles < 0) {
+    fprintf(stderr, "%s: --min_triangles must not be negative\n", kWho);
+    return 1;
+  }
 
   std::vector<std::vector<float>> cols;
   size_t n = 0;
@@ -89,19 +100,23 @@ int main(int argc, char** argv) {
   }
   stage_done("HIP runtime up, volume created");
   int rc = 0, n_units = 0;
-  long nv = 0, nt = 0;
+  long nv = 0, nt = 0, stats[4] = {0, 0, 0, 0};
   std::vector<float> verts, nrm;
   std::vector<int> tris;
   if (er_tsdf_import_world(vol, rows.data(), (long)n, &n_units) != 0) rc = 1;
   stage_done("import (er_tsdf_import_world)");
-  if (rc == 0 && er_tsdf_extract_mesh_indexed(vol, nullptr, nullptr, 0, nullptr, 0, &nv, &nt) != 0) rc = 1;
+  auto extract = [&](float* v, float* q, int* t) {
+    return clean ? er_tsdf_extract_mesh_cleaned(vol, min_triangles, largest_only ? 1 : 0, v, q, nullptr, nv, t, nt, &nv, &nt, stats)
+                 : er_tsdf_extract_mesh_indexed(vol, v, q, nv, t, nt, &nv, &nt);
+  };
+  if (rc == 0 && extract(nullptr, nullptr, nullptr) != 0) rc = 1;
   if (rc == 0 && nv > 0) {
     verts.resize((size_t)nv * 4);
     if (!no_normals) nrm.resize((size_t)nv * 4);
     tris.resize((size_t)nt * 3);
-    if (er_tsdf_extract_mesh_indexed(vol, verts.data(), no_normals ? nullptr : nrm.data(), nv, tris.data(), nt, &nv, &nt) != 0) rc = 1;
+    if (extract(verts.data(), no_normals ? nullptr : nrm.data(), tris.data()) != 0) rc = 1;
   }
-  stage_done("mesh (er_tsdf_extract_mesh_indexed)");
+  stage_done(clean ? "mesh and cleaning (er_tsdf_extract_mesh_cleaned)" : "mesh (er_tsdf_extract_mesh_indexed)");
   if (rc != 0) {
     fprintf(stderr, "%s: %s\n", kWho, er_last_error());
     er_tsdf_destroy(vol);
@@ -114,6 +129,7 @@ int main(int argc, char** argv) {
     return 1;
   }
   stage_done("write PLY");
+  if (clean) printf("%s: %ld of %ld components kept, %ld vertices and %ld triangles dropped\n", kWho, stats[1], stats[0], stats[2], stats[3]);
   printf("%s: %zu voxels in %d units -> %ld vertices, %ld triangles -> %s\n", kWho, n, n_units, nv, nt, out_file.c_str());
   er_tsdf_destroy(vol);
   return 0;

@@ -310,12 +310,42 @@ class TSDFVolume:
             return verts, np.ascontiguousarray(nrm[:, :3]), tris, self.sample_colors(verts)
         return verts, np.ascontiguousarray(nrm[:, :3]), tris
 
-    def SaveMesh(self, filename, normals=True, binary=True, colors=None):
+    def extract_clean_mesh(self, min_triangles=0, largest_only=False, colors=False, stats=False):
+        """extract_indexed_mesh without its small connected components (er_tsdf_extract_mesh_cleaned; the unfiltered mesh never leaves the
+        device): (verts, normals, tris, index[, rgba][, stats]) in extract_indexed_mesh's layouts.  A component -- vertices joined by
+        triangles -- is kept iff it has at least min_triangles triangles and, with largest_only, is the one with the most (a tie goes to the
+        one that holds the lowest vertex); kept vertices and triangles keep their order, index int32[n] is each kept vertex's position in the
+        unfiltered mesh.  colors = True appends sample_colors(verts); stats = True appends (components found, components kept, vertices
+        dropped, triangles dropped)."""
+        nv, nt = C.c_long(0), C.c_long(0)
+        st = (C.c_long * 4)(0, 0, 0, 0)
+        call = self._lib.er_tsdf_extract_mesh_cleaned
+        _ffi.check(call(self._h, int(min_triangles), int(bool(largest_only)), None, None, None, 0, None, 0, C.byref(nv), C.byref(nt), st),
+                   "er_tsdf_extract_mesh_cleaned")
+        verts = np.empty((nv.value, 4), dtype=np.float32)
+        nrm = np.empty((nv.value, 4), dtype=np.float32)
+        index = np.empty(nv.value, dtype=np.int32)
+        tris = np.empty((nt.value, 3), dtype=np.int32)
+        if nv.value:
+            _ffi.check(call(self._h, int(min_triangles), int(bool(largest_only)), _ffi.ptr(verts), _ffi.ptr(nrm), _ffi.ptr(index), nv.value,
+                            _ffi.ptr(tris), nt.value, C.byref(nv), C.byref(nt), st), "er_tsdf_extract_mesh_cleaned")
+        out = (verts, np.ascontiguousarray(nrm[:, :3]), tris, index)
+        if colors:
+            out += (self.sample_colors(verts),)
+        if stats:
+            out += ((st[0], st[1], st[2], st[3]),)
+        return out
+
+    def SaveMesh(self, filename, normals=True, binary=True, colors=None, min_triangles=0, largest_only=False):
         """The indexed mesh of the resident volume as PLY (formats.save_ply; NaN normals become 0 0 0).  colors = None: per-vertex colours iff
-        colour is enabled on the volume; False suppresses them; True demands them.  Returns (vertices, triangles)."""
+        colour is enabled on the volume; False suppresses them; True demands them.  min_triangles > 1 or largest_only: the cleaned mesh of
+        extract_clean_mesh.  Returns (vertices, triangles)."""
         if colors is None:
             colors = self.color_enabled_
-        if colors:
+        if min_triangles > 1 or largest_only:
+            got = self.extract_clean_mesh(min_triangles, largest_only, colors=bool(colors))
+            verts, nrm, tris, rgba = got[0], got[1], got[2], (got[4] if colors else None)
+        elif colors:
             verts, nrm, tris, rgba = self.extract_indexed_mesh(colors=True)
         else:
             (verts, nrm, tris), rgba = self.extract_indexed_mesh(), None

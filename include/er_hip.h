@@ -199,6 +199,37 @@ int er_mc_table(unsigned char out[256 * 16]);
 int er_tsdf_extract_mesh_indexed(er_tsdf_t h, float* verts_host, float* normals_host, long capacity_vertices, int* tri_host,
                                  long capacity_triangles, long* n_vertices, long* n_triangles);
 
+/* Mesh cleaning: the connected components of an indexed mesh, and the mesh without its small ones.  Definitions, for a mesh
+ * of nv vertices and nt triangles int32[nt][3]:
+ *   - two vertices are connected if one triangle names both; components are the transitive closure;
+ *   - a vertex that no triangle names is a component of its own with 0 triangles;
+ *   - a triangle that repeats a vertex (a a b) is legal and connects what it names; duplicate triangles count as often as they occur;
+ *   - label[v] is the smallest vertex index of v's component, count[v] the number of triangles in v's component, and the number of
+ *     components the number of v with label[v] == v;
+ *   - the filter, with min_triangles >= 0 and a flag largest_only: a component is kept iff count >= min_triangles and, with largest_only, it
+ *     is also the component with the most triangles (a tie goes to the smaller label).  0 and 1 keep everything.  largest_only with a largest
+ *     component below min_triangles gives the empty mesh and succeeds;
+ *   - the cleaned mesh: kept vertices in their original order, kept triangles in their original order; a triangle is kept iff its vertices
+ *     are; an index becomes the number of kept vertices before it; index[i] is the unfiltered index of cleaned vertex i.
+ * Every result is defined without reference to any order of execution: the same bytes on every call.
+ *
+ * er_mesh_components labels any indexed mesh held in host memory on `device`.  label_host [n_vertices], count_host [n_vertices] and rounds
+ * (the labelling rounds the call needed, a diagnostic) are nullable.  Refused: a NULL argument, negative sizes, n_vertices > 2^31 - 1, no
+ * device, and an index outside [0, n_vertices) -- naming the first offending triangle in triangle order, found before any kernel uses an index
+ * as an address, with nothing written.  n_triangles == 0 succeeds, every vertex its own component. */
+int er_mesh_components(const int* tri_host, long n_triangles, long n_vertices, int device, int* label_host, long* count_host, long* n_components,
+                       int* rounds);
+
+/* er_tsdf_extract_mesh_indexed's mesh filtered as above, without the unfiltered mesh leaving device memory: extraction, labelling, selection
+ * and compaction run there and only the cleaned arrays are copied back.  verts_host / normals_host: 4 floats per cleaned vertex in
+ * er_tsdf_extract_mesh_indexed's layouts; index_host: its index in the unfiltered mesh; tri_host: 3 ints per kept triangle.  Any output
+ * pointer may be NULL; all NULL: only counts, those after filtering.  A capacity that is too small is refused with the need in the message,
+ * after the counts (and stats) have been set, and nothing is written.  An empty volume gives 0 and 0.  stats (nullable): components found,
+ * components kept, vertices dropped, triangles dropped.  With min_triangles <= 1 and largest_only == 0 the three arrays are
+ * er_tsdf_extract_mesh_indexed's bit for bit.  A negative min_triangles is refused. */
+int er_tsdf_extract_mesh_cleaned(er_tsdf_t h, long min_triangles, int largest_only, float* verts_host, float* normals_host, int* index_host,
+                                 long capacity_vertices, int* tri_host, long capacity_triangles, long* n_vertices, long* n_triangles, long stats[4]);
+
 /* TSDFVolume::SaveWorld's inverse: a world.pcd voxel list back into a volume.  xyzi_host: n rows x y z intensity in er_tsdf_extract_world's
  * layout -- x, y, z integer voxel indices as floats, i + (xi - 256) * 64; intensity = the sdf.  Afterwards every listed voxel is (intensity, 1)
  * and every other voxel of a created unit (+0, 0); the created units are those with at least one listed voxel, *n_units (nullable) their number.
