@@ -21,7 +21,7 @@ SYMBOLS = [
     "er_tsdf_export_raw", "er_tsdf_import_raw",
     "er_tsdf_color_enable", "er_tsdf_read_unit_color", "er_tsdf_write_unit_color", "er_tsdf_color_frames", "er_tsdf_reproject_color", "er_tsdf_sample_colors",
     "er_tsdf_band_sizes", "er_tsdf_export_band", "er_tsdf_merge_band", "er_tsdf_import_band", "er_tsdf_drop_units",
-    "er_tsdf_set_profiling", "er_tsdf_get_profile",
+    "er_tsdf_set_profiling", "er_tsdf_get_profile", "er_tsdf_set_timeline", "er_tsdf_get_timeline",
     "er_comm_unique_id", "er_comm_create", "er_comm_create_local", "er_comm_create_loopback", "er_comm_destroy", "er_comm_rank", "er_comm_world",
     "er_tsdf_allreduce", "er_comm_merge_stats", "er_comm_merge_stats_owner", "er_frame_block",
     "er_cloud_create", "er_cloud_create_batch", "er_cloud_create_from_tsdf", "er_cloud_destroy", "er_cloud_size",
@@ -187,6 +187,9 @@ def lib():
     L.er_frame_block.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip]
     L.er_tsdf_set_profiling.argtypes = [vp, C.c_int]
     L.er_tsdf_get_profile.argtypes = [vp, dp, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)]
+    if hasattr(L, "er_tsdf_set_timeline"):                      # (absent from an older build selected with ER_HIP_LIB)
+        L.er_tsdf_set_timeline.argtypes = [vp, C.c_int]
+        L.er_tsdf_get_timeline.argtypes = [vp, C.c_int, vp, vp, ip]
     if hasattr(L, "er_cloud_create"):
         L.er_cloud_create.argtypes = [vp, vp, C.c_int, C.c_float, C.c_int, C.POINTER(vp)]
         L.er_cloud_create_batch.argtypes = [C.c_int, vp, vp, vp, C.c_float, C.c_int, vp]

@@ -192,6 +192,18 @@ struct er_tsdf_s {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
   double ms_total = 0.0;
   long launches = 0, frames_done = 0;
+  // timeline of the batch pipeline (er_tsdf_set_timeline): while off, run_batch creates and records nothing
+  struct TimelineRow {
+    long batch;
+    int slot, stream, frames;
+    double host_ms[3];                              // against tl_host0
+    hipEvent_t ev[7];                               // X: behind the int_done wait, the constants copy, k_reproject_fix, k_prepare, k_plan; V: round k_integrate
+  };
+  bool tl_on = false;
+  hipEvent_t tl_base = nullptr;                     // recorded (and waited for) when the hook is switched on; tl_host0 is the host's clock just behind it
+  double tl_host0 = 0.0;
+  std::vector<TimelineRow> tl_rows;
+  std::vector<hipEvent_t> tl_free;                  // timing events of rows already read, for the next rows
   // round 6 (owner merge): units this GPU handed to their owner -- zeroed, still in the table, hidden from every key / count / extraction query until
   // the next frame is integrated or the unit is imported again -- and the grow-only device scratch of the band kernels
   std::vector<int> dropped;                         // sorted

@@ -32,6 +32,9 @@
 // and the band records of the multi-GPU merge live in er_tsdf_extract.hip and er_tsdf_band.hip.
 #include "er_tsdf_dev.h"
 
+#include <chrono>
+#include <climits>
+
 namespace {
 
 using namespace er_tsdf_k;
@@ -216,6 +219,14 @@ __global__ void k_ensure_units(const int* __restrict__ keys, int n, int* __restr
   slots_out[t] = slot;
 }
 
+// n16 16-byte words and `tail` (< 4) 4-byte words behind them from a page-locked block of the handle, read in place, into device memory
+// (fetch_pinned says why this is not a hipMemcpyAsync).  One load per thread for the per-batch constants; a grid-stride loop for more.
+__global__ __launch_bounds__(kBlock) void k_fetch_pinned(const uint4* __restrict__ src, uint4* __restrict__ dst, int n16, int tail) {
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n16; i += gridDim.x * kBlock) dst[i] = src[i];
+  if (blockIdx.x == 0 && (int)threadIdx.x < tail)
+    reinterpret_cast<uint32_t*>(dst + n16)[threadIdx.x] = reinterpret_cast<const uint32_t*>(src + n16)[threadIdx.x];
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -337,6 +348,52 @@ struct Staging {
   int gi[ER_MAX_BATCH];
 };
 
+// `bytes` (a multiple of 4) from a page-locked block of the handle (hipHostMalloc: mapped into the device's address space) to device memory,
+// on stream s, by a kernel that reads the block in place.  Not hipMemcpyAsync: the runtime's host-to-device copy path stalls the calling
+// thread for 5 - 9 ms a few times per process -- at copies number 8, 15 and about 25 of a fresh process and then once or twice more, at a
+// moment that the timing of the first passes moves about -- and such a stall empties the pipeline, which runs 1.3 ms ahead of the device:
+// one of them in a 3000-frame pass is 16 ms against 23 (profiles/r10a_slow_mode.txt).  A kernel launch takes the path of every other launch
+// of the pipeline; what the host wrote before the launch is visible to the kernel, and the event recorded behind it frees the block.
+int fetch_pinned(void* dst, void* pinned, size_t bytes, hipStream_t s) {
+  void* src = nullptr;
+  ER_HIP_TRY(hipHostGetDevicePointer(&src, pinned, 0));
+  const size_t n16 = bytes / 16;
+  if (bytes % 4 != 0 || n16 > (size_t)INT_MAX) return er::fail("fetch_pinned: %zu bytes", bytes);
+  const int blocks = (int)std::min<size_t>(std::max<size_t>((n16 + kBlock - 1) / kBlock, 1), 64);
+  hipLaunchKernelGGL(k_fetch_pinned, dim3(blocks), dim3(kBlock), 0, s, static_cast<const uint4*>(src), static_cast<uint4*>(dst), (int)n16,
+                     (int)(bytes % 16 / 4));
+  ER_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+double host_now_ms() {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// One timing event of a timeline row, recorded on s: an event of a row already read, or a new one.
+int tl_record(er_tsdf_t h, hipEvent_t* e, hipStream_t s) {
+  if (!h->tl_free.empty()) {
+    *e = h->tl_free.back();
+    h->tl_free.pop_back();
+  } else {
+    ER_HIP_TRY(hipEventCreate(e));
+  }
+  ER_HIP_TRY(hipEventRecord(*e, s));
+  return 0;
+}
+
+// Waits for the rows' events and hands them back for re-use.
+int tl_drop_rows(er_tsdf_t h) {
+  for (auto& r : h->tl_rows)
+    for (hipEvent_t e : r.ev)
+      if (e) {
+        ER_HIP_TRY(hipEventSynchronize(e));
+        h->tl_free.push_back(e);
+      }
+  h->tl_rows.clear();
+  return 0;
+}
+
 int sync_all(er_tsdf_t h) {
   if (h->copy_stream) ER_HIP_TRY(hipStreamSynchronize(h->copy_stream));
   for (int a = 0; a < kAux; a++) ER_HIP_TRY(hipStreamSynchronize(h->aux_stream[a]));
@@ -399,11 +456,17 @@ int sync_all(er_tsdf_t h) {
 int run_batch(er_tsdf_t h, int n, const uint16_t* depth_dev, const double* T, const er_warp* warp, int frame0) {
   const int p = (int)(h->batch_no % kDepth), a = (int)(h->batch_no % kAux);
   h->batch_no++;
+  er_tsdf_s::TimelineRow* tl = nullptr;                     // (the vector only grows here: the pointer holds until the batch returns)
+  if (h->tl_on) {
+    h->tl_rows.push_back(er_tsdf_s::TimelineRow{h->batch_no - 1, p, a, n, {host_now_ms() - h->tl_host0, 0.0, 0.0}, {}});
+    tl = &h->tl_rows.back();
+  }
   // Slot p was last used by batch n-3.  The HOST only needs its pinned constants block back (the H2D copy of batch n-3, an
   // early event); the DEVICE buffers of the slot (scaled depth, masks, frame constants) are protected on the device: the
   // pre-pass stream waits for k_integrate of batch n-3 before it touches them.  The host therefore never blocks on a voxel
   // pass and runs up to three batches ahead (host-frame copies and pre-passes queue up behind the events).
   if (h->used[p]) ER_HIP_TRY(hipEventSynchronize(h->consts_done[p]));
+  if (tl) tl->host_ms[1] = host_now_ms() - h->tl_host0;
   Staging* st = static_cast<Staging*>(h->pinned[p]);
   for (int f = 0; f < n; f++) {
     const double* Tf = T + (size_t)f * 16;
@@ -445,10 +508,13 @@ int run_batch(er_tsdf_t h, int n, const uint16_t* depth_dev, const double* T, co
       st->gi[f] = g;
     }
   }
-  // all per-batch constants travel in ONE copy (every launch or copy on this stream costs ~5 us of the pre-pass chain)
+  // all per-batch constants travel in ONE copy kernel (every launch on this stream costs ~5 us of the pre-pass chain)
   if (h->used[p]) ER_HIP_TRY(hipStreamWaitEvent(X, h->int_done[p], 0));     // k_integrate of batch n-3 still reads dstage[p] / scaled[p] / plan_rec[p]
-  ER_HIP_TRY(hipMemcpyAsync(h->dstage[p], st, sizeof(Staging), hipMemcpyHostToDevice, X));
+  if (tl && tl_record(h, &tl->ev[0], X)) return 1;
+  static_assert(sizeof(Staging) % 4 == 0, "fetch_pinned copies 4-byte words");
+  if (fetch_pinned(h->dstage[p], st, sizeof(Staging), X)) return 1;
   ER_HIP_TRY(hipEventRecord(h->consts_done[p], X));
+  if (tl && tl_record(h, &tl->ev[1], X)) return 1;
   uint32_t ztag = 0;
   if (warp) {
     // every cell of zbuf is empty under this batch's tag: what earlier batches left carries theirs
@@ -460,6 +526,7 @@ int run_batch(er_tsdf_t h, int n, const uint16_t* depth_dev, const double* T, co
     if (launch_reproject(h, RA, n, X)) return 1;
     zsrc = h->zbuf[a];
   }
+  if (tl && tl_record(h, &tl->ev[2], X)) return 1;
 
   // wide accesses (16 bytes per array and thread, 8 for the 16-bit depth): every frame base must be a multiple of four elements -- cols % 4 == 0
   // gives that for the handle's own buffers -- and a caller's device depth, which may sit at any 2-byte boundary, 8-byte aligned (the warped
@@ -470,12 +537,15 @@ int run_batch(er_tsdf_t h, int n, const uint16_t* depth_dev, const double* T, co
                      h->ht_mask[p], h->ht_cap - 1, h->ht_shift, h->batch[p], nbatch, h->counters,
                      h->tile_max[p], h->tile_lo[p], h->tile_lo_fine[p], make_int2(h->shard_rank, h->shard_world), h->lastzero[a], h->zfix[a],
                      h->counters + kZeroFlagSlot[a], ztag);
+  if (tl && tl_record(h, &tl->ev[3], X)) return 1;
   hipLaunchKernelGGL(k_plan, dim3(1), dim3(256), 0, X, h->batch[p], nbatch, h->ht_mask[p], h->ht_key, h->ht_slot, h->unit_key, h->max_units,
                      h->counters, h->plan_rec[p], h->plan[p], warp ? h->counters + kZeroFlagSlot[a] : (int*)nullptr, h->stats);
   ER_HIP_TRY(hipGetLastError());
+  if (tl && tl_record(h, &tl->ev[4], X)) return 1;
   ER_HIP_TRY(hipEventRecord(h->pre_done[p], X));
 
   ER_HIP_TRY(hipStreamWaitEvent(S, h->pre_done[p], 0));
+  if (tl && tl_record(h, &tl->ev[5], S)) return 1;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   const bool timed = h->prof_stride > 0 && (h->prof_tick++ % h->prof_stride) == 0;
   if (timed) {
@@ -492,9 +562,11 @@ int run_batch(er_tsdf_t h, int n, const uint16_t* depth_dev, const double* T, co
     h->events.emplace_back(e0, e1);
   }
   ER_HIP_TRY(hipGetLastError());
+  if (tl && tl_record(h, &tl->ev[6], S)) return 1;
   ER_HIP_TRY(hipEventRecord(h->int_done[p], S));
   h->used[p] = true;
   h->frames_done += n;
+  if (tl) tl->host_ms[2] = host_now_ms() - h->tl_host0;
   return 0;
 }
 
@@ -637,6 +709,11 @@ int er_tsdf_destroy(er_tsdf_t h) {
   }
   for (int a = 0; a < kAux; a++)
     if (h->aux_stream[a]) (void)hipStreamSynchronize(h->aux_stream[a]);
+  for (auto& r : h->tl_rows)
+    for (hipEvent_t e : r.ev)
+      if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : h->tl_free) (void)hipEventDestroy(e);
+  if (h->tl_base) (void)hipEventDestroy(h->tl_base);
   std::vector<void*> ptrs = {h->pool, h->ht_key, h->ht_slot, h->unit_key, h->counters, h->stats, h->lambda, h->T12, h->seg12, h->madj12,
                              h->grid_index, h->dsum, h->ctr_dev[0], h->ctr_dev[1], h->key_scratch,
                              h->slot_scratch, h->band_scratch, h->color, h->color_scratch};
@@ -742,7 +819,7 @@ static int upload_ctr(er_tsdf_t h, const float* ctr, int res, int num_grids, hip
   if (h->ctr_rd_set[q])                                     // the pre-passes of two calls ago read this device buffer
     for (int a = 0; a < kAux; a++)
       if (a != a0) ER_HIP_TRY(hipStreamWaitEvent(C, h->ctr_rd[q][a], 0));
-  ER_HIP_TRY(hipMemcpyAsync(h->ctr_dev[q], h->ctr_pinned[q], floats * sizeof(float), hipMemcpyHostToDevice, C));
+  if (fetch_pinned(h->ctr_dev[q], h->ctr_pinned[q], floats * sizeof(float), C)) return 1;
   ER_HIP_TRY(hipEventRecord(h->ctr_ev[q], C));
   for (int a = 0; a < kAux; a++)
     if (a != a0) ER_HIP_TRY(hipStreamWaitEvent(h->aux_stream[a], h->ctr_ev[q], 0));
@@ -1047,6 +1124,50 @@ int er_tsdf_get_profile(er_tsdf_t h, double* integrate_ms_total, long* integrate
   return 0;
 }
 
+int er_tsdf_set_timeline(er_tsdf_t h, int on) {
+  if (!h) return er::fail("er_tsdf_set_timeline: NULL handle");
+  ER_HIP_TRY(hipSetDevice(h->device));
+  h->tl_on = false;
+  if (!on) return 0;                                         // (batches in flight keep their events; the rows stay readable)
+  if (sync_all(h) || tl_drop_rows(h)) return 1;
+  if (!h->tl_base) ER_HIP_TRY(hipEventCreate(&h->tl_base));
+  ER_HIP_TRY(hipEventRecord(h->tl_base, h->own_stream));
+  ER_HIP_TRY(hipEventSynchronize(h->tl_base));
+  h->tl_host0 = host_now_ms();
+  h->tl_on = true;
+  return 0;
+}
+
+int er_tsdf_get_timeline(er_tsdf_t h, int cap, long long* meta, double* times_ms, int* n_rows) {
+  if (!h || !n_rows) return er::fail("er_tsdf_get_timeline: NULL argument");
+  ER_HIP_TRY(hipSetDevice(h->device));
+  *n_rows = (int)h->tl_rows.size();
+  if (!meta || !times_ms) return 0;
+  if (cap < 0) return er::fail("er_tsdf_get_timeline: negative capacity");
+  const int n = std::min(cap, *n_rows);
+  *n_rows = 0;
+  for (int i = 0; i < n; i++) {
+    const er_tsdf_s::TimelineRow& r = h->tl_rows[(size_t)i];
+    long long* m = meta + (size_t)i * ER_TIMELINE_META;
+    double* t = times_ms + (size_t)i * ER_TIMELINE_TIMES;
+    m[0] = r.batch;
+    m[1] = r.slot;
+    m[2] = r.stream;
+    m[3] = r.frames;
+    for (int q = 0; q < 3; q++) t[q] = r.host_ms[q];
+    for (int q = 0; q < 7; q++) {
+      float ms = -1.f;                                       // (a batch that failed half-way leaves the rest of its row unrecorded)
+      if (r.ev[q]) {
+        ER_HIP_TRY(hipEventSynchronize(r.ev[q]));
+        ER_HIP_TRY(hipEventElapsedTime(&ms, h->tl_base, r.ev[q]));
+      }
+      t[3 + q] = (double)ms;
+    }
+  }
+  if (tl_drop_rows(h)) return 1;
+  *n_rows = n;
+  return 0;
+}
 
 }  // extern "C"
 

@@ -490,6 +490,23 @@ class TSDFVolume:
         _ffi.check(self._lib.er_tsdf_get_profile(self._h, C.byref(ms), C.byref(ln), C.byref(fr), C.byref(uv)), "er_tsdf_get_profile")
         return {"integrate_ms": ms.value, "launches": ln.value, "frames": fr.value, "unit_visits": uv.value}
 
+    TIMELINE_COLUMNS = ("host_in", "host_consts", "host_out", "x_wait", "x_consts", "x_fix", "x_prepare", "x_plan", "v_begin", "v_end")
+
+    def set_timeline(self, on):
+        """er_tsdf_set_timeline: record host and device times of every batch (include/er_hip.h); off by default."""
+        _ffi.check(self._lib.er_tsdf_set_timeline(self._h, int(bool(on))), "er_tsdf_set_timeline")
+
+    def get_timeline(self):
+        """er_tsdf_get_timeline: waits for the recorded batches and returns one dict per batch, in order -- batch, slot, stream, frames and
+        the TIMELINE_COLUMNS in ms since set_timeline(True); clears the record."""
+        n = C.c_int(0)
+        _ffi.check(self._lib.er_tsdf_get_timeline(self._h, 0, None, None, C.byref(n)), "er_tsdf_get_timeline")
+        meta = np.zeros((max(n.value, 1), 4), np.int64)
+        t = np.zeros((max(n.value, 1), len(self.TIMELINE_COLUMNS)), np.float64)
+        _ffi.check(self._lib.er_tsdf_get_timeline(self._h, n.value, _ffi.ptr(meta), _ffi.ptr(t), C.byref(n)), "er_tsdf_get_timeline")
+        return [dict(batch=int(m[0]), slot=int(m[1]), stream=int(m[2]), frames=int(m[3]), **dict(zip(self.TIMELINE_COLUMNS, map(float, r))))
+                for m, r in zip(meta[:n.value], t[:n.value])]
+
 
 def raycast_batch(jobs, depth=True):
     """er_tsdf_raycast_batch: a list of ray-casts in ONE launch.  jobs: dicts (or tuples in this order) of volume (a TSDFVolume), T

@@ -412,6 +412,24 @@ int er_tsdf_set_profiling(er_tsdf_t h, int enable);
 int er_tsdf_get_profile(er_tsdf_t h, double* integrate_ms_total, long* integrate_launches, long* frames,
                         long* unit_visits);
 
+/* Timeline of the batch pipeline (scripts/slow_mode_probe.py).  While on, every batch of er_tsdf_integrate_frames records the host's monotonic
+ * clock at three points and seven timing events on its two streams; off (the default) no event is created or recorded.  Switching on waits
+ * for the handle's streams, drops what an earlier recording left and records the base event every time is measured against; switching off only
+ * stops the recording, also with batches in flight: what was recorded stays readable.
+ * er_tsdf_get_timeline waits for the recorded batches and returns one row per batch, in order.  meta: ER_TIMELINE_META long long per row --
+ * batch number (it restarts at er_tsdf_reset), pipeline slot, pre-pass stream, frames.  times_ms: ER_TIMELINE_TIMES doubles per row, all in
+ * ms since the hook was switched on --
+ *   0..2  host: entry of the batch, behind the wait for the slot's page-locked constants block, return;
+ *   3..7  pre-pass stream: behind the wait for the slot's last voxel pass, behind the constants copy, behind k_reproject_fix (without a warp
+ *         nothing runs there: the stream as it stands), behind k_prepare, behind k_plan;
+ *   8, 9  voxel stream: in front of and behind k_integrate.
+ * With meta or times_ms NULL only *n_rows is set (the rows recorded so far; nothing is waited for).  Otherwise the first min(cap, rows) rows
+ * are written, *n_rows is their number and the record is CLEARED. */
+#define ER_TIMELINE_META 4
+#define ER_TIMELINE_TIMES 10
+int er_tsdf_set_timeline(er_tsdf_t h, int on);
+int er_tsdf_get_timeline(er_tsdf_t h, int cap, long long* meta, double* times_ms, int* n_rows);
+
 /* ------------------------------------------------------------- path B: ICP ---- */
 typedef struct er_cloud_s* er_cloud_t;
 
