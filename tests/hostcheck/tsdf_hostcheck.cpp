@@ -4,6 +4,10 @@
 // ascending order per voxel, scatter-min re-projection -- in plain loops, so the arithmetic the GPU will
 // execute can be compared with the oracle on a machine that has no GPU.  Never shipped, never loaded by
 // the product: tests/test_hostcheck.py builds it into tests/hostcheck/_build/.
+// hc_set_patch_shape chooses the voxel patch a "wave" owns; shape 3 is the 8 x 4 x 8 box of today's k_integrate, and with it every box is also
+// walked through a statement-for-statement copy of the kernel's frame loop (walk_box) whose events -- which exit of the pipeline, where runs of
+// full frames fall, which branch of apply_full, why the sure shortcut was declined, ... -- are counted (hc_events) and whose result is held to
+// the replay's (hc_walk_violations).  hc_write_unit plants a state, so a replay can start from what er_tsdf_import_raw delivers.
 #include "../../elasticreconstruction_amd/csrc/er_tsdf_math.h"
 
 #include <algorithm>
@@ -15,10 +19,158 @@ using namespace er;
 
 struct HcUnit { std::vector<float> sdf, w; std::vector<int> frames; };
 static int g_lo_shift = 4;             // granularity of the second-level tile_lo in the replay (k_prepare: 16-pixel tiles; 5 = no second level)
-static int g_patch_shape = 1;          // 1 = the 4 x 8 x 8 box k_integrate gives a wave (default), 2 = the 8 x 8 x 8 cube of mid round 3, 0 = a 16 x 16 square of one slab
-struct HcVolume { Camera cam; CameraInv cami; int cols, rows; std::map<int, HcUnit> units; long culled = 0, kept = 0, inside = 0, inside_violations = 0, sure = 0, visited = 0, unsure_pf = 0, sure_violations = 0, full_pf = 0, full_violations = 0, exact_rows = 0, exact_rows_needing = 0; };
+static int g_patch_shape = 1;          // 3 = the 8 x 4 x 8 box k_integrate gives a wave today, 1 = the 4 x 8 x 8 box of rounds 3-5 (default), 2 = the 8 x 8 x 8 cube of mid round 3, 0 = a 16 x 16 square of one slab
+
+// The PATH TALLY (patch shape 3 only): next to the per-voxel replay below, every (unit, box) of a call is also walked the way k_integrate's frame
+// loop walks it -- mn / mf, the two-stage pipeline with its alternating sample registers, runs_before, apply_full, the sure test, the store
+// predicate -- on a copy of the box, and what the walk meets is counted.  The walk's result is never written to the volume (the per-voxel replay
+// stays the arithmetic); it is compared with the replay's, voxel by voxel (walk_violations).  One count per occurrence.
+#define HC_EVENTS(X) \
+  X(E_ALL_CULLED) X(E_FULL_ONLY) X(E_PROJ_1) X(E_PROJ_2) X(E_PROJ_3) X(E_PROJ_4) X(E_PROJ_5PLUS) \
+  X(E_RUN_BEFORE_FIRST) X(E_RUN_BETWEEN) X(E_RUN_AFTER_LAST) X(E_RUN_LEN_GE2) \
+  X(E_FULL_TRIVIAL) X(E_FULL_DIVIDE) X(E_FULL_DIVIDE_LEN_GE2) X(E_FRAME63_PROJECTED) X(E_FRAME63_FULL) \
+  X(E_SURE_TAKEN) X(E_SURE_DECLINED_UNSURE) X(E_SURE_DECLINED_NONTRIVIAL) \
+  X(E_PROJ_INSIDE) X(E_PROJ_TESTED) X(E_PROJ_PAD) X(E_ROW_STORED) X(E_ROW_UNCHANGED)
+#define HC_X(name) name,
+enum HcEvent { HC_EVENTS(HC_X) E_COUNT };
+#undef HC_X
+#define HC_X(name) #name,
+static const char* const kEventNames[E_COUNT] = {HC_EVENTS(HC_X)};
+#undef HC_X
+
+struct HcVolume { Camera cam; CameraInv cami; int cols, rows; std::map<int, HcUnit> units; long culled = 0, kept = 0, inside = 0, inside_violations = 0, sure = 0, visited = 0, unsure_pf = 0, sure_violations = 0, full_pf = 0, full_violations = 0, exact_rows = 0, exact_rows_needing = 0, walk_violations = 0; long ev[E_COUNT] = {0}; };
 
 static bool inverse4(const double* m, double* out);
+
+// One wave's box as k_integrate holds it: 256 voxels = kRows (4) register rows x 64 lanes; what the walk leaves in S / W is what the kernel would
+// have in its registers before the stores.
+constexpr int kWalkVox = 256;
+struct HcWalk { float S[kWalkVox], W[kWalkVox], S0[kWalkVox], W0[kWalkVox], g0[kWalkVox], g1[kWalkVox], g2[kWalkVox]; };
+
+// k_integrate from "unsigned long long mn = m & ~m_full" to the stores, statement for statement, with every wave-uniform decision taken over the
+// 256 voxels of the box (the kernel's ballots) and the events counted where they happen.  scaled[f] has no pad: the pad's zero is supplied here.
+static void walk_box(HcVolume* v, HcWalk& w, unsigned long long m, unsigned long long m_in, unsigned long long m_full, const std::vector<FrameXform>& frames,
+                     const std::vector<std::vector<float>>& scaled) {
+  long* ev = v->ev;
+  const unsigned pixels = (unsigned)(v->cols * v->rows);
+  const bool kSure = v->cam.integration_trunc < 64.0f;
+  if (m == 0ull) ev[E_ALL_CULLED]++;
+  auto project = [&](int f, float* dp) {
+    const FrameXform& fx = frames[f];
+    bool pad = false;
+    for (int t = 0; t < kWalkVox; t++) {
+      unsigned pix;
+      if ((m_in >> f) & 1ull) {
+        pix = voxel_project_inside(w.g0[t], w.g1[t], w.g2[t], fx, v->cam, v->cols, v->rows);
+      } else {
+        unsigned pixel;
+        const bool ok = voxel_project(w.g0[t], w.g1[t], w.g2[t], fx, v->cam, v->cols, v->rows, pixel);
+        pix = ok ? pixel : pixels;
+        pad |= !ok;
+      }
+      dp[t] = pix < pixels ? scaled[f][pix] : 0.0f;
+    }
+    ev[((m_in >> f) & 1ull) ? E_PROJ_INSIDE : E_PROJ_TESTED]++;
+    ev[E_PROJ_PAD] += pad;
+    ev[E_FRAME63_PROJECTED] += f == 63;
+  };
+  auto finish = [&](int f, const float* dp) {
+    const FrameXform& fx = frames[f];
+    float d2[kWalkVox];
+    for (int t = 0; t < kWalkVox; t++) d2[t] = voxel_dist2(w.g0[t], w.g1[t], w.g2[t], fx);
+    if (kSure) {
+      bool fre[kWalkVox], need = false, unsure = false;
+      for (int t = 0; t < kWalkVox; t++) {
+        bool behind;
+        voxel_classify(dp[t], d2[t], fre[t], behind);
+        unsure |= !(fre[t] | behind);
+        need = need | !(fre[t] | behind) | (fre[t] & !voxel_free_trivial(w.S[t], w.W[t]));
+      }
+      if (!need) {
+        for (int t = 0; t < kWalkVox; t++) {
+          w.S[t] = fre[t] ? 1.0f : w.S[t];
+          w.W[t] = fre[t] ? w.W[t] + 1.0f : w.W[t];
+        }
+        ev[E_SURE_TAKEN]++;
+        return;
+      }
+      ev[unsure ? E_SURE_DECLINED_UNSURE : E_SURE_DECLINED_NONTRIVIAL]++;   // (NONTRIVIAL: that term of `need` alone decided)
+    }
+    for (int t = 0; t < kWalkVox; t++) (void)voxel_finish_d2(w.S[t], w.W[t], dp[t], d2[t]);
+  };
+  unsigned long long mn = m & ~m_full, mf = m & m_full;
+  ev[E_FRAME63_FULL] += (mf >> 63) & 1ull;
+  const int n_proj = __builtin_popcountll(mn);
+  if (mn == 0ull && mf != 0ull) ev[E_FULL_ONLY]++;
+  if (n_proj) ev[n_proj >= 5 ? E_PROJ_5PLUS : E_PROJ_1 + (n_proj - 1)]++;
+  auto apply_full = [&](unsigned long long run) {
+    const int n = __builtin_popcountll(run);
+    bool nontrivial = false;
+    for (int t = 0; t < kWalkVox; t++) nontrivial = nontrivial | !(voxel_free_trivial(w.S[t], w.W[t]) & (w.W[t] < 8388608.0f));
+    if (!nontrivial) {
+      for (int t = 0; t < kWalkVox; t++) {
+        w.S[t] = 1.0f;
+        w.W[t] = w.W[t] + (float)n;
+      }
+      ev[E_FULL_TRIVIAL]++;
+    } else {
+      for (int q = 0; q < n; q++)
+        for (int t = 0; t < kWalkVox; t++) {
+          w.S[t] = div_inrange(w.S[t] * w.W[t] + 1.0f, w.W[t] + 1.0f);
+          w.W[t] = w.W[t] + 1.0f;
+        }
+      ev[E_FULL_DIVIDE]++;
+      ev[E_FULL_DIVIDE_LEN_GE2] += n >= 2;
+    }
+    ev[E_RUN_LEN_GE2] += n >= 2;
+  };
+  auto runs_before = [&](int f, int place) {                             // place: the event of a non-empty run here, or -1
+    const unsigned long long run = f < 64 ? (mf & ((1ull << f) - 1ull)) : mf;
+    if (run) {
+      mf &= ~run;
+      if (place >= 0) ev[place]++;
+      apply_full(run);
+    }
+  };
+  if (mn) {
+    float dpa[kWalkVox], dpb[kWalkVox];
+    int pf = __builtin_ctzll(mn);
+    mn &= mn - 1;
+    project(pf, dpa);
+    bool last_in_b = false;
+    int place = E_RUN_BEFORE_FIRST;
+    for (;;) {
+      runs_before(pf, place);
+      place = E_RUN_BETWEEN;
+      if (mn == 0ull) break;
+      int nf = __builtin_ctzll(mn);
+      mn &= mn - 1;
+      project(nf, dpb);
+      finish(pf, dpa);
+      pf = nf;
+      runs_before(pf, place);
+      if (mn == 0ull) {
+        last_in_b = true;
+        break;
+      }
+      nf = __builtin_ctzll(mn);
+      mn &= mn - 1;
+      project(nf, dpa);
+      finish(pf, dpb);
+      pf = nf;
+    }
+    if (last_in_b != (n_proj % 2 == 0)) v->walk_violations++;            // an even number of projected frames leaves through the dpb exit
+    finish(pf, last_in_b ? dpb : dpa);
+    runs_before(64, E_RUN_AFTER_LAST);
+  } else {
+    runs_before(64, -1);                                                 // (E_FULL_ONLY: counted above)
+  }
+  for (int t = 0; t < kWalkVox; t++) {
+    const bool stored = w.W[t] != w.W0[t];
+    ev[stored ? E_ROW_STORED : E_ROW_UNCHANGED]++;
+    if (!stored) w.S[t] = w.S0[t];                                       // what the unit holds after the kernel's predicated store
+  }
+}
 
 extern "C" {
 
@@ -63,6 +215,8 @@ int hc_integrate_frames(void* h, int n, const uint16_t* depth, const double* T, 
   const int px = v->cols * v->rows;
   std::vector<std::vector<float>> scaled(n, std::vector<float>(px));
   std::vector<FrameXform> fx(n);
+  if (g_patch_shape == 3 && n > 64) return -2;                           // the walk's masks are the kernel's: one batch of at most 64 frames
+  std::fill(v->ev, v->ev + E_COUNT, 0L);
   for (auto& kv : v->units) kv.second.frames.clear();
   for (int f = 0; f < n; f++) {
     const double* Tf = T + f * 16;
@@ -102,17 +256,20 @@ int hc_integrate_frames(void* h, int n, const uint16_t* depth, const double* T, 
     if (u.frames.empty()) continue;
     const int xi = key >> 18, yi = (key >> 9) & 511, zi = key & 511;
     const float xs = unit_shift(xi), ys = unit_shift(yi), zs = unit_shift(zi);
-    // patch shape of a wave: 2 = the 8 x 8 x 8 cube (k_integrate's default), 1 = the 4 x 8 x 8 box, 0 = the 16 x 16 (j, k) square of one slab
+    // patch shape of a wave: 3 = the 8 x 4 x 8 box (eight slabs, four j, eight k) k_integrate has used since the lane-shape change, 2 = the
+    // 8 x 8 x 8 cube of mid round 3, 1 = the 4 x 8 x 8 box of rounds 3-5, 0 = the 16 x 16 (j, k) square of one slab
     const int n_patches = g_patch_shape == 2 ? 8 * 64 : (g_patch_shape ? 16 * 64 : 64 * 16);
     for (int pi = 0; pi < n_patches; pi++) {
       {
         int i0, j0, k0, ni, nj, nk;
-        if (g_patch_shape == 2) { i0 = (pi >> 6) * 8; j0 = ((pi >> 3) & 7) * 8; k0 = (pi & 7) * 8; ni = 8; nj = 8; nk = 8; }
+        if (g_patch_shape == 3) { i0 = (pi >> 7) * 8; j0 = ((pi >> 3) & 15) * 4; k0 = (pi & 7) * 8; ni = 8; nj = 4; nk = 8; }
+        else if (g_patch_shape == 2) { i0 = (pi >> 6) * 8; j0 = ((pi >> 3) & 7) * 8; k0 = (pi & 7) * 8; ni = 8; nj = 8; nk = 8; }
         else if (g_patch_shape) { i0 = (pi >> 6) * 4; j0 = ((pi >> 3) & 7) * 8; k0 = (pi & 7) * 8; ni = 4; nj = 8; nk = 8; }
         else { i0 = pi >> 4; j0 = ((pi >> 2) & 3) * 16; k0 = (pi & 3) * 16; ni = 1; nj = 16; nk = 16; }
         // the same (patch, frame) culling k_integrate applies before its frame loop
         std::vector<int> frames;
         std::vector<char> in, ful;
+        unsigned long long wm = 0ull, wm_in = 0ull, wm_full = 0ull;        // m, m_in, m_full of k_integrate
         for (int f : u.frames) {
           bool inside = false, full = false;
           if (patch_may_update_box(grid_coord(i0, xs), grid_coord(i0 + ni - 1, xs), grid_coord(j0, ys), grid_coord(j0 + nj - 1, ys), grid_coord(k0, zs),
@@ -124,16 +281,30 @@ int hc_integrate_frames(void* h, int n, const uint16_t* depth, const double* T, 
             kept++;
             v->inside += inside;
             v->full_pf += full;
+            if (f < 64) { wm |= 1ull << f; wm_in |= (unsigned long long)inside << f; wm_full |= (unsigned long long)full << f; }
           } else {
             culled++;
           }
         }
         auto voxel_of = [&](int t, int& i, int& j, int& k) {
-          if (g_patch_shape) { i = i0 + (t >> 6); j = j0 + ((t >> 3) & 7); k = k0 + (t & 7); }
+          if (g_patch_shape == 3) { i = i0 + (t >> 5); j = j0 + ((t >> 3) & 3); k = k0 + (t & 7); }   // (register row = t >> 6: two slabs)
+          else if (g_patch_shape) { i = i0 + (t >> 6); j = j0 + ((t >> 3) & 7); k = k0 + (t & 7); }
           else { i = i0; j = j0 + (t >> 4); k = k0 + (t & 15); }
         };
         // frame-major over the patch, like the wave of k_integrate: all lanes x register rows against frame q, then the next frame
         const int nvox = ni * nj * nk;
+        HcWalk walk;
+        if (g_patch_shape == 3) {                                          // the path tally: before the replay touches the box
+          for (int t = 0; t < nvox; t++) {
+            int i, j, k;
+            voxel_of(t, i, j, k);
+            const int l = (i * 64 + j) * 64 + k;
+            walk.S[t] = walk.S0[t] = u.sdf[l];
+            walk.W[t] = walk.W0[t] = u.w[l];
+            walk.g0[t] = grid_coord(i, xs); walk.g1[t] = grid_coord(j, ys); walk.g2[t] = grid_coord(k, zs);
+          }
+          walk_box(v, walk, wm, wm_in, wm_full, fx, scaled);
+        }
         float dpv[512], d2v[512];
         bool frev[512], behv[512];
         for (size_t q = 0; q < frames.size(); q++) {
@@ -203,6 +374,13 @@ int hc_integrate_frames(void* h, int n, const uint16_t* depth, const double* T, 
             u.sdf[l] = S2; u.w[l] = W2;
           }
         }
+        if (g_patch_shape == 3)                                            // the walk and the frame-by-frame replay end in the same bits
+          for (int t = 0; t < nvox; t++) {
+            int i, j, k;
+            voxel_of(t, i, j, k);
+            const int l = (i * 64 + j) * 64 + k;
+            if (memcmp(&walk.S[t], &u.sdf[l], 4) != 0 || memcmp(&walk.W[t], &u.w[l], 4) != 0) v->walk_violations++;
+          }
       }
     }
   }
@@ -213,6 +391,17 @@ int hc_integrate_frames(void* h, int n, const uint16_t* depth, const double* T, 
 
 void hc_set_patch_shape(int shape) { g_patch_shape = shape; }
 void hc_set_lo_shift(int shift) { g_lo_shift = shift; }
+long hc_walk_violations(void* h) { return static_cast<HcVolume*>(h)->walk_violations; }
+int hc_event_count() { return E_COUNT; }
+const char* hc_event_name(int e) { return e >= 0 && e < E_COUNT ? kEventNames[e] : ""; }
+// the path tally of the last hc_integrate_frames call (patch shape 3): out[hc_event_count()]
+void hc_events(void* h, long* out) { memcpy(out, static_cast<HcVolume*>(h)->ev, sizeof(long) * E_COUNT); }
+// a replay that starts from a given state: the unit as er_tsdf_import_raw would leave it
+void hc_write_unit(void* h, int key, const float* sdf, const float* w) {
+  HcUnit& u = static_cast<HcVolume*>(h)->units[key];
+  u.sdf.assign(sdf, sdf + kUnitVox);
+  u.w.assign(w, w + kUnitVox);
+}
 long hc_sure(void* h) { return static_cast<HcVolume*>(h)->sure; }
 long hc_visited(void* h) { return static_cast<HcVolume*>(h)->visited; }
 long hc_full(void* h) { return static_cast<HcVolume*>(h)->full_pf; }

@@ -42,7 +42,7 @@ def hc():
     L.hc_inside.argtypes = [vp]
     L.hc_inside_violations.restype = C.c_long
     L.hc_inside_violations.argtypes = [vp]
-    for name in ("hc_sure", "hc_visited", "hc_unsure_pf", "hc_sure_violations", "hc_full", "hc_full_violations", "hc_exact_rows", "hc_exact_rows_needing"):
+    for name in ("hc_sure", "hc_visited", "hc_unsure_pf", "hc_sure_violations", "hc_full", "hc_full_violations", "hc_exact_rows", "hc_exact_rows_needing", "hc_walk_violations"):
         getattr(L, name).restype = C.c_long
         getattr(L, name).argtypes = [vp]
     L.hc_set_patch_shape.restype = None
@@ -116,11 +116,12 @@ def test_device_math_rigid_matches_golden(hc):
     print("full (patch, frame) visits: %d of %d kept (%.1f %%)" % (hc.hc_full(v.h), kept, 100.0 * hc.hc_full(v.h) / max(kept, 1)))
 
 
-@pytest.mark.parametrize("shape", [0, 1, 2])
+@pytest.mark.parametrize("shape", [0, 1, 2, 3])
 def test_device_math_warp_matches_golden(hc, shape):
-    """shape 1: the 4 x 8 x 8 box k_integrate gives a wave (patch_may_update_box with eight corners); shape 2: the 8 x 8 x 8 cube the
-    kernel used for part of round 3; shape 0: a 16 x 16 square of one slab.  Same golden digests every way: the culling and the
-    shortcuts are exact whatever the patch."""
+    """shape 3: the 8 x 4 x 8 box k_integrate gives a wave today (patch_may_update_box with eight corners), walked through the kernel's
+    frame loop as well (tests/test_integrate_cases_cpu.py reads that walk's tally); shape 1: the 4 x 8 x 8 box of rounds 3-5; shape 2: the
+    8 x 8 x 8 cube the kernel used for part of round 3; shape 0: a 16 x 16 square of one slab.  Same golden digests every way: the culling
+    and the shortcuts are exact whatever the patch."""
     hc.hc_set_patch_shape(shape)
     try:
         _warp_matches_golden(hc)
@@ -151,6 +152,7 @@ def _warp_matches_golden(hc):
     # the FULL verdict (every voxel of the patch updated with tsdf = 1: no projection, no sample): checked voxel by voxel
     assert hc.hc_full_violations(v.h) == 0
     print("full (patch, frame) visits: %d of %d kept (%.1f %%)" % (hc.hc_full(v.h), hc.hc_kept(v.h), 100.0 * hc.hc_full(v.h) / max(hc.hc_kept(v.h), 1)))
+    assert hc.hc_walk_violations(v.h) == 0                    # (shape 3: the walk through k_integrate's frame loop ends in the replay's bits)
     print("register rows of the exact-path visits that need the exact update: %d of %d (%.1f %%)" % (
         hc.hc_exact_rows_needing(v.h), hc.hc_exact_rows(v.h), 100.0 * hc.hc_exact_rows_needing(v.h) / max(hc.hc_exact_rows(v.h), 1)))
 
