@@ -11,7 +11,7 @@
 // word per round to learn of it.  Inside a launch other workgroups' labels are touched only by agent-scope atomics and relaxed agent-scope
 // atomic loads, every value only ever decreases, and a value read late costs at most a round: no fence, no flag, no grid synchronisation
 // hands anything over inside a launch -- the launch boundary publishes the rest.
-#include "er_tsdf.h"
+#include "er_mesh.h"
 
 #include <climits>
 
@@ -326,12 +326,40 @@ int er_tsdf_extract_mesh_cleaned(er_tsdf_t h, long min_triangles, int largest_on
   const bool want_v = verts_host || normals_host, want_rows = want_v || index_host;
   hipStream_t s = h->stream;
   DeviceMesh m;
-  auto counted = [&](long nv, long) {
-    if (nv > (long)INT_MAX) return er::fail("er_tsdf_extract_mesh_cleaned: %ld vertices; the limit is 2^31 - 1 (int32 indices)", nv);
+  CleanedMesh c;
+  auto counted = [&](const CleanedMesh& k) {
+    *n_vertices = k.nv;
+    *n_triangles = k.ntri;
+    if (stats)
+      for (int q = 0; q < 4; q++) stats[q] = k.stats[q];
+    if (want_rows && capacity_vertices < k.nv) return er::fail("er_tsdf_extract_mesh_cleaned: capacity %ld < %ld vertices", capacity_vertices, k.nv);
+    if (tri_host && capacity_triangles < k.ntri) return er::fail("er_tsdf_extract_mesh_cleaned: capacity %ld < %ld triangles", capacity_triangles, k.ntri);
+    return 0;
+  };
+  if (mesh_cleaned_on_device(h, who, min_triangles, largest_only, want_v, normals_host != nullptr, want_rows, tri_host != nullptr, counted, &m, &c)) return 1;
+  if (!c.d_index) return 0;                                  // (nothing has been written to the host)
+  if (verts_host) ER_W(who, hipMemcpyAsync(verts_host, c.d_verts, (size_t)c.nv * sizeof(float4), hipMemcpyDeviceToHost, s));
+  if (normals_host) ER_W(who, hipMemcpyAsync(normals_host, c.d_nrm, (size_t)c.nv * sizeof(float4), hipMemcpyDeviceToHost, s));
+  if (index_host) ER_W(who, hipMemcpyAsync(index_host, c.d_index, (size_t)c.nv * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (c.d_tri) ER_W(who, hipMemcpyAsync(tri_host, c.d_tri, (size_t)c.ntri * 3 * sizeof(int), hipMemcpyDeviceToHost, s));
+  ER_W(who, hipStreamSynchronize(s));
+  return 0;
+}
+
+}  // extern "C"
+
+namespace er_tsdf_k {
+
+int mesh_cleaned_on_device(er_tsdf_t h, const char* who, long min_triangles, int largest_only, bool want_v, bool want_n, bool want_rows, bool want_t,
+                           const std::function<int(const CleanedMesh&)>& counted, DeviceMesh* mesh, CleanedMesh* c) {
+  DeviceMesh& m = *mesh;
+  hipStream_t s = h->stream;
+  auto limit = [&](long nv, long) {
+    if (nv > (long)INT_MAX) return er::fail("%s: %ld vertices; the limit is 2^31 - 1 (int32 indices)", who, nv);
     return 0;
   };
   long nv = 0, nt = 0;                                       // (of the unfiltered mesh; the caller's counts are those after filtering)
-  if (mesh_indexed_on_device(h, who, want_v, normals_host != nullptr, true, &nv, &nt, counted, &m)) return 1;
+  if (mesh_indexed_on_device(h, who, want_v, want_n, true, &nv, &nt, limit, &m)) return 1;
   if (nv == 0 || nt == 0 || !m.d_tri) return 0;              // an empty volume, or one without a crossing
 
   // labels, triangles per root, the largest component
@@ -373,7 +401,9 @@ int er_tsdf_extract_mesh_cleaned(er_tsdf_t h, long min_triangles, int largest_on
     return 0;
   };
   if (vertices(0) || triangles(0)) return 1;
-  std::vector<long> blk((size_t)(3 * nbv + nbt)), off((size_t)(nbv + nbt));
+  std::vector<long> blk((size_t)(3 * nbv + nbt));
+  std::vector<long>& off = c->off;                           // (read by a copy that is still in flight on return)
+  off.assign((size_t)(nbv + nbt), 0);
   ER_W(who, hipMemcpyAsync(blk.data(), d_blk, blk.size() * sizeof(long), hipMemcpyDeviceToHost, s));
   ER_W(who, hipStreamSynchronize(s));
   long nvk = 0, ntk = 0, found = 0, kept = 0;
@@ -387,38 +417,34 @@ int er_tsdf_extract_mesh_cleaned(er_tsdf_t h, long min_triangles, int largest_on
     off[(size_t)(nbv + b)] = ntk;
     ntk += blk[(size_t)(3 * nbv + b)];
   }
-  *n_vertices = nvk;
-  *n_triangles = ntk;
-  if (stats) {
-    stats[0] = found;
-    stats[1] = kept;
-    stats[2] = nv - nvk;
-    stats[3] = nt - ntk;
-  }
-  if (want_rows && capacity_vertices < nvk) return er::fail("er_tsdf_extract_mesh_cleaned: capacity %ld < %ld vertices", capacity_vertices, nvk);
-  if (tri_host && capacity_triangles < ntk) return er::fail("er_tsdf_extract_mesh_cleaned: capacity %ld < %ld triangles", capacity_triangles, ntk);
-  if (nvk == 0 || (!want_rows && !tri_host)) return 0;       // (nothing has been written to the host)
+  c->nv = nvk;
+  c->ntri = ntk;
+  c->stats[0] = found;
+  c->stats[1] = kept;
+  c->stats[2] = nv - nvk;
+  c->stats[3] = nt - ntk;
+  if (counted(*c)) return 1;
+  if (nvk == 0 || (!want_rows && !want_t)) return 0;
 
-  // the second passes and the way back
+  // the second passes
   ER_W(who, hipMemcpyAsync(d_ov, off.data(), off.size() * sizeof(long), hipMemcpyHostToDevice, s));
   ER_W_OWNED(who, m.owned, &d_remap, (size_t)nv * sizeof(int));
   ER_W_OWNED(who, m.owned, &d_index, (size_t)nvk * sizeof(int));
   if (m.d_verts) ER_W_OWNED(who, m.owned, &d_verts_out, (size_t)nvk * sizeof(float4));
   if (m.d_nrm) ER_W_OWNED(who, m.owned, &d_nrm_out, (size_t)nvk * sizeof(float4));
   if (vertices(1)) return 1;
-  if (verts_host) ER_W(who, hipMemcpyAsync(verts_host, d_verts_out, (size_t)nvk * sizeof(float4), hipMemcpyDeviceToHost, s));
-  if (normals_host) ER_W(who, hipMemcpyAsync(normals_host, d_nrm_out, (size_t)nvk * sizeof(float4), hipMemcpyDeviceToHost, s));
-  if (index_host) ER_W(who, hipMemcpyAsync(index_host, d_index, (size_t)nvk * sizeof(int), hipMemcpyDeviceToHost, s));
-  if (tri_host && ntk > 0) {
+  if (want_t && ntk > 0) {
     ER_W_OWNED(who, m.owned, &d_tri_out, (size_t)ntk * 3 * sizeof(int));
     if (triangles(1)) return 1;
-    ER_W(who, hipMemcpyAsync(tri_host, d_tri_out, (size_t)ntk * 3 * sizeof(int), hipMemcpyDeviceToHost, s));
   }
-  ER_W(who, hipStreamSynchronize(s));
+  c->d_verts = d_verts_out;
+  c->d_nrm = d_nrm_out;
+  c->d_index = d_index;
+  c->d_tri = d_tri_out;
   return 0;
 }
 
+}  // namespace er_tsdf_k
+
 #undef ER_W_OWNED
 #undef ER_W
-
-}  // extern "C"

@@ -11,6 +11,7 @@
 // Nothing here touches the sdf pool, the pre-pass buffers (zbuf, lastzero, zfix) or the batch pipeline: the calls run on the handle's stream behind
 // the voxel passes (check_flags), read the unit table when nobody inserts, and stage their inputs in scratch of their own.
 #include "er_tsdf_dev.h"
+#include "er_mesh.h"
 
 #include <cmath>
 
@@ -324,6 +325,20 @@ namespace er_tsdf_k {
 int color_zero_slots(er_tsdf_t h, int n) {
   if (!h->color || n <= 0) return 0;
   hipLaunchKernelGGL(k_zero_unit_colors, dim3(kUnitVox / 256, n), dim3(256), 0, h->stream, h->color, h->slot_scratch, h->max_units);
+  ER_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int color_sample_on_device(er_tsdf_t h, const char* who, const float4* d_points, long n, uchar4* d_rgba) {
+  if (color_ready(h, who)) return 1;
+  if (check_flags(h)) return 1;
+  if (n == 0) return 0;
+  if (n < 0 || n > 0x7FFFFFFFL) return er::fail("%s: %ld points are more than the 2^31 - 1 a colour call takes", who, n);
+  if (ensure_color_scratch(h, 256)) return 1;                // (the level counts, which nobody reads here)
+  unsigned long long* d_counts = static_cast<unsigned long long*>(h->color_scratch);
+  ER_HIP_TRY(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), h->stream));
+  hipLaunchKernelGGL(k_color_sample, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, h->color, h->ht_key, h->ht_slot,
+                     h->ht_cap - 1, h->ht_shift, h->max_units, d_points, n, d_rgba, d_counts);
   ER_HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -1,7 +1,7 @@
 // MeshOutput -- the last box of the reference workflow (README.txt:100-103: "pcl_kinfu_largeScale_mesh_output world.pcd", a tool of the
 // author's PCL fork, outside the reference tree): world.pcd in, a triangle mesh out, with the numeric core on MI355X through liber_hip.so.
 //
-//   MeshOutput <world.pcd> [--save_to mesh.ply] [--ascii] [--no_normals] [--min_triangles N] [--largest_only] [--device D]
+//   MeshOutput <world.pcd> [--save_to mesh.ply] [--ascii] [--no_normals] [--min_triangles N] [--largest_only] [--cell C] [--device D]
 //
 // world.pcd is TSDFVolume::SaveWorld's voxel list (FIELDS x y z intensity; ascii, binary or binary_compressed): integer voxel indices and
 // the sdf.  The list goes back into a volume sized from its own unit keys (er_tsdf_import_world: every listed voxel observed with weight 1),
@@ -10,7 +10,8 @@
 // voxels the file holds: SaveWorld drops |sdf| >= 0.98 and unobserved voxels, so cells next to those are missing here and present in
 // `Integrate --save_mesh`, which reads the resident volume.  --min_triangles N drops the connected components of the mesh that have fewer than
 // N triangles, --largest_only all but the one with the most (er_tsdf_extract_mesh_cleaned: the unfiltered mesh never leaves the device);
-// without the two the file is the unfiltered mesh.  ER_TIMING=1 prints the stages.
+// without the two the file is the unfiltered mesh.  --cell C simplifies what is left by vertex clustering, one vertex per occupied cell of C
+// metres (er_tsdf_extract_mesh_simplified, in device memory too).  ER_TIMING=1 prints the stages.
 #include <cmath>
 #include <cstdio>
 #include <string>
@@ -31,6 +32,7 @@ int print_help() {
          "  --no_normals              leave out the per-vertex normals nx ny nz\n"
          "  --min_triangles <n> (=0)  drop the connected components of the mesh that have fewer than n triangles\n"
          "  --largest_only            keep only the connected component with the most triangles\n"
+         "  --cell <metres>           simplify the mesh by vertex clustering: one vertex per occupied cell of that size\n"
          "  --device <gpu> (=0)\n"
          "  -h [ --help ]             print this message\n");
   return 0;
@@ -52,6 +54,14 @@ int main(int argc, char** argv) {
   const bool largest_only = find_switch(argc, argv, "--largest_only"), clean = min_triangles > 1 || largest_only;
   if (min_triangles < 0) {
     fprintf(stderr, "%s: --min_triangles must not be negative\n", kWho);
+    return 1;
+  }
+  std::string cell_text;
+  const bool simplify = find_switch(argc, argv, "--cell");
+  parse_argument(argc, argv, "--cell", cell_text);
+  float cell = 0.0f;
+  if (simplify && !parse_cell(cell_text, &cell)) {
+    fprintf(stderr, "%s: --cell needs a finite size above 0, in metres\n", kWho);
     return 1;
   }
 
@@ -100,12 +110,14 @@ int main(int argc, char** argv) {
   }
   stage_done("HIP runtime up, volume created");
   int rc = 0, n_units = 0;
-  long nv = 0, nt = 0, stats[4] = {0, 0, 0, 0};
+  long nv = 0, nt = 0, stats[4] = {0, 0, 0, 0}, before[2] = {0, 0};
   std::vector<float> verts, nrm;
   std::vector<int> tris;
   if (er_tsdf_import_world(vol, rows.data(), (long)n, &n_units) != 0) rc = 1;
   stage_done("import (er_tsdf_import_world)");
   auto extract = [&](float* v, float* q, int* t) {
+    if (simplify)
+      return er_tsdf_extract_mesh_simplified(vol, cell, min_triangles, largest_only ? 1 : 0, 0, v, q, nullptr, nullptr, nv, t, nt, &nv, &nt, stats, before, nullptr);
     return clean ? er_tsdf_extract_mesh_cleaned(vol, min_triangles, largest_only ? 1 : 0, v, q, nullptr, nv, t, nt, &nv, &nt, stats)
                  : er_tsdf_extract_mesh_indexed(vol, v, q, nv, t, nt, &nv, &nt);
   };
@@ -116,7 +128,7 @@ int main(int argc, char** argv) {
     tris.resize((size_t)nt * 3);
     if (extract(verts.data(), no_normals ? nullptr : nrm.data(), tris.data()) != 0) rc = 1;
   }
-  stage_done(clean ? "mesh and cleaning (er_tsdf_extract_mesh_cleaned)" : "mesh (er_tsdf_extract_mesh_indexed)");
+  stage_done(simplify ? "mesh and simplification (er_tsdf_extract_mesh_simplified)" : clean ? "mesh and cleaning (er_tsdf_extract_mesh_cleaned)" : "mesh (er_tsdf_extract_mesh_indexed)");
   if (rc != 0) {
     fprintf(stderr, "%s: %s\n", kWho, er_last_error());
     er_tsdf_destroy(vol);
@@ -129,7 +141,10 @@ int main(int argc, char** argv) {
     return 1;
   }
   stage_done("write PLY");
-  if (clean) printf("%s: %ld of %ld components kept, %ld vertices and %ld triangles dropped\n", kWho, stats[1], stats[0], stats[2], stats[3]);
+  if (simplify)
+    printf("%s: cells of %g m: %ld vertices and %ld triangles in %ld cells -> %ld vertices and %ld triangles (%ld degenerate and %ld duplicate triangles, %ld cells dropped)\n",
+           kWho, (double)cell, before[0], before[1], stats[0], nv, nt, stats[1], stats[2], stats[3]);
+  else if (clean) printf("%s: %ld of %ld components kept, %ld vertices and %ld triangles dropped\n", kWho, stats[1], stats[0], stats[2], stats[3]);
   printf("%s: %zu voxels in %d units -> %ld vertices, %ld triangles -> %s\n", kWho, n, n_units, nv, nt, out_file.c_str());
   er_tsdf_destroy(vol);
   return 0;

@@ -637,6 +637,15 @@ inline int parse_argument(int argc, char** argv, const char* name, double& v) {
   return -1;
 }
 
+// A cell size on a command line: the whole text a number, finite and above 0.
+inline bool parse_cell(const std::string& text, float* cell) {
+  char* end = nullptr;
+  const float c = strtof(text.c_str(), &end);
+  if (text.empty() || end != text.c_str() + text.size() || !(c > 0.0f) || !(c <= 3.4e38f)) return false;
+  *cell = c;
+  return true;
+}
+
 // ER_TIMING=1 in the environment: the wall time of each stage of a host program on stderr (bench.py's boundary leg reads them).
 inline void stage_done(const char* what) {
   static const bool on = getenv("ER_TIMING") != nullptr;

@@ -336,13 +336,43 @@ class TSDFVolume:
             out += ((st[0], st[1], st[2], st[3]),)
         return out
 
-    def SaveMesh(self, filename, normals=True, binary=True, colors=None, min_triangles=0, largest_only=False):
+    def extract_simplified_mesh(self, cell, min_triangles=0, largest_only=False, colors=False, stats=False):
+        """The mesh of the resident volume simplified by vertex clustering (er_tsdf_extract_mesh_simplified; the unsimplified
+        mesh never leaves the device): (verts float32[n, 4] = x y z 0, normals float32[n, 3], tris int32[m, 3][, rgba][, stats]).  The mesh that
+        is clustered is extract_indexed_mesh's or, with min_triangles > 1 or largest_only, extract_clean_mesh's; the result is
+        mesh.simplify(verts, tris, cell, normals, colors) of it, where colors = True samples the unsimplified vertices (sample_colors) and
+        averages them per cluster.  cell is in metres.  stats = True appends (occupied cells, degenerate triangles dropped, duplicates dropped,
+        cells dropped, vertices before, triangles before)."""
+        nv, nt = C.c_long(0), C.c_long(0)
+        st, before = (C.c_long * 4)(0, 0, 0, 0), (C.c_long * 2)(0, 0)
+        call = self._lib.er_tsdf_extract_mesh_simplified
+        head = (self._h, C.c_float(cell), int(min_triangles), int(bool(largest_only)), int(bool(colors)))
+        _ffi.check(call(*head, None, None, None, None, 0, None, 0, C.byref(nv), C.byref(nt), st, before, None), "er_tsdf_extract_mesh_simplified")
+        verts = np.zeros((nv.value, 4), dtype=np.float32)
+        nrm = np.zeros((nv.value, 4), dtype=np.float32)
+        rgba = np.zeros((nv.value, 4), dtype=np.uint8)
+        tris = np.zeros((nt.value, 3), dtype=np.int32)
+        if nv.value:
+            _ffi.check(call(*head, _ffi.ptr(verts), _ffi.ptr(nrm), _ffi.ptr(rgba) if colors else None, None, nv.value, _ffi.ptr(tris), nt.value,
+                            C.byref(nv), C.byref(nt), st, before, None), "er_tsdf_extract_mesh_simplified")
+        out = (verts, np.ascontiguousarray(nrm[:, :3]), tris)
+        if colors:
+            out += (rgba,)
+        if stats:
+            out += ((st[0], st[1], st[2], st[3], before[0], before[1]),)
+        return out
+
+    def SaveMesh(self, filename, normals=True, binary=True, colors=None, min_triangles=0, largest_only=False, cell=0.0):
         """The indexed mesh of the resident volume as PLY (formats.save_ply; NaN normals become 0 0 0).  colors = None: per-vertex colours iff
         colour is enabled on the volume; False suppresses them; True demands them.  min_triangles > 1 or largest_only: the cleaned mesh of
-        extract_clean_mesh.  Returns (vertices, triangles)."""
+        extract_clean_mesh.  cell > 0: that mesh simplified by vertex clustering with cells of `cell` metres (extract_simplified_mesh); 0 writes
+        the unsimplified mesh.  Returns (vertices, triangles)."""
         if colors is None:
             colors = self.color_enabled_
-        if min_triangles > 1 or largest_only:
+        if cell != 0:
+            got = self.extract_simplified_mesh(cell, min_triangles, largest_only, colors=bool(colors))
+            verts, nrm, tris, rgba = got[0], got[1], got[2], (got[3] if colors else None)
+        elif min_triangles > 1 or largest_only:
             got = self.extract_clean_mesh(min_triangles, largest_only, colors=bool(colors))
             verts, nrm, tris, rgba = got[0], got[1], got[2], (got[4] if colors else None)
         elif colors:

@@ -230,6 +230,58 @@ int er_mesh_components(const int* tri_host, long n_triangles, long n_vertices, i
 int er_tsdf_extract_mesh_cleaned(er_tsdf_t h, long min_triangles, int largest_only, float* verts_host, float* normals_host, int* index_host,
                                  long capacity_vertices, int* tri_host, long capacity_triangles, long* n_vertices, long* n_triangles, long stats[4]);
 
+/* Mesh simplification by vertex clustering (Rossignac-Borrel).  Definitions, for nv vertices as float4 rows (x y z .; the 4th
+ * column is ignored), optional normals as float4 rows, optional colours (4 bytes r g b a per vertex), nt triangles int32[nt][3] and a cell
+ * (float32, metres):
+ *   - cell of a vertex: c_a = floor((double)p_a / (double)cell) per axis; its key (c_x + 2^20) << 42 | (c_y + 2^20) << 21 | (c_z + 2^20);
+ *   - a cluster is the set of vertices with one key; its lead is its smallest vertex index;
+ *   - position of a cluster: q_a = llrint((double)p_a * 2^20) per member (half to even; the product is exact), S_a the int64 sum of q_a over
+ *     the n members, x_a = (float)(((double)S_a / (double)n) * 2^-20), every operation rounded on its own; the 4th column is 0.0f.  The sum
+ *     is integer arithmetic: exact and associative;
+ *   - normal of a cluster: a member contributes iff its three components are finite and below 4096 in magnitude; N_a the int64 sum of
+ *     llrint((double)n_a * 2^20) over the contributing members, g_a = (double)N_a, len = sqrt((g_x g_x + g_y g_y) + g_z g_z) in float64, the
+ *     normal (float)(g_a / len); NaN NaN NaN when nobody contributes or len == 0; the 4th column is 0;
+ *   - colour of a cluster: over the m members with a != 0 each channel is (2 sum + m) / (2 m) in integer division, a = 255; a cluster
+ *     without such a member gets 0 0 0 0 (er_tsdf_sample_colors' rounding);
+ *   - triangles: (a, b, c) becomes (A, B, C), the clusters of its vertices; it is degenerate, and dropped, iff two of them are equal; two
+ *     non-degenerate triangles are duplicates iff one triple is a rotation of the other (the same vertices and the same winding), and of a
+ *     set of duplicates the one with the lowest input index stays; opposite windings are not duplicates, both stay; a kept triangle keeps
+ *     its own rotation and its place in the input order;
+ *   - vertices: a cluster becomes an output vertex iff a kept triangle names it; output vertices are ordered by lead, ascending; a triangle's
+ *     indices are the ranks of its clusters in that order;
+ *   - side outputs: cluster[v] the output index of v's cluster or -1; members[i] the number of members of the cluster behind output vertex i;
+ *     tri_index[j] the input index of kept triangle j; stats: occupied cells, degenerate triangles dropped, duplicates dropped, cells dropped
+ *     because no kept triangle names them.
+ * Every result is defined without reference to any order of execution: the same bytes on every call.  probes (nullable) is a diagnostic
+ * outside that promise: the longest probe sequence of the call in the vertex table and in the triangle table, which depends on arrival order.
+ *
+ * Refused, each before any kernel uses an index as an address, with nothing written, the message naming the FIRST offender in input order
+ * (vertices before triangles): a NULL required argument (the two counts; the vertices and the triangles where there are any; an output of
+ * normals or colours without its input) or negative sizes; n_vertices or n_triangles > 2^31 - 1; no device; a cell that is not finite or
+ * is <= 0; a coordinate that is not finite or is >= 4096 m in magnitude ("vertex <v> ..."); a c_a outside [-2^20, 2^20) ("vertex <v> ...");
+ * a triangle index outside [0, n_vertices) ("triangle <t> names vertex <i>, outside [0, <nv>)"); a capacity that is too small, refused after
+ * the counts, stats and probes have been set.  n_vertices == 0 or n_triangles == 0 gives the empty mesh and succeeds: counts and stats 0,
+ * cluster all -1, and no vertex is looked at.
+ *
+ * er_mesh_simplify clusters any indexed mesh held in host memory on `device`.  Every output pointer is nullable (verts_out, normals_out:
+ * 4 floats per output vertex; colors_out: 4 bytes; members_out: int32; tri_out: 3 ints per kept triangle; tri_index_out: int32 per kept
+ * triangle; cluster_out: int32 [n_vertices]); with all of them NULL the call returns only counts and stats.  Capacities are in output
+ * vertices and kept triangles. */
+int er_mesh_simplify(const float* verts_host, const float* normals_host, const uint8_t* colors_host, long n_vertices, const int* tri_host,
+                     long n_triangles, float cell, int device, float* verts_out, float* normals_out, uint8_t* colors_out, int* members_out,
+                     long capacity_vertices, int* tri_out, int* tri_index_out, long capacity_triangles, int* cluster_out, long* n_vertices_out,
+                     long* n_triangles_out, long stats[4], long probes[2]);
+
+/* The simplified mesh of the resident volume, without the unsimplified mesh leaving device memory: er_tsdf_extract_mesh_indexed's mesh --
+ * er_tsdf_extract_mesh_cleaned's, with its semantics on the UNSIMPLIFIED mesh, if min_triangles > 1 || largest_only -- is clustered as
+ * above where it lies and only the simplified arrays are copied back.  want_colors: the unsimplified vertices are coloured on the device
+ * (er_tsdf_sample_colors' rule) and averaged per cluster; it is refused before er_tsdf_color_enable, and colors_host without it is refused.
+ * Output layouts, nullable pointers, capacities, stats and probes as for er_mesh_simplify; before (nullable): vertices and triangles of the
+ * mesh that was clustered.  An empty volume, or a cleaning that keeps nothing, gives 0 and 0.  A negative min_triangles is refused. */
+int er_tsdf_extract_mesh_simplified(er_tsdf_t h, float cell, long min_triangles, int largest_only, int want_colors, float* verts_host,
+                                    float* normals_host, uint8_t* colors_host, int* members_host, long capacity_vertices, int* tri_host,
+                                    long capacity_triangles, long* n_vertices, long* n_triangles, long stats[4], long before[2], long probes[2]);
+
 /* TSDFVolume::SaveWorld's inverse: a world.pcd voxel list back into a volume.  xyzi_host: n rows x y z intensity in er_tsdf_extract_world's
  * layout -- x, y, z integer voxel indices as floats, i + (xi - 256) * 64; intensity = the sdf.  Afterwards every listed voxel is (intensity, 1)
  * and every other voxel of a created unit (+0, 0); the created units are those with at least one listed voxel, *n_units (nullable) their number.
