@@ -4,6 +4,7 @@
 
 #include "er_common.h"
 #include "er_grid.h"
+#include "er_mem.h"
 
 #include "../../include/er_hip.h"
 
@@ -28,7 +29,7 @@ struct er_cloud_s {
 
 struct er_features_s {
   int device = 0, n = 0, dim = 0, dp = 0;     // dp = dim rounded up to a multiple of 8 (rows padded with zeros: they add +0 to a distance)
-  float* d = nullptr;                         // [n][dp]
+  er::Buffer<float> d;                        // [n][dp]
 };
 
 namespace er {
@@ -67,21 +68,6 @@ struct StreamLease {
 
  private:
   void* group_ = nullptr;
-};
-
-// ---- shared by er_ransac.hip and er_fpfh.hip ----
-struct __attribute__((visibility("hidden"))) DevBufs {   // frees what a call allocated, whatever way it leaves
-  std::vector<void*> p;
-  template <typename T>
-  hipError_t alloc(T** out, size_t bytes) {
-    *out = nullptr;
-    hipError_t e = hipMalloc((void**)out, std::max<size_t>(bytes, 16));
-    if (e == hipSuccess) p.push_back(*out);
-    return e;
-  }
-  ~DevBufs() {
-    for (void* q : p) (void)hipFree(q);
-  }
 };
 
 }  // namespace er

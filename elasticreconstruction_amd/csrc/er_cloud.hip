@@ -22,7 +22,7 @@
 namespace er {
 // One device allocation shared by the clouds of a chunk (freed with the last of them).
 struct CloudSlab {
-  void* p = nullptr;
+  Buffer<char> p;
   std::atomic<int> refs{0};
 };
 }  // namespace er
@@ -192,10 +192,11 @@ __global__ __launch_bounds__(kBlock) void k_chunk_occ(ChunkDesc D, const int* __
 struct GridScratch {
   std::mutex mu;
   int device = -1;
-  unsigned *key[4] = {nullptr, nullptr, nullptr, nullptr}, *idx[4] = {nullptr, nullptr, nullptr, nullptr};   // two sets: [2 lane], [2 lane + 1]
-  void* cub[2] = {nullptr, nullptr};
-  int *bounds = nullptr, *h_bounds = nullptr;                   // 8 ints per cloud of a batch: device and its page-locked mirror (+ the initial pattern)
-  size_t n_cap = 0, cub_cap = 0, bounds_cap = 0;
+  // Arrays that grow together have one capacity: a failed growth empties all of them.
+  Buffer<unsigned> key[4], idx[4];                              // two sets: [2 lane], [2 lane + 1]
+  Buffer<char> cub[2];
+  Buffer<int> bounds;                                           // 8 ints per cloud of a batch ...
+  PinnedBuffer<int> h_bounds;                                   // ... and its page-locked mirror: [cap][8] results, then [cap][8] initial pattern
   hipStream_t up[2] = {nullptr, nullptr};                       // uploads: coordinates on one, normals on the other (two DMA engines keep the link busy)
   hipStream_t cs2[2] = {nullptr, nullptr};                      // grid kernels: consecutive chunks alternate between two lanes
   hipStream_t bs = nullptr;                                     // the bounding boxes of EVERY chunk (stage A): waits for uploads never sit in front of a grid
@@ -208,10 +209,7 @@ GridScratch& grid_scratch(int device) {
 }
 
 void slab_release(CloudSlab* sl) {
-  if (sl && sl->refs.fetch_sub(1) == 1) {
-    if (sl->p) (void)hipFree(sl->p);
-    delete sl;
-  }
+  if (sl && sl->refs.fetch_sub(1) == 1) delete sl;
 }
 
 }  // namespace
@@ -232,9 +230,9 @@ int er::check_pair(er_cloud_t src, er_cloud_t tgt, double radius, const char* wh
 
 int er::cloud_bounds(const er_cloud_s* c, hipStream_t stream, float lo[3], float hi[3]) {
   const int n = c->n;
-  DevBufs B;
+  DevScope B;
   int* d_box;
-  ER_HIP_TRY(B.alloc(&d_box, 8 * sizeof(int)));
+  if (B.alloc(&d_box, 8, "cloud_bounds")) return 1;
   int box[8] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN, 0, 0};
   ER_HIP_TRY(hipMemcpyAsync(d_box, box, sizeof box, hipMemcpyHostToDevice, stream));
   ChunkDesc D{};
@@ -350,54 +348,47 @@ static int cloud_create_impl(int n_clouds, const float* const* xyz_host, const f
     ER_CTRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     gs.ev.push_back(e);
   }
-  if (gs.bounds_cap < (size_t)n_clouds) {
+  const char* who = "er_cloud_create";
+  if (gs.bounds.capacity() < (size_t)n_clouds * 8) {
     ER_CTRY(sync_all());
-    if (gs.bounds) (void)hipFree(gs.bounds);
-    if (gs.h_bounds) (void)hipHostFree(gs.h_bounds);
-    gs.bounds = gs.h_bounds = nullptr;
-    gs.bounds_cap = 0;
     const size_t cap = (size_t)n_clouds + 16;
-    ER_CTRY(hipMalloc((void**)&gs.bounds, cap * 8 * sizeof(int)));
-    ER_CTRY(hipHostMalloc((void**)&gs.h_bounds, cap * 16 * sizeof(int), hipHostMallocDefault));   // [cap][8] results, then [cap][8] initial pattern
-    gs.bounds_cap = cap;
+    if (gs.bounds.reserve(cap * 8, who) || gs.h_bounds.reserve(cap * 16, who)) {
+      gs.bounds.reset();
+      undo();
+      return 1;
+    }
   }
   long t_max = 0;
   for (const Chunk& c : chunks) t_max = std::max(t_max, c.total);
   if (t_max >= (1L << 31) - kBlock) return er::fail("er_cloud_create: a cloud of %ld points is beyond the 32-bit point index", t_max);
   if (t_max > 0) {
-    if (gs.n_cap < (size_t)t_max) {
+    if (gs.key[0].capacity() < (size_t)t_max) {
       ER_CTRY(sync_all());
-      for (int q = 0; q < 4; q++) {
-        if (gs.key[q]) (void)hipFree(gs.key[q]);
-        if (gs.idx[q]) (void)hipFree(gs.idx[q]);
-        gs.key[q] = gs.idx[q] = nullptr;
-      }
-      gs.n_cap = 0;
       const size_t cap = (size_t)t_max + (size_t)t_max / 8;
-      for (int q = 0; q < 4; q++) {
-        ER_CTRY(hipMalloc((void**)&gs.key[q], cap * sizeof(unsigned)));
-        ER_CTRY(hipMalloc((void**)&gs.idx[q], cap * sizeof(unsigned)));
+      bool ok = true;
+      for (int q = 0; q < 4; q++) ok = ok && !gs.key[q].reserve(cap, who) && !gs.idx[q].reserve(cap, who);
+      if (!ok) {
+        for (int q = 0; q < 4; q++) gs.key[q].reset(), gs.idx[q].reset();
+        undo();
+        return 1;
       }
-      gs.n_cap = cap;
     }
     // temporary storage of the sort / scan for the largest chunk and the largest grids (2^25 cells and 3 cloud bits: 28 key bits) this call can meet
     size_t need_sort = 0, need_scan = 0;
-    ER_CTRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need_sort, gs.key[0], gs.key[1], gs.idx[0], gs.idx[1], (int)t_max, 0, 28, gs.cs2[0]));
+    ER_CTRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need_sort, gs.key[0].get(), gs.key[1].get(), gs.idx[0].get(), gs.idx[1].get(), (int)t_max, 0, 28, gs.cs2[0]));
     ER_CTRY(hipcub::DeviceScan::InclusiveSum(nullptr, need_scan, (int*)nullptr, (int*)nullptr, kCloudChunk * ((1 << 25) + 1), gs.cs2[0]));
     const size_t need = std::max(need_sort, need_scan);
-    if (gs.cub_cap < need) {
+    if (gs.cub[0].capacity() < need) {
       ER_CTRY(sync_all());
-      for (int q = 0; q < 2; q++) {
-        if (gs.cub[q]) (void)hipFree(gs.cub[q]);
-        gs.cub[q] = nullptr;
+      if (gs.cub[0].reserve(need + need / 4, who) || gs.cub[1].reserve(need + need / 4, who)) {
+        gs.cub[0].reset();
+        undo();
+        return 1;
       }
-      gs.cub_cap = 0;
-      for (int q = 0; q < 2; q++) ER_CTRY(hipMalloc(&gs.cub[q], need + need / 4));
-      gs.cub_cap = need + need / 4;
     }
   }
   int* h_got = gs.h_bounds;
-  int* h_init = gs.h_bounds + gs.bounds_cap * 8;
+  int* h_init = gs.h_bounds + gs.bounds.capacity();
   for (int i = 0; i < n_clouds; i++) {
     const int init[8] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN, 0, 0};
     memcpy(h_init + (size_t)i * 8, init, sizeof init);
@@ -417,15 +408,14 @@ static int cloud_create_impl(int n_clouds, const float* const* xyz_host, const f
     const size_t f_base = (xn_base + 2 * N) * 4;
     const size_t bytes = std::max((f_base + 6 * N) * sizeof(float), (size_t)256);
     C.pts = new CloudSlab();
-    hipError_t e = hipMalloc(&C.pts->p, bytes);
-    if (e != hipSuccess) {
+    if (C.pts->p.reserve(bytes, who)) {
       delete C.pts;
       C.pts = nullptr;
-      return er::fail("er_cloud_create: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+      return 1;
     }
     C.pts->refs = m;
-    C.sorted = static_cast<float4*>(C.pts->p);
-    float* fbase = static_cast<float*>(C.pts->p) + f_base;
+    C.sorted = reinterpret_cast<float4*>(C.pts->p.get());
+    float* fbase = reinterpret_cast<float*>(C.pts->p.get()) + f_base;
     C.D.m = m;
     long off = 0;
     for (int k = 0; k < m; k++) {                                 // the cloud objects first: from here on undo() releases the allocation through them
@@ -521,14 +511,13 @@ static int cloud_create_impl(int n_clouds, const float* const* xyz_host, const f
     C.D.cs_off[m] = cs_total;
     C.cells = new CloudSlab();
     const size_t cells_bytes = (size_t)cs_total * sizeof(int) + (size_t)cs_total;   // cell_start of the chunk's clouds, then one occupancy byte per cell
-    hipError_t e = hipMalloc(&C.cells->p, cells_bytes);
-    if (e != hipSuccess) {
+    if (C.cells->p.reserve(cells_bytes, who)) {
       delete C.cells;
       C.cells = nullptr;
-      return er::fail("er_cloud_create: hipMalloc(%zu) failed: %s", cells_bytes, hipGetErrorString(e));
+      return 1;
     }
     C.cells->refs = m;
-    int* cs = static_cast<int*>(C.cells->p);
+    int* cs = reinterpret_cast<int*>(C.cells->p.get());
     unsigned char* occ = reinterpret_cast<unsigned char*>(cs + cs_total);
     for (int k = 0; k < m; k++) {
       er_cloud_t c = out[C.i0 + k];
@@ -548,9 +537,9 @@ static int cloud_create_impl(int n_clouds, const float* const* xyz_host, const f
     int n_big = 0;
     for (int k = 0; k < m; k++) n_big = std::max(n_big, C.D.n[k]);
     hipLaunchKernelGGL(k_chunk_cells, dim3(nblocks_of(n_big), m), dim3(kBlock), 0, L, C.D, k0, x0, cs);
-    size_t tmp = gs.cub_cap;
+    size_t tmp = gs.cub[q].capacity();
     if (C.total > 0) ER_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(gs.cub[q], tmp, k0, k1, x0, x1, (int)C.total, 0, bits + 3, L));
-    tmp = gs.cub_cap;
+    tmp = gs.cub[q].capacity();
     ER_HIP_TRY(hipcub::DeviceScan::InclusiveSum(gs.cub[q], tmp, cs, cs, (int)cs_total, L));
     hipLaunchKernelGGL(k_chunk_occ, dim3((unsigned)((max_cells + kBlock - 1) / kBlock), m), dim3(kBlock), 0, L, C.D, cs, occ);
     if (C.total > 0) hipLaunchKernelGGL(k_chunk_gather, dim3(nblocks_of((int)C.total)), dim3(kBlock), 0, L, C.D, k1, x1, (int)C.total, C.sorted);

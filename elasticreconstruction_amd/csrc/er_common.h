@@ -24,6 +24,13 @@ int fail(const char* fmt, ...);
       return ::er::fail("%s:%d: %s failed: %s", __FILE__, __LINE__, #expr, hipGetErrorString(er_e_)); \
   } while (0)
 
+// The same for code shared by several entry points: the text names the entry point `who` instead of the file and line.
+#define ER_W(who, expr)                                                                         \
+  do {                                                                                          \
+    hipError_t e_ = (expr);                                                                     \
+    if (e_ != hipSuccess) return ::er::fail("%s: %s failed: %s", who, #expr, hipGetErrorString(e_)); \
+  } while (0)
+
 }  // namespace er
 
 // internal accessors of a TSDF handle for the other translation units of the library (not part of the C ABI)

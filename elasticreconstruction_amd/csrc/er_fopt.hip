@@ -13,6 +13,7 @@
 // the dense matrix with float64 atomics, folding coinciding lattice indices exactly like OptApp.cpp:537-548.
 // This is the one GEMM-shaped loop of the pipeline; the reference runs it as scalar double loops under OpenMP.
 #include "er_common.h"
+#include "er_mem.h"
 
 #include "../../include/er_hip.h"
 
@@ -24,6 +25,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 namespace {
@@ -465,54 +467,46 @@ int rocblas_load(RocBlas& R, hipStream_t stream) {
 
 }  // namespace
 
-struct er_fopt_s {
-  int device = 0, num = 0, res = 8, nper = 0;
-  float length = 3.0f, ul = 0.375f;
-  hipStream_t stream = nullptr;
+// Every device array of a handle.  A fresh FoptMem assigned over it frees them all, at that point (er_fopt_destroy: before the stream goes).
+struct FoptMem {
   struct Frag {
     int n = 0;
-    int* idx0 = nullptr;
-    float *val = nullptr, *nval = nullptr, *p = nullptr, *nrm = nullptr;
+    er::Buffer<int> idx0;
+    er::Buffer<float> val, nval, p, nrm;
     std::vector<int> h_idx0;
   };
   std::vector<Frag> frag;
+  er::DevScope fixed;                              // made once by er_fopt_create:
   FragPtr* d_frags = nullptr;
+  double *d_rot = nullptr, *d_ctr = nullptr;
+  float* d_M = nullptr;
+  er::Buffer<double> d_diag, d_off, d_rhs, d_big, d_JJ, d_Jb;
+  er::Buffer<long> d_blk_off;
+  er::Buffer<int> d_info, d_ginfo, d_first, d_second;
+  er::Buffer<Chunk> d_chunks;
+};
+
+struct er_fopt_s : FoptMem {
+  int device = 0, num = 0, res = 8, nper = 0;
+  float length = 3.0f, ul = 0.375f;
+  hipStream_t stream = nullptr;
   int n_pairs = 0, n_chunks = 0, n_groups = 0;
   std::vector<int> group_info;   // 4 per group: fragment i, fragment j, idx_[0] of the cell of p_i, of p_j
-  double *d_diag = nullptr, *d_off = nullptr;
-  size_t diag_cap = 0, off_cap = 0;
   // the system kept on the device for er_fopt_solve
   RocBlas roc;
-  double *d_sys = nullptr, *d_rhs = nullptr;       // d_sys aliases d_JJ in the SLAC mode, own allocation in the non-rigid mode
-  double* d_big = nullptr;
-  size_t big_cap = 0;
+  double* d_sys = nullptr;                         // aliases d_JJ in the SLAC mode, d_big in the non-rigid mode
   // block-sparse lower triangle of the non-rigid system (fragment blocks; er_fopt_factor_nonrigid when the dense matrix is too big)
   bool blocked = false;
   std::vector<long> blk_off;                       // [nb * nb]: offset (doubles) of block (row, col), row >= col, or -1
   std::vector<std::vector<int>> blk_rows;          // per block column: rows > column with a structurally non-zero block (ascending)
-  long* d_blk_off = nullptr;
   long sys_n = 0;
-  int* d_info = nullptr;
-  int* d_ginfo = nullptr;
   long shift_index = -1;         // er_fopt_debug_shift_diagonal: added to one diagonal entry of every system before it is factored
   double shift_value = 0.0;
   bool factored = false;
   long n_corr = 0;
-  int *d_first = nullptr, *d_second = nullptr;
-  Chunk* d_chunks = nullptr;
-  double *d_JJ = nullptr, *d_Jb = nullptr, *d_rot = nullptr, *d_ctr = nullptr;
-  float* d_M = nullptr;
-  size_t jj_cap = 0;
 };
 
 namespace {
-
-void free_frag(er_fopt_s::Frag& f) {
-  void* ptrs[] = {f.idx0, f.val, f.nval, f.p, f.nrm};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  f = er_fopt_s::Frag();
-}
 
 // PointCloud::GetCoordinate, PointCloud.h:92-176, on the host (once per point at load time; float32 like the reference)
 bool get_coordinate(int res, float ul, const float* in6, int& idx0, float val[8], float nval[8], float nrm[3]) {
@@ -547,6 +541,18 @@ bool get_coordinate(int res, float ul, const float* in6, int& idx0, float val[8]
   return true;
 }
 
+// The lists, their chunks and groups go, and with them any factored system.
+void drop_correspondences(er_fopt_t h) {
+  h->d_first.reset();
+  h->d_second.reset();
+  h->d_chunks.reset();
+  h->d_ginfo.reset();
+  h->n_pairs = h->n_chunks = h->n_groups = 0;
+  h->n_corr = 0;
+  h->group_info.clear();
+  h->factored = false;
+}
+
 int upload_frag_table(er_fopt_t h) {
   std::vector<FragPtr> t((size_t)h->num);
   for (int f = 0; f < h->num; f++) t[(size_t)f] = FragPtr{h->frag[(size_t)f].idx0, h->frag[(size_t)f].val, h->frag[(size_t)f].p, h->frag[(size_t)f].nrm};
@@ -556,14 +562,10 @@ int upload_frag_table(er_fopt_t h) {
 
 int ensure_matrix(er_fopt_t h, size_t N) {
   if (h->d_sys == h->d_JJ) h->factored = false;                  // the caller is about to overwrite a SLAC factor kept in d_JJ
-  if (N * N <= h->jj_cap) return 0;
-  if (h->d_JJ) (void)hipFree(h->d_JJ);
-  if (h->d_Jb) (void)hipFree(h->d_Jb);
-  h->d_JJ = h->d_Jb = nullptr;
-  h->jj_cap = 0;
-  ER_HIP_TRY(hipMalloc((void**)&h->d_JJ, N * N * sizeof(double)));
-  ER_HIP_TRY(hipMalloc((void**)&h->d_Jb, (N + 1) * sizeof(double)));
-  h->jj_cap = N * N;
+  if (h->d_JJ.reserve(N * N, "er_fopt_assemble") || h->d_Jb.reserve(N + 1, "er_fopt_assemble")) {   // (they grow together)
+    h->d_JJ.reset();
+    return 1;
+  }
   return 0;
 }
 
@@ -614,14 +616,14 @@ int er_fopt_create(int num, int resolution, float length, int device, er_fopt_t*
   h->ul = length / resolution;                                  // PointCloud.cpp:10
   h->nper = (resolution + 1) * (resolution + 1) * (resolution + 1) * 3;
   h->frag.resize((size_t)num);
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess || hipMalloc((void**)&h->d_frags, (size_t)num * sizeof(FragPtr)) != hipSuccess ||
-      hipMalloc((void**)&h->d_rot, (size_t)num * 9 * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&h->d_ctr, (size_t)h->nper * sizeof(double)) != hipSuccess || hipMalloc((void**)&h->d_M, 16 * sizeof(float)) != hipSuccess) {
-    const hipError_t e = hipGetLastError();
+  const char* who = "er_fopt_create";
+  const hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+  if (e != hipSuccess) {
     er_fopt_destroy(h);
-    return er::fail("er_fopt_create: allocation failed: %s", hipGetErrorString(e));
+    return er::fail("er_fopt_create: hipStreamCreateWithFlags failed: %s", hipGetErrorString(e));
   }
-  if (upload_frag_table(h)) {
+  if (h->fixed.alloc(&h->d_frags, (size_t)num, who) || h->fixed.alloc(&h->d_rot, (size_t)num * 9, who) ||
+      h->fixed.alloc(&h->d_ctr, (size_t)h->nper, who) || h->fixed.alloc(&h->d_M, 16, who) || upload_frag_table(h)) {
     er_fopt_destroy(h);
     return 1;
   }
@@ -633,12 +635,8 @@ int er_fopt_destroy(er_fopt_t h) {
   if (!h) return 0;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (auto& f : h->frag) free_frag(f);
   if (h->roc.handle && h->roc.destroy_handle) (void)h->roc.destroy_handle(h->roc.handle);
-  void* ptrs[] = {h->d_frags, h->d_first, h->d_second, h->d_chunks, h->d_JJ, h->d_Jb, h->d_rot, h->d_ctr, h->d_M, h->d_diag, h->d_off,
-                  h->d_big, h->d_rhs, h->d_info, h->d_ginfo, h->d_blk_off};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
+  static_cast<FoptMem&>(*h) = FoptMem();
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return 0;
@@ -662,23 +660,26 @@ int er_fopt_set_cloud(er_fopt_t h, int frag, const float* xyz, const float* nrm,
   }
   er_fopt_s::Frag& f = h->frag[(size_t)frag];
   ER_HIP_TRY(hipStreamSynchronize(h->stream));
-  free_frag(f);
+  f = er_fopt_s::Frag();
   // correspondence lists index into the clouds: a new cloud invalidates them (set them again) and any factored system
   h->n_pairs = h->n_chunks = h->n_groups = 0;
   h->group_info.clear();
   h->factored = false;
-  const size_t mm = (size_t)std::max(m, 1);
-  const bool ok = hipMalloc((void**)&f.idx0, mm * sizeof(int)) == hipSuccess && hipMalloc((void**)&f.val, mm * 8 * sizeof(float)) == hipSuccess &&
-                  hipMalloc((void**)&f.nval, mm * 8 * sizeof(float)) == hipSuccess && hipMalloc((void**)&f.p, mm * 3 * sizeof(float)) == hipSuccess &&
-                  hipMalloc((void**)&f.nrm, mm * 3 * sizeof(float)) == hipSuccess &&
-                  (m == 0 || (hipMemcpy(f.idx0, idx0.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
+  const char* who = "er_fopt_set_cloud";
+  const size_t mm = (size_t)m;
+  if (f.idx0.reserve(mm, who) || f.val.reserve(mm * 8, who) || f.nval.reserve(mm * 8, who) || f.p.reserve(mm * 3, who) || f.nrm.reserve(mm * 3, who)) {
+    f = er_fopt_s::Frag();                                       // leave an empty fragment behind, never a half-built one
+    (void)upload_frag_table(h);
+    return 1;
+  }
+  const bool ok = (m == 0 || (hipMemcpy(f.idx0, idx0.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
                               hipMemcpy(f.val, val.data(), (size_t)m * 8 * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
                               hipMemcpy(f.nval, nval.data(), (size_t)m * 8 * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
                               hipMemcpy(f.p, p.data(), (size_t)m * 3 * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
                               hipMemcpy(f.nrm, nn.data(), (size_t)m * 3 * sizeof(float), hipMemcpyHostToDevice) == hipSuccess));
-  if (!ok) {                                                     // leave an empty fragment behind, never a half-built one
+  if (!ok) {
     const hipError_t e = hipGetLastError();
-    free_frag(f);
+    f = er_fopt_s::Frag();
     (void)upload_frag_table(h);
     return er::fail("er_fopt_set_cloud: fragment %d (%d points): %s", frag, m, hipGetErrorString(e));
   }
@@ -769,23 +770,10 @@ int er_fopt_set_correspondences(er_fopt_t h, int n_pairs, const int* frag_i, con
       g0 = g1;
     }
   }
-  void* old[] = {h->d_first, h->d_second, h->d_chunks};
-  for (void* p : old)
-    if (p) (void)hipFree(p);
-  h->d_first = h->d_second = nullptr;
-  h->d_chunks = nullptr;
-  h->n_pairs = h->n_chunks = h->n_groups = 0;                    // an upload failure below leaves "no correspondences", not dangling lists
-  h->n_corr = 0;
-  h->group_info.clear();
-  if (h->d_ginfo) {
-    (void)hipFree(h->d_ginfo);
-    h->d_ginfo = nullptr;
-  }
-  h->factored = false;
+  drop_correspondences(h);                                       // an upload failure below leaves "no correspondences", not dangling lists
   if (!first.empty()) {
-    ER_HIP_TRY(hipMalloc((void**)&h->d_first, first.size() * sizeof(int)));
-    ER_HIP_TRY(hipMalloc((void**)&h->d_second, second.size() * sizeof(int)));
-    ER_HIP_TRY(hipMalloc((void**)&h->d_chunks, chunks.size() * sizeof(Chunk)));
+    const char* who = "er_fopt_set_correspondences";
+    if (h->d_first.reserve(first.size(), who) || h->d_second.reserve(second.size(), who) || h->d_chunks.reserve(chunks.size(), who)) return 1;
     ER_HIP_TRY(hipMemcpy(h->d_first, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice));
     ER_HIP_TRY(hipMemcpy(h->d_second, second.data(), second.size() * sizeof(int), hipMemcpyHostToDevice));
     ER_HIP_TRY(hipMemcpy(h->d_chunks, chunks.data(), chunks.size() * sizeof(Chunk), hipMemcpyHostToDevice));
@@ -857,28 +845,19 @@ int er_fopt_set_correspondences_dev(er_fopt_t h, int n_pairs, const int* frag_i,
   const long N = off[(size_t)n_pairs];
   if (N >= (1L << 31)) return er::fail("er_fopt_set_correspondences_dev: %ld correspondences exceed 2^31 - 1", N);
   // the old lists go first (as in the host path: a failure below leaves "no correspondences", not dangling lists)
-  void* old[] = {h->d_first, h->d_second, h->d_chunks, h->d_ginfo};
-  for (void* p : old)
-    if (p) (void)hipFree(p);
-  h->d_first = h->d_second = nullptr;
-  h->d_chunks = nullptr;
-  h->d_ginfo = nullptr;
-  h->n_pairs = h->n_chunks = h->n_groups = 0;
-  h->n_corr = 0;
-  h->group_info.clear();
-  h->factored = false;
+  drop_correspondences(h);
   if (N == 0) {
     h->n_pairs = n_pairs;
     return 0;
   }
-  int rc = 0;
+  const char* who = "er_fopt_set_correspondences_dev";
+  er::DevScope tmp;                                             // everything but the lists themselves, which are the handle's
   const int** d_lists = nullptr;
   long* d_off = nullptr;
-  int *d_fi = nullptr, *d_fj = nullptr, *d_fn = nullptr, *d_a = nullptr, *d_b = nullptr, *d_bad = nullptr, *d_cnt = nullptr, *d_runs = nullptr, *d_first = nullptr,
-      *d_second = nullptr;
+  int *d_fi = nullptr, *d_fj = nullptr, *d_fn = nullptr, *d_a = nullptr, *d_b = nullptr, *d_bad = nullptr, *d_cnt = nullptr, *d_runs = nullptr;
   unsigned long long *d_k0 = nullptr, *d_k1 = nullptr, *d_uni = nullptr;
   unsigned *d_v0 = nullptr, *d_v1 = nullptr;
-  void* d_tmp = nullptr;
+  char* d_tmp = nullptr;
   std::vector<unsigned long long> uni;
   std::vector<int> cnt, ginfo;
   std::vector<Chunk> chunks;
@@ -886,68 +865,48 @@ int er_fopt_set_correspondences_dev(er_fopt_t h, int n_pairs, const int* frag_i,
   size_t need_sort = 0, need_rle = 0;
   int lbits = 1;
   while ((1L << lbits) < (long)n_pairs) lbits++;
-#define ER_D(expr)                                                                                      \
-  do {                                                                                                  \
-    hipError_t e_ = (expr);                                                                             \
-    if (e_ != hipSuccess) {                                                                             \
-      rc = er::fail("er_fopt_set_correspondences_dev: %s failed: %s", #expr, hipGetErrorString(e_));    \
-      goto done;                                                                                        \
-    }                                                                                                   \
-  } while (0)
-  ER_D(hipMalloc((void**)&d_lists, (size_t)n_pairs * sizeof(int*)));
-  ER_D(hipMalloc((void**)&d_off, ((size_t)n_pairs + 1) * sizeof(long)));
-  ER_D(hipMalloc((void**)&d_fi, (size_t)n_pairs * sizeof(int)));
-  ER_D(hipMalloc((void**)&d_fj, (size_t)n_pairs * sizeof(int)));
-  ER_D(hipMalloc((void**)&d_fn, (size_t)h->num * sizeof(int)));
-  ER_D(hipMalloc((void**)&d_bad, 5 * sizeof(int)));
-  ER_D(hipMalloc((void**)&d_runs, sizeof(int)));
-  ER_D(hipMalloc((void**)&d_k0, (size_t)N * 8));
-  ER_D(hipMalloc((void**)&d_k1, (size_t)N * 8));
-  ER_D(hipMalloc((void**)&d_uni, (size_t)N * 8));
-  ER_D(hipMalloc((void**)&d_v0, (size_t)N * 4));
-  ER_D(hipMalloc((void**)&d_v1, (size_t)N * 4));
-  ER_D(hipMalloc((void**)&d_a, (size_t)N * 4));
-  ER_D(hipMalloc((void**)&d_b, (size_t)N * 4));
-  ER_D(hipMalloc((void**)&d_cnt, (size_t)N * 4));
-  ER_D(hipMalloc((void**)&d_first, (size_t)N * 4));
-  ER_D(hipMalloc((void**)&d_second, (size_t)N * 4));
-  ER_D(hipMemcpyAsync(d_lists, pairs_dev, (size_t)n_pairs * sizeof(int*), hipMemcpyHostToDevice, h->stream));
-  ER_D(hipMemcpyAsync(d_off, off.data(), ((size_t)n_pairs + 1) * sizeof(long), hipMemcpyHostToDevice, h->stream));
-  ER_D(hipMemcpyAsync(d_fi, frag_i, (size_t)n_pairs * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  ER_D(hipMemcpyAsync(d_fj, frag_j, (size_t)n_pairs * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  ER_D(hipMemcpyAsync(d_fn, fn.data(), (size_t)h->num * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  ER_D(hipMemsetAsync(d_bad, 0, 5 * sizeof(int), h->stream));
+  if (tmp.alloc(&d_lists, (size_t)n_pairs, who) || tmp.alloc(&d_off, (size_t)n_pairs + 1, who) || tmp.alloc(&d_fi, (size_t)n_pairs, who) ||
+      tmp.alloc(&d_fj, (size_t)n_pairs, who) || tmp.alloc(&d_fn, (size_t)h->num, who) || tmp.alloc(&d_bad, 5, who) || tmp.alloc(&d_runs, 1, who) ||
+      tmp.alloc(&d_k0, (size_t)N, who) || tmp.alloc(&d_k1, (size_t)N, who) || tmp.alloc(&d_uni, (size_t)N, who) || tmp.alloc(&d_v0, (size_t)N, who) ||
+      tmp.alloc(&d_v1, (size_t)N, who) || tmp.alloc(&d_a, (size_t)N, who) || tmp.alloc(&d_b, (size_t)N, who) || tmp.alloc(&d_cnt, (size_t)N, who) ||
+      h->d_first.reserve((size_t)N, who) || h->d_second.reserve((size_t)N, who))
+    return 1;
+  ER_W(who, hipMemcpyAsync(d_lists, pairs_dev, (size_t)n_pairs * sizeof(int*), hipMemcpyHostToDevice, h->stream));
+  ER_W(who, hipMemcpyAsync(d_off, off.data(), ((size_t)n_pairs + 1) * sizeof(long), hipMemcpyHostToDevice, h->stream));
+  ER_W(who, hipMemcpyAsync(d_fi, frag_i, (size_t)n_pairs * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  ER_W(who, hipMemcpyAsync(d_fj, frag_j, (size_t)n_pairs * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  ER_W(who, hipMemcpyAsync(d_fn, fn.data(), (size_t)h->num * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  ER_W(who, hipMemsetAsync(d_bad, 0, 5 * sizeof(int), h->stream));
   {
     int mx = 1;
     for (int l = 0; l < n_pairs; l++) mx = std::max(mx, counts[l]);
     hipLaunchKernelGGL(k_corr_keys, dim3(std::min((mx + kBlock - 1) / kBlock, 1024), n_pairs), dim3(kBlock), 0, h->stream, d_lists, d_off, d_fi, d_fj, h->d_frags, d_fn,
                        d_k0, d_v0, d_a, d_b, d_bad);
   }
-  ER_D(hipGetLastError());
-  ER_D(hipcub::DeviceRadixSort::SortPairs(nullptr, need_sort, d_k0, d_k1, d_v0, d_v1, (int)N, 0, 40 + lbits, h->stream));
-  ER_D(hipcub::DeviceRunLengthEncode::Encode(nullptr, need_rle, d_k1, d_uni, d_cnt, d_runs, (int)N, h->stream));
+  ER_W(who, hipGetLastError());
+  ER_W(who, hipcub::DeviceRadixSort::SortPairs(nullptr, need_sort, d_k0, d_k1, d_v0, d_v1, (int)N, 0, 40 + lbits, h->stream));
+  ER_W(who, hipcub::DeviceRunLengthEncode::Encode(nullptr, need_rle, d_k1, d_uni, d_cnt, d_runs, (int)N, h->stream));
   {
     size_t need = std::max(need_sort, need_rle);
-    ER_D(hipMalloc(&d_tmp, need));
+    if (tmp.alloc(&d_tmp, need, who)) return 1;
     size_t t = need;
-    ER_D(hipcub::DeviceRadixSort::SortPairs(d_tmp, t, d_k0, d_k1, d_v0, d_v1, (int)N, 0, 40 + lbits, h->stream));
+    ER_W(who, hipcub::DeviceRadixSort::SortPairs(d_tmp, t, d_k0, d_k1, d_v0, d_v1, (int)N, 0, 40 + lbits, h->stream));
     t = need;
-    ER_D(hipcub::DeviceRunLengthEncode::Encode(d_tmp, t, d_k1, d_uni, d_cnt, d_runs, (int)N, h->stream));
+    ER_W(who, hipcub::DeviceRunLengthEncode::Encode(d_tmp, t, d_k1, d_uni, d_cnt, d_runs, (int)N, h->stream));
   }
-  hipLaunchKernelGGL(k_corr_gather, dim3((unsigned)((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, d_v1, d_a, d_b, N, d_first, d_second);
-  ER_D(hipGetLastError());
-  ER_D(hipMemcpyAsync(bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, h->stream));
-  ER_D(hipMemcpyAsync(&runs, d_runs, sizeof runs, hipMemcpyDeviceToHost, h->stream));
-  ER_D(hipStreamSynchronize(h->stream));
+  hipLaunchKernelGGL(k_corr_gather, dim3((unsigned)((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, d_v1, d_a, d_b, N, h->d_first, h->d_second);
+  ER_W(who, hipGetLastError());
+  ER_W(who, hipMemcpyAsync(bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, h->stream));
+  ER_W(who, hipMemcpyAsync(&runs, d_runs, sizeof runs, hipMemcpyDeviceToHost, h->stream));
+  ER_W(who, hipStreamSynchronize(h->stream));
   if (bad[0]) {
-    rc = er::fail("er_fopt_set_correspondences_dev: pair %d row %d (%d, %d) out of range (%d, %d points)", bad[1], bad[2], bad[3], bad[4],
-                  fn[(size_t)frag_i[bad[1]]], fn[(size_t)frag_j[bad[1]]]);
-    goto done;
+    return er::fail("er_fopt_set_correspondences_dev: pair %d row %d (%d, %d) out of range (%d, %d points)", bad[1], bad[2], bad[3], bad[4],
+                    fn[(size_t)frag_i[bad[1]]], fn[(size_t)frag_j[bad[1]]]);
   }
   uni.resize((size_t)runs);
   cnt.resize((size_t)runs);
-  ER_D(hipMemcpy(uni.data(), d_uni, (size_t)runs * 8, hipMemcpyDeviceToHost));
-  ER_D(hipMemcpy(cnt.data(), d_cnt, (size_t)runs * 4, hipMemcpyDeviceToHost));
+  ER_W(who, hipMemcpy(uni.data(), d_uni, (size_t)runs * 8, hipMemcpyDeviceToHost));
+  ER_W(who, hipMemcpy(cnt.data(), d_cnt, (size_t)runs * 4, hipMemcpyDeviceToHost));
   {
     long start = 0;
     for (int r = 0; r < runs; r++) {                            // the group table: the only part of the lists' structure that visits the host
@@ -959,24 +918,14 @@ int er_fopt_set_correspondences_dev(er_fopt_t h, int n_pairs, const int* frag_i,
       start += m;
     }
   }
-  ER_D(hipMalloc((void**)&h->d_chunks, chunks.size() * sizeof(Chunk)));
-  ER_D(hipMemcpy(h->d_chunks, chunks.data(), chunks.size() * sizeof(Chunk), hipMemcpyHostToDevice));
-  h->d_first = d_first;
-  h->d_second = d_second;
-  d_first = d_second = nullptr;                                 // (now owned by the handle)
+  if (h->d_chunks.reserve(chunks.size(), who)) return 1;
+  ER_W(who, hipMemcpy(h->d_chunks, chunks.data(), chunks.size() * sizeof(Chunk), hipMemcpyHostToDevice));
   h->n_pairs = n_pairs;
   h->n_chunks = (int)chunks.size();
   h->n_groups = runs;
   h->group_info.swap(ginfo);
   h->n_corr = N;
-#undef ER_D
-done:
-  {
-    void* tmp[] = {(void*)d_lists, d_off, d_fi, d_fj, d_fn, d_a, d_b, d_bad, d_cnt, d_runs, d_first, d_second, d_k0, d_k1, d_uni, d_v0, d_v1, d_tmp};
-    for (void* p : tmp)
-      if (p) (void)hipFree(p);
-  }
-  return rc;
+  return 0;
 }
 
 int er_fopt_group_count(er_fopt_t h) { return h ? h->n_groups : -1; }
@@ -1002,20 +951,7 @@ int er_fopt_assemble_nonrigid(er_fopt_t h, double weight, double* diag, double* 
   ER_HIP_TRY(hipSetDevice(h->device));
   const size_t nv = (size_t)(h->res + 1) * (h->res + 1) * (h->res + 1);
   const size_t nd = (size_t)h->num * nv * 576, no = (size_t)std::max(h->n_groups, 1) * 576;
-  if (nd > h->diag_cap) {
-    if (h->d_diag) (void)hipFree(h->d_diag);
-    h->d_diag = nullptr;
-    h->diag_cap = 0;
-    ER_HIP_TRY(hipMalloc((void**)&h->d_diag, nd * sizeof(double)));
-    h->diag_cap = nd;
-  }
-  if (no > h->off_cap) {
-    if (h->d_off) (void)hipFree(h->d_off);
-    h->d_off = nullptr;
-    h->off_cap = 0;
-    ER_HIP_TRY(hipMalloc((void**)&h->d_off, no * sizeof(double)));
-    h->off_cap = no;
-  }
+  if (h->d_diag.reserve(nd, "er_fopt_assemble_nonrigid") || h->d_off.reserve(no, "er_fopt_assemble_nonrigid")) return 1;
   ER_HIP_TRY(hipMemsetAsync(h->d_diag, 0, nd * sizeof(double), h->stream));
   ER_HIP_TRY(hipMemsetAsync(h->d_off, 0, no * sizeof(double), h->stream));
   ER_HIP_TRY(hipMemcpyAsync(h->d_rot, &weight, sizeof(double), hipMemcpyHostToDevice, h->stream));     // MODE 2 reads the weight from rot_t[0]
@@ -1066,13 +1002,10 @@ static int potrf_lower(er_fopt_t h, double* A, long n, long lda) {
 
 static int factor_common(er_fopt_t h, double* A, long n) {
   if (rocblas_load(h->roc, h->stream)) return 1;
-  if (!h->d_info) ER_HIP_TRY(hipMalloc((void**)&h->d_info, sizeof(int)));
-  if (h->d_rhs) {
-    (void)hipFree(h->d_rhs);
-    h->d_rhs = nullptr;
-  }
+  if (h->d_info.reserve(1, "er_fopt_factor")) return 1;
+  h->d_rhs.reset();                                              // (as large as this system, never larger)
   if (n > 2147483647L) return er::fail("system too large for the 32-bit rocBLAS interface (%ld unknowns)", n);
-  ER_HIP_TRY(hipMalloc((void**)&h->d_rhs, (size_t)n * sizeof(double)));
+  if (h->d_rhs.reserve((size_t)n, "er_fopt_factor")) return 1;
   // ER_FOPT_DIAG=1 (debugging aid): keep a host copy of the assembled matrix and, if potrf_lower reports a non-positive pivot,
   // factor that copy on the host -- tells a wrong matrix (assembly) from a wrong factorisation.
   if (h->shift_index >= 0 && h->shift_index < n) {
@@ -1196,19 +1129,12 @@ static int factor_nonrigid_blocked(er_fopt_t h, size_t nv, size_t nd) {
   const long bsz = (long)B * B;
   const int n_blocks = block_symbolic(h);
   const size_t need = (size_t)n_blocks * (size_t)bsz;
-  if (need > h->big_cap) {
-    if (h->d_big) (void)hipFree(h->d_big);
-    h->d_big = nullptr;
-    h->big_cap = 0;
-    hipError_t e = hipMalloc((void**)&h->d_big, need * sizeof(double));
-    if (e != hipSuccess)
-      return er::fail("er_fopt_factor_nonrigid: %d fragment blocks of %d x %d float64 (%.1f GB) do not fit: %s", n_blocks, B, B, (double)need * 8 / 1e9,
-                      hipGetErrorString(e));
-    h->big_cap = need;
+  if (h->d_big.reserve(need, "er_fopt_factor_nonrigid")) {
+    const std::string why = er::error_buffer();
+    return er::fail("er_fopt_factor_nonrigid: %d fragment blocks of %d x %d float64 (%.1f GB) do not fit: %s", n_blocks, B, B, (double)need * 8 / 1e9, why.c_str());
   }
-  if (h->d_blk_off) (void)hipFree(h->d_blk_off);
-  h->d_blk_off = nullptr;
-  ER_HIP_TRY(hipMalloc((void**)&h->d_blk_off, (size_t)nb * nb * sizeof(long)));
+  h->d_blk_off.reset();
+  if (h->d_blk_off.reserve((size_t)nb * nb, "er_fopt_factor_nonrigid")) return 1;
   ER_HIP_TRY(hipMemcpyAsync(h->d_blk_off, h->blk_off.data(), (size_t)nb * nb * sizeof(long), hipMemcpyHostToDevice, h->stream));
   ER_HIP_TRY(hipMemsetAsync(h->d_big, 0, need * sizeof(double), h->stream));
   const MatView V{h->d_big, 0, h->d_blk_off, nb, (long)B};
@@ -1224,12 +1150,9 @@ static int factor_nonrigid_blocked(er_fopt_t h, size_t nv, size_t nd) {
     hipLaunchKernelGGL(k_fopt_add_diag_v, dim3(1), dim3(64), 0, h->stream, V, h->shift_index, 1, h->shift_value);
   ER_HIP_TRY(hipGetLastError());
   // ---- numeric factorisation, right-looking over the blocks ----
-  if (!h->d_info) ER_HIP_TRY(hipMalloc((void**)&h->d_info, sizeof(int)));
-  if (h->d_rhs) {
-    (void)hipFree(h->d_rhs);
-    h->d_rhs = nullptr;
-  }
-  ER_HIP_TRY(hipMalloc((void**)&h->d_rhs, (size_t)nb * B * sizeof(double)));
+  if (h->d_info.reserve(1, "er_fopt_factor_nonrigid")) return 1;
+  h->d_rhs.reset();
+  if (h->d_rhs.reserve((size_t)nb * B, "er_fopt_factor_nonrigid")) return 1;
   const double one = 1.0, minus = -1.0;
   auto blk = [&](int i, int j) { return h->d_big + h->blk_off[(size_t)i * nb + j]; };
   for (int k = 0; k < nb; k++) {
@@ -1296,22 +1219,9 @@ static int factor_nonrigid_once(er_fopt_t h, double weight) {
   h->blocked = false;
   const size_t nv = (size_t)h->nper / 3, M = (size_t)h->num * h->nper;
   const size_t nd = (size_t)h->num * nv * 576, no = (size_t)std::max(h->n_groups, 1) * 576;
-  if (nd > h->diag_cap) {
-    if (h->d_diag) (void)hipFree(h->d_diag);
-    h->d_diag = nullptr;
-    h->diag_cap = 0;
-    ER_HIP_TRY(hipMalloc((void**)&h->d_diag, nd * sizeof(double)));
-    h->diag_cap = nd;
-  }
-  if (no > h->off_cap) {
-    if (h->d_off) (void)hipFree(h->d_off);
-    h->d_off = nullptr;
-    h->off_cap = 0;
-    ER_HIP_TRY(hipMalloc((void**)&h->d_off, no * sizeof(double)));
-    h->off_cap = no;
-  }
+  if (h->d_diag.reserve(nd, "er_fopt_factor_nonrigid") || h->d_off.reserve(no, "er_fopt_factor_nonrigid")) return 1;
   if (!h->d_ginfo && h->n_groups > 0) {
-    ER_HIP_TRY(hipMalloc((void**)&h->d_ginfo, (size_t)h->n_groups * 4 * sizeof(int)));
+    if (h->d_ginfo.reserve((size_t)h->n_groups * 4, "er_fopt_factor_nonrigid")) return 1;
     ER_HIP_TRY(hipMemcpyAsync(h->d_ginfo, h->group_info.data(), (size_t)h->n_groups * 4 * sizeof(int), hipMemcpyHostToDevice, h->stream));
   }
   ER_HIP_TRY(hipMemsetAsync(h->d_diag, 0, nd * sizeof(double), h->stream));
@@ -1326,13 +1236,9 @@ static int factor_nonrigid_once(er_fopt_t h, double weight) {
   const char* env = getenv("ER_FOPT_DENSE_MAX");
   const size_t dense_max = env ? (size_t)atol(env) : 30000;
   if (M > dense_max) return factor_nonrigid_blocked(h, nv, nd);
-  if (M * M > h->big_cap) {
-    if (h->d_big) (void)hipFree(h->d_big);
-    h->d_big = nullptr;
-    h->big_cap = 0;
-    hipError_t e = hipMalloc((void**)&h->d_big, M * M * sizeof(double));
-    if (e != hipSuccess) return er::fail("er_fopt_factor_nonrigid: %zu x %zu float64 system (%.1f GB) does not fit: %s", M, M, (double)(M * M * 8) / 1e9, hipGetErrorString(e));
-    h->big_cap = M * M;
+  if (h->d_big.reserve(M * M, "er_fopt_factor_nonrigid")) {
+    const std::string why = er::error_buffer();
+    return er::fail("er_fopt_factor_nonrigid: %zu x %zu float64 system (%.1f GB) does not fit: %s", M, M, (double)(M * M * 8) / 1e9, why.c_str());
   }
   ER_HIP_TRY(hipMemsetAsync(h->d_big, 0, M * M * sizeof(double), h->stream));
   const MatView V{h->d_big, (long)M, nullptr, 0, 0};

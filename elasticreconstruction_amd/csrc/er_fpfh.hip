@@ -301,7 +301,7 @@ int er_cloud_voxel_grid(er_cloud_t in, float leaf, float grid_cell, er_cloud_t* 
   StreamLease L;
   if (L.acquire(in->device)) return 1;
   hipStream_t st = L.stream;
-  DevBufs B;
+  DevScope B;
   // the cloud's bounding box (k_chunk_bounds of the grid builder), then min_b / max_b = the cell of its corners: x -> floor(fl32(x * inv)) is monotonic
   float box_lo[3], box_hi[3];
   if (er::cloud_bounds(in, st, box_lo, box_hi)) return 1;
@@ -323,18 +323,18 @@ int er_cloud_voxel_grid(er_cloud_t in, float leaf, float grid_cell, er_cloud_t* 
   while (bits < 31 && (1L << bits) < (long)cells) bits++;
   unsigned *k0, *k1, *x0, *x1;
   int *head, *seg;
-  ER_HIP_TRY(B.alloc(&k0, (size_t)n * sizeof(unsigned)));
-  ER_HIP_TRY(B.alloc(&k1, (size_t)n * sizeof(unsigned)));
-  ER_HIP_TRY(B.alloc(&x0, (size_t)n * sizeof(unsigned)));
-  ER_HIP_TRY(B.alloc(&x1, (size_t)n * sizeof(unsigned)));
-  ER_HIP_TRY(B.alloc(&head, (size_t)n * sizeof(int)));
-  ER_HIP_TRY(B.alloc(&seg, (size_t)n * sizeof(int)));
+  if (B.alloc(&k0, (size_t)n, "er_cloud_voxel_grid")) return 1;
+  if (B.alloc(&k1, (size_t)n, "er_cloud_voxel_grid")) return 1;
+  if (B.alloc(&x0, (size_t)n, "er_cloud_voxel_grid")) return 1;
+  if (B.alloc(&x1, (size_t)n, "er_cloud_voxel_grid")) return 1;
+  if (B.alloc(&head, (size_t)n, "er_cloud_voxel_grid")) return 1;
+  if (B.alloc(&seg, (size_t)n, "er_cloud_voxel_grid")) return 1;
   size_t need_sort = 0, need_scan = 0;
   ER_HIP_TRY(er::sort_pairs_u32(nullptr, need_sort, k0, k1, x0, x1, n, 0, bits, st));
   ER_HIP_TRY(er::inclusive_sum_i32(nullptr, need_scan, head, seg, n, st));
   size_t tmp_bytes = std::max(need_sort, need_scan);
   char* tmp;
-  ER_HIP_TRY(B.alloc(&tmp, tmp_bytes));
+  if (B.alloc(&tmp, tmp_bytes, "er_cloud_voxel_grid")) return 1;
   hipLaunchKernelGGL(k_vox_keys, dim3(nblocks_of(n)), dim3(kBlock), 0, st, in->xyz, n, V, k0, x0);
   size_t t = tmp_bytes;
   ER_HIP_TRY(er::sort_pairs_u32(tmp, t, k0, k1, x0, x1, n, 0, bits, st));       // stable: a cell's members stay in file order
@@ -348,9 +348,9 @@ int er_cloud_voxel_grid(er_cloud_t in, float leaf, float grid_cell, er_cloud_t* 
   if (m < 1 || m > n) return er::fail("er_cloud_voxel_grid: internal error (%d cells of %d points)", m, n);
   int* start;
   float *oxyz, *onrm;
-  ER_HIP_TRY(B.alloc(&start, ((size_t)m + 1) * sizeof(int)));
-  ER_HIP_TRY(B.alloc(&oxyz, (size_t)m * 3 * sizeof(float)));
-  ER_HIP_TRY(B.alloc(&onrm, (size_t)m * 3 * sizeof(float)));
+  if (B.alloc(&start, (size_t)m + 1, "er_cloud_voxel_grid")) return 1;
+  if (B.alloc(&oxyz, (size_t)m * 3, "er_cloud_voxel_grid")) return 1;
+  if (B.alloc(&onrm, (size_t)m * 3, "er_cloud_voxel_grid")) return 1;
   hipLaunchKernelGGL(k_vox_starts, dim3(nblocks_of(n)), dim3(kBlock), 0, st, k1, seg, n, m, start);
   hipLaunchKernelGGL(k_vox_mean, dim3(nblocks_of(m)), dim3(kBlock), 0, st, in->xyz, in->nrm, x1, start, m, oxyz, onrm);
   ER_HIP_TRY(hipGetLastError());
@@ -372,11 +372,11 @@ int er_cloud_estimate_normals(er_cloud_t in, float radius, er_cloud_t* out, int*
   StreamLease L;
   if (L.acquire(in->device)) return 1;
   hipStream_t st = L.stream;
-  DevBufs B;
+  DevScope B;
   float* nrm;
   int* nn;
-  ER_HIP_TRY(B.alloc(&nrm, (size_t)n * 3 * sizeof(float)));
-  ER_HIP_TRY(B.alloc(&nn, (size_t)n * sizeof(int)));
+  if (B.alloc(&nrm, (size_t)n * 3, "er_cloud_estimate_normals")) return 1;
+  if (B.alloc(&nn, (size_t)n, "er_cloud_estimate_normals")) return 1;
   hipLaunchKernelGGL(k_fp_normals, dim3(fp_blocks(n)), dim3(kBlock), 0, st, T.c->xn, n, T.c->grid, radius * radius, nrm, nn);
   ER_HIP_TRY(hipGetLastError());
   if (n_neighbours_host) ER_HIP_TRY(hipMemcpyAsync(n_neighbours_host, nn, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -396,16 +396,16 @@ int er_fpfh_estimate(er_cloud_t c, float radius, er_features_t* out, int* spfh_c
   StreamLease L;
   if (L.acquire(c->device)) return 1;
   hipStream_t st = L.stream;
-  DevBufs B;
+  DevScope B;
   int *counts, *nn;
-  ER_HIP_TRY(B.alloc(&counts, (size_t)n * er_fp::kDim * sizeof(int)));
-  ER_HIP_TRY(B.alloc(&nn, (size_t)n * sizeof(int)));
+  if (B.alloc(&counts, (size_t)n * er_fp::kDim, "er_fpfh_estimate")) return 1;
+  if (B.alloc(&nn, (size_t)n, "er_fpfh_estimate")) return 1;
   er_features_s* f = new er_features_s();
   f->device = c->device; f->n = n; f->dim = er_fp::kDim; f->dp = (er_fp::kDim + 7) / 8 * 8;
   const size_t fbytes = (size_t)n * f->dp * sizeof(float);
-  if (hipMalloc((void**)&f->d, fbytes) != hipSuccess) {
+  if (f->d.reserve((size_t)n * f->dp, "er_fpfh_estimate")) {
     delete f;
-    return er::fail("er_fpfh_estimate: hipMalloc(%zu) failed: %s", fbytes, hipGetErrorString(hipGetLastError()));
+    return 1;
   }
   const float r2 = radius * radius;
   hipError_t e = hipMemsetAsync(f->d, 0, fbytes, st);
@@ -419,7 +419,6 @@ int er_fpfh_estimate(er_cloud_t c, float radius, er_features_t* out, int* spfh_c
   if (e == hipSuccess && n_neighbours_host) e = hipMemcpyAsync(n_neighbours_host, nn, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) {
-    (void)hipFree(f->d);
     delete f;
     return er::fail("er_fpfh_estimate: %s", hipGetErrorString(e));
   }

@@ -7,6 +7,7 @@
 // computes is DepthOdometry.track_model on its fragment's frames, call for call (the same kernels on the same data in the same order per
 // volume), so every pose, status, point and normal is the same bits whatever the lane count and whichever lane a fragment lands on.
 #include "er_common.h"
+#include "er_mem.h"
 
 #include "../../include/er_hip.h"
 
@@ -20,6 +21,7 @@ namespace {
 
 struct Lane {
   er_tsdf_t vol = nullptr;
+  er::DevScope mem;              // owns rec[]
   std::vector<void*> rec;        // [levels] record maps of the lane's model, device memory
   int frag = -1;                 // the fragment in flight (-1: idle)
   int pos = 0;                   // its next frame, counted from the fragment's first
@@ -48,8 +50,7 @@ void frag_free(er_frag_s* h) {
   (void)hipSetDevice(h->device);
   for (Lane& L : h->lanes) {
     if (L.vol) er_tsdf_destroy(L.vol);
-    for (void* p : L.rec)
-      if (p) (void)hipFree(p);
+    L.mem.free_all();
   }
   if (h->odom) er_odom_destroy(h->odom);
   delete h;
@@ -128,7 +129,7 @@ int er_frag_create(int cols, int rows, const float cam6[6], const er_odom_params
     bool ok = er_tsdf_create(cols, rows, cam6, P.max_units, device, &L.vol) == 0;
     L.rec.assign((size_t)h->levels, nullptr);
     for (int l = 0; ok && l < h->levels; l++)
-      ok = hipMalloc(&L.rec[(size_t)l], (size_t)(cols >> l) * (rows >> l) * 32) == hipSuccess;
+      ok = L.mem.alloc(&L.rec[(size_t)l], (size_t)(cols >> l) * (rows >> l) * 32, who) == 0;
     if (!ok) {
       const size_t need = h->lane_bytes ? h->lane_bytes : estimate;
       std::string why = er_last_error();
@@ -168,13 +169,13 @@ int er_frag_build(er_frag_t h, int n_frames, const uint16_t* depth, int depth_on
   ER_HIP_TRY(hipSetDevice(h->device));
   const size_t px = (size_t)h->cols * h->rows;
   // Host depth is uploaded once; the odometry and the lane volumes read that copy.
+  er::DevScope own;
   uint16_t* d_own = nullptr;
   if (!depth_on_device) {
     const size_t bytes = (size_t)n_frames * px * sizeof(uint16_t);
-    hipError_t e = hipMalloc((void**)&d_own, bytes);
-    if (e == hipSuccess) e = hipMemcpy(d_own, depth, bytes, hipMemcpyHostToDevice);
+    if (own.alloc(&d_own, (size_t)n_frames * px, who)) return 1;
+    const hipError_t e = hipMemcpy(d_own, depth, bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
-      if (d_own) (void)hipFree(d_own);
       return er::fail("%s: %zu bytes for the depth stream on the device: %s", who, bytes, hipGetErrorString(e));
     }
   }
@@ -281,7 +282,6 @@ int er_frag_build(er_frag_t h, int n_frames, const uint16_t* depth, int depth_on
     for (Lane& L : h->lanes) (void)er_tsdf_synchronize(L.vol);
     er::fail("%s", why.c_str());
   }
-  if (d_own) (void)hipFree(d_own);
   return rc;
 }
 

@@ -771,51 +771,34 @@ __global__ __launch_bounds__(kBlock) void k_compact(const PairDev* __restrict__ 
 // per-source-point scratch cut into one slice per pair.  Groups live in a per-device pool: an API call borrows one (calls from
 // several host threads -- the reference's "#pragma omp parallel for" -- borrow one each and overlap on the GPU) and returns it.
 // The pool is never freed behind the HIP runtime's back (er_icp_release_workspaces does it).
-struct Group {
+// The memory of a group.  A fresh GroupMem assigned over it frees all of it, at that point (group_destroy: before the streams go).
+struct GroupMem {
+  // per pair, device and pinned host mirrors: they grow together (group_reserve), d_pairs first, so its capacity is the group's
+  Buffer<PairDev> d_pairs;
+  Buffer<IcpDev> d_state;
+  Buffer<int> d_active, d_counts, d_totals;
+  Buffer<double> d_info, d_fit;                    // kAcc per pair; 2 per pair
+  PinnedBuffer<PairDev> h_pairs;
+  PinnedBuffer<IcpDev> h_state;
+  PinnedBuffer<int> h_active, h_counts, h_totals;
+  PinnedBuffer<double> h_info, h_fit;
+  // slabs of per-source-point scratch: [3 points], [points], [2 points], [blocks], [blocks], [64 parts]; they regrow together too
+  Buffer<float> X;
+  Buffer<int> match, pairs, block_count, block_offset;
+  Buffer<double> partial;
+  PinnedBuffer<int> stage;      // pair lists on their way to pageable caller memory (lazy)
+};
+
+struct Group : GroupMem {
   int device = 0;
   hipStream_t stream = nullptr, copy_stream = nullptr, copy_stream2 = nullptr;   // copy streams: list copies alternate between them
   hipEvent_t ev = nullptr, ev2 = nullptr;
   std::vector<hipEvent_t> sub_ev, sub_ev2;  // per sub-group of er_find_correspondence_batch (grown on demand): done / scanned
-  int cap_pairs = 0;
-  size_t cap_points = 0, cap_blocks = 0, cap_parts = 0;
-  // device
-  PairDev* d_pairs = nullptr;
-  IcpDev* d_state = nullptr;
-  int *d_active = nullptr, *d_counts = nullptr, *d_totals = nullptr;
-  double *d_info = nullptr, *d_fit = nullptr;      // kAcc per pair; 2 per pair
-  float* X = nullptr;
-  int *match = nullptr, *pairs = nullptr, *block_count = nullptr, *block_offset = nullptr;
-  double* partial = nullptr;
-  // pinned host mirrors
-  PairDev* h_pairs = nullptr;
-  IcpDev* h_state = nullptr;
-  int *h_active = nullptr, *h_counts = nullptr, *h_totals = nullptr;
-  double *h_info = nullptr, *h_fit = nullptr;
-  int* stage = nullptr;         // pinned: pair lists on their way to pageable caller memory (lazy)
-  size_t stage_cap = 0;
+  int cap_pairs() const { return (int)d_pairs.capacity(); }
+  size_t cap_points() const { return match.capacity(); }
+  size_t cap_blocks() const { return block_count.capacity(); }
+  size_t cap_parts() const { return partial.capacity() / 64; }
 };
-
-void group_free_slabs(Group* g) {
-  void* ptrs[] = {g->X, g->match, g->pairs, g->block_count, g->block_offset, g->partial};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  g->X = nullptr;
-  g->match = g->pairs = g->block_count = g->block_offset = nullptr;
-  g->partial = nullptr;
-  g->cap_points = g->cap_blocks = g->cap_parts = 0;
-}
-
-void group_free_pairs(Group* g) {
-  void* dev[] = {g->d_pairs, g->d_state, g->d_active, g->d_counts, g->d_totals, g->d_info, g->d_fit};
-  for (void* p : dev)
-    if (p) (void)hipFree(p);
-  void* host[] = {g->h_pairs, g->h_state, g->h_active, g->h_counts, g->h_totals, g->h_info, g->h_fit};
-  for (void* p : host)
-    if (p) (void)hipHostFree(p);
-  g->d_pairs = nullptr; g->d_state = nullptr; g->d_active = g->d_counts = g->d_totals = nullptr; g->d_info = g->d_fit = nullptr;
-  g->h_pairs = nullptr; g->h_state = nullptr; g->h_active = g->h_counts = g->h_totals = nullptr; g->h_info = g->h_fit = nullptr;
-  g->cap_pairs = 0;
-}
 
 void group_destroy(Group* g) {
   if (!g) return;
@@ -823,9 +806,7 @@ void group_destroy(Group* g) {
   if (g->stream) (void)hipStreamSynchronize(g->stream);
   if (g->copy_stream) (void)hipStreamSynchronize(g->copy_stream);
   if (g->copy_stream2) (void)hipStreamSynchronize(g->copy_stream2);
-  group_free_slabs(g);
-  group_free_pairs(g);
-  if (g->stage) (void)hipHostFree(g->stage);
+  static_cast<GroupMem&>(*g) = GroupMem();
   if (g->ev) (void)hipEventDestroy(g->ev);
   if (g->ev2) (void)hipEventDestroy(g->ev2);
   for (hipEvent_t e : g->sub_ev)
@@ -846,42 +827,33 @@ int nparts_of(int n, int pts) { return (std::max(n, 1) + kBlock * pts - 1) / (kB
 
 // Room for `pairs` descriptors and, when per-point scratch is needed, for `points` source points in `blocks` / `parts` blocks.
 int group_reserve(Group* g, int pairs, size_t points, size_t blocks, size_t parts) {
-  if (pairs > g->cap_pairs) {
+  const char* who = "the ICP workspace";
+  if (pairs > g->cap_pairs()) {
     ER_HIP_TRY(hipStreamSynchronize(g->stream));
-    group_free_pairs(g);
     const size_t c = (size_t)std::max(pairs, 16);
-    ER_HIP_TRY(hipMalloc((void**)&g->d_pairs, c * sizeof(PairDev)));
-    ER_HIP_TRY(hipMalloc((void**)&g->d_state, c * sizeof(IcpDev)));
-    ER_HIP_TRY(hipMalloc((void**)&g->d_active, c * sizeof(int)));
-    ER_HIP_TRY(hipMalloc((void**)&g->d_counts, c * sizeof(int)));
-    ER_HIP_TRY(hipMalloc((void**)&g->d_totals, c * sizeof(int)));
-    ER_HIP_TRY(hipMalloc((void**)&g->d_info, c * kAcc * sizeof(double)));
-    ER_HIP_TRY(hipMalloc((void**)&g->d_fit, c * 2 * sizeof(double)));
-    ER_HIP_TRY(hipHostMalloc((void**)&g->h_pairs, c * sizeof(PairDev), hipHostMallocDefault));
-    ER_HIP_TRY(hipHostMalloc((void**)&g->h_state, c * sizeof(IcpDev), hipHostMallocDefault));
-    ER_HIP_TRY(hipHostMalloc((void**)&g->h_active, c * sizeof(int), hipHostMallocDefault));
-    ER_HIP_TRY(hipHostMalloc((void**)&g->h_counts, c * sizeof(int), hipHostMallocDefault));
-    ER_HIP_TRY(hipHostMalloc((void**)&g->h_totals, c * sizeof(int), hipHostMallocDefault));
-    ER_HIP_TRY(hipHostMalloc((void**)&g->h_info, c * kAcc * sizeof(double), hipHostMallocDefault));
-    ER_HIP_TRY(hipHostMalloc((void**)&g->h_fit, c * 2 * sizeof(double), hipHostMallocDefault));
-    g->cap_pairs = (int)c;
+    if (g->d_pairs.reserve(c, who) || g->d_state.reserve(c, who) || g->d_active.reserve(c, who) || g->d_counts.reserve(c, who) ||
+        g->d_totals.reserve(c, who) || g->d_info.reserve(c * kAcc, who) || g->d_fit.reserve(c * 2, who) || g->h_pairs.reserve(c, who) ||
+        g->h_state.reserve(c, who) || g->h_active.reserve(c, who) || g->h_counts.reserve(c, who) || g->h_totals.reserve(c, who) ||
+        g->h_info.reserve(c * kAcc, who) || g->h_fit.reserve(c * 2, who)) {
+      g->d_pairs.reset();                            // (capacity 0: the next call starts over)
+      return 1;
+    }
   }
-  if (points > g->cap_points || blocks > g->cap_blocks || parts > g->cap_parts) {
+  if (points > g->cap_points() || blocks > g->cap_blocks() || parts > g->cap_parts()) {
     ER_HIP_TRY(hipStreamSynchronize(g->stream));
     if (g->copy_stream) ER_HIP_TRY(hipStreamSynchronize(g->copy_stream));
     if (g->copy_stream2) ER_HIP_TRY(hipStreamSynchronize(g->copy_stream2));
-    const size_t cp = std::max(points + points / 8, g->cap_points), cb = std::max(blocks + blocks / 8, g->cap_blocks),
-                 cq = std::max(parts + parts / 8, g->cap_parts);
-    group_free_slabs(g);
-    ER_HIP_TRY(hipMalloc((void**)&g->X, std::max<size_t>(cp, 1) * 3 * sizeof(float)));
-    ER_HIP_TRY(hipMalloc((void**)&g->match, std::max<size_t>(cp, 1) * sizeof(int)));
-    ER_HIP_TRY(hipMalloc((void**)&g->pairs, std::max<size_t>(cp, 1) * 2 * sizeof(int)));
-    ER_HIP_TRY(hipMalloc((void**)&g->block_count, std::max<size_t>(cb, 1) * sizeof(int)));
-    ER_HIP_TRY(hipMalloc((void**)&g->block_offset, std::max<size_t>(cb, 1) * sizeof(int)));
-    ER_HIP_TRY(hipMalloc((void**)&g->partial, std::max<size_t>(cq, 1) * 64 * sizeof(double)));   // 32 x 16 bytes per part (k_icp_iter's 128-bit sums)
-    g->cap_points = cp;
-    g->cap_blocks = cb;
-    g->cap_parts = cq;
+    const size_t cp = std::max(points + points / 8, g->cap_points()), cb = std::max(blocks + blocks / 8, g->cap_blocks()),
+                 cq = std::max(parts + parts / 8, g->cap_parts());
+    auto drop = [g] {
+      g->X.reset(), g->match.reset(), g->pairs.reset(), g->block_count.reset(), g->block_offset.reset(), g->partial.reset();
+    };
+    drop();                                          // all six go before the first comes back
+    if (g->X.reserve(cp * 3, who) || g->match.reserve(cp, who) || g->pairs.reserve(cp * 2, who) || g->block_count.reserve(cb, who) ||
+        g->block_offset.reserve(cb, who) || g->partial.reserve(cq * 64, who)) {   // partial: 32 x 16 bytes per part (k_icp_iter's 128-bit sums)
+      drop();
+      return 1;
+    }
   }
   return 0;
 }
@@ -906,7 +878,7 @@ Group* group_acquire(int device) {
     auto& v = pool().idle;
     long best = -1;
     for (size_t i = 0; i < v.size(); i++)
-      if (v[i]->device == device && (best < 0 || v[i]->cap_points >= v[(size_t)best]->cap_points)) best = (long)i;
+      if (v[i]->device == device && (best < 0 || v[i]->cap_points() >= v[(size_t)best]->cap_points())) best = (long)i;
     if (best >= 0) {
       g = v[(size_t)best];
       v.erase(v.begin() + best);
@@ -1314,15 +1286,16 @@ int er_ransac_fitness_batch(er_cloud_t src, er_cloud_t tgt, int n_hyp, const flo
   GroupLease L;
   if (L.acquire(src->device)) return 1;
   Group* w = L.g;
+  DevScope tmp;
   float* d_hyp = nullptr;
   int* d_cnt = nullptr;
   double* d_sum = nullptr;
   std::vector<double> sums((size_t)n_hyp, 0.0);
   int rc = 0;
   const size_t nh = (size_t)n_hyp;
-  if (hipMalloc((void**)&d_hyp, nh * 16 * sizeof(float)) != hipSuccess || hipMalloc((void**)&d_cnt, nh * sizeof(int)) != hipSuccess ||
-      hipMalloc((void**)&d_sum, nh * sizeof(double)) != hipSuccess) {
-    rc = er::fail("er_ransac_fitness_batch: hipMalloc failed: %s", hipGetErrorString(hipGetLastError()));
+  if (tmp.alloc(&d_hyp, nh * 16, "er_ransac_fitness_batch") || tmp.alloc(&d_cnt, nh, "er_ransac_fitness_batch") ||
+      tmp.alloc(&d_sum, nh, "er_ransac_fitness_batch")) {
+    rc = 1;
   } else if (hipMemcpyAsync(d_hyp, M, nh * 16 * sizeof(float), hipMemcpyHostToDevice, w->stream) != hipSuccess ||
              hipMemsetAsync(d_cnt, 0, nh * sizeof(int), w->stream) != hipSuccess ||
              hipMemsetAsync(d_sum, 0, nh * sizeof(double), w->stream) != hipSuccess) {
@@ -1343,9 +1316,6 @@ int er_ransac_fitness_batch(er_cloud_t src, er_cloud_t tgt, int n_hyp, const flo
                     hipStreamSynchronize(w->stream) != hipSuccess))
       rc = er::fail("er_ransac_fitness_batch: %s", hipGetErrorString(hipGetLastError()));
   }
-  if (d_hyp) (void)hipFree(d_hyp);
-  if (d_cnt) (void)hipFree(d_cnt);
-  if (d_sum) (void)hipFree(d_sum);
   if (rc == 0 && fitness)
     for (int h = 0; h < n_hyp; h++) fitness[h] = inliers[h] > 0 ? sums[(size_t)h] / (double)inliers[h] : (double)FLT_MAX;   // :697-703
   return rc;
@@ -1376,15 +1346,10 @@ static int corr_chain(Group* g, int s0, int m, int mxb, bool want_source, bool w
 }
 
 static int stage_reserve(Group* g, size_t ints) {
-  if (ints <= g->stage_cap) return 0;
+  if (ints <= g->stage.capacity()) return 0;
   ER_HIP_TRY(hipStreamSynchronize(g->copy_stream));
   ER_HIP_TRY(hipStreamSynchronize(g->copy_stream2));
-  if (g->stage) (void)hipHostFree(g->stage);
-  g->stage = nullptr;
-  g->stage_cap = 0;
-  ER_HIP_TRY(hipHostMalloc((void**)&g->stage, ints * sizeof(int), hipHostMallocDefault));
-  g->stage_cap = ints;
-  return 0;
+  return g->stage.reserve(ints, "the ICP workspace");
 }
 
 int er_ransac_inliers(er_cloud_t src, er_cloud_t tgt, const float* M16, float corr_dist_threshold, int* pairs_host, int capacity,

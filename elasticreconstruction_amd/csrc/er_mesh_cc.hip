@@ -196,28 +196,6 @@ __global__ __launch_bounds__(kCcBlock) void k_cc_triangles(const int* __restrict
   out[3 * o + 2] = remap[c];
 }
 
-#define ER_W(who, expr)                                                                         \
-  do {                                                                                          \
-    hipError_t e_ = (expr);                                                                     \
-    if (e_ != hipSuccess) return er::fail("%s: %s failed: %s", who, #expr, hipGetErrorString(e_)); \
-  } while (0)
-// hipMalloc of a device temporary that `owned` frees: pp = the address of the caller's pointer.
-#define ER_W_OWNED(who, owned, pp, bytes)             \
-  do {                                                \
-    ER_W(who, hipMalloc((void**)pp, bytes));          \
-    (owned).push_back(*(pp));                         \
-  } while (0)
-
-struct Owned {
-  std::vector<void*> p;
-  Owned() = default;
-  Owned(const Owned&) = delete;
-  Owned& operator=(const Owned&) = delete;
-  ~Owned() {
-    for (void* q : p) (void)hipFree(q);
-  }
-};
-
 unsigned cc_grid(long n) { return (unsigned)((n + kCcBlock - 1) / kCcBlock); }
 
 // Labels and triangles per root of the nt > 0 triangles d_tri over nv > 0 vertices, on stream s: d_label[nv], d_cnt[nv] (the count at the
@@ -279,16 +257,16 @@ int er_mesh_components(const int* tri_host, long n_triangles, long n_vertices, i
   }
   ER_HIP_TRY(hipSetDevice(device));
   hipStream_t s = nullptr;                                   // (the null stream: the call is synchronous)
-  Owned own;
+  er::DevScope own;
   int *d_tri = nullptr, *d_label = nullptr, *d_word = nullptr;
   unsigned long long* d_cnt = nullptr;
   long *d_vcnt = nullptr, *d_blk = nullptr;
   const long nblk = (long)cc_grid(nv);
-  ER_W_OWNED(who, own.p, &d_tri, (size_t)nt * 3 * sizeof(int));
-  ER_W_OWNED(who, own.p, &d_label, (size_t)nv * sizeof(int));
-  ER_W_OWNED(who, own.p, &d_cnt, (size_t)nv * sizeof(unsigned long long));
-  ER_W_OWNED(who, own.p, &d_word, sizeof(int));
-  ER_W_OWNED(who, own.p, &d_blk, (size_t)nblk * 3 * sizeof(long));
+  if (own.alloc(&d_tri, (size_t)nt * 3, who)) return 1;
+  if (own.alloc(&d_label, (size_t)nv, who)) return 1;
+  if (own.alloc(&d_cnt, (size_t)nv, who)) return 1;
+  if (own.alloc(&d_word, 1, who)) return 1;
+  if (own.alloc(&d_blk, (size_t)nblk * 3, who)) return 1;
   ER_W(who, hipMemcpyAsync(d_tri, tri_host, (size_t)nt * 3 * sizeof(int), hipMemcpyHostToDevice, s));
   int r = 0;
   if (cc_label(who, s, d_tri, nt, nv, d_label, d_cnt, d_word, &r)) return 1;
@@ -298,7 +276,7 @@ int er_mesh_components(const int* tri_host, long n_triangles, long n_vertices, i
   std::vector<long> blk((size_t)nblk * 3);
   ER_W(who, hipMemcpyAsync(blk.data(), d_blk, blk.size() * sizeof(long), hipMemcpyDeviceToHost, s));
   if (count_host) {
-    ER_W_OWNED(who, own.p, &d_vcnt, (size_t)nv * sizeof(long));
+    if (own.alloc(&d_vcnt, (size_t)nv, who)) return 1;
     hipLaunchKernelGGL(k_cc_vertex_count, dim3((unsigned)nblk), dim3(kCcBlock), 0, s, d_label, d_cnt, nv, d_vcnt);
     ER_W(who, hipGetLastError());
     ER_W(who, hipMemcpyAsync(count_host, d_vcnt, (size_t)nv * sizeof(long), hipMemcpyDeviceToHost, s));
@@ -365,14 +343,14 @@ int mesh_cleaned_on_device(er_tsdf_t h, const char* who, long min_triangles, int
   // labels, triangles per root, the largest component
   int *d_label = nullptr, *d_word = nullptr;
   unsigned long long *d_cnt = nullptr, *d_best = nullptr;
-  ER_W_OWNED(who, m.owned, &d_label, (size_t)nv * sizeof(int));
-  ER_W_OWNED(who, m.owned, &d_cnt, (size_t)nv * sizeof(unsigned long long));
-  ER_W_OWNED(who, m.owned, &d_word, sizeof(int));
+  if (m.owned.alloc(&d_label, (size_t)nv, who)) return 1;
+  if (m.owned.alloc(&d_cnt, (size_t)nv, who)) return 1;
+  if (m.owned.alloc(&d_word, 1, who)) return 1;
   int r = 0, best = -1;
   if (cc_label(who, s, m.d_tri, nt, nv, d_label, d_cnt, d_word, &r)) return 1;
   if (largest_only) {
     unsigned long long key = 0ull;
-    ER_W_OWNED(who, m.owned, &d_best, sizeof(unsigned long long));
+    if (m.owned.alloc(&d_best, 1, who)) return 1;
     ER_W(who, hipMemsetAsync(d_best, 0, sizeof(unsigned long long), s));
     hipLaunchKernelGGL(k_cc_largest, dim3(cc_grid(nv)), dim3(kCcBlock), 0, s, d_label, d_cnt, nv, d_best);
     ER_W(who, hipGetLastError());
@@ -384,7 +362,7 @@ int mesh_cleaned_on_device(er_tsdf_t h, const char* who, long min_triangles, int
   // what stays: counts per block, offsets on the host
   const long nbv = (long)cc_grid(nv), nbt = (long)cc_grid(nt);
   long* d_blk = nullptr;                                      // [3 nbv] vertex counts, [nbt] triangle counts, then [nbv] and [nbt] offsets
-  ER_W_OWNED(who, m.owned, &d_blk, (size_t)(4 * nbv + 2 * nbt) * sizeof(long));
+  if (m.owned.alloc(&d_blk, (size_t)(4 * nbv + 2 * nbt), who)) return 1;
   long *d_bt = d_blk + 3 * nbv, *d_ov = d_bt + nbt, *d_ot = d_ov + nbv;
   int *d_remap = nullptr, *d_index = nullptr, *d_tri_out = nullptr;
   float4 *d_verts_out = nullptr, *d_nrm_out = nullptr;
@@ -428,13 +406,13 @@ int mesh_cleaned_on_device(er_tsdf_t h, const char* who, long min_triangles, int
 
   // the second passes
   ER_W(who, hipMemcpyAsync(d_ov, off.data(), off.size() * sizeof(long), hipMemcpyHostToDevice, s));
-  ER_W_OWNED(who, m.owned, &d_remap, (size_t)nv * sizeof(int));
-  ER_W_OWNED(who, m.owned, &d_index, (size_t)nvk * sizeof(int));
-  if (m.d_verts) ER_W_OWNED(who, m.owned, &d_verts_out, (size_t)nvk * sizeof(float4));
-  if (m.d_nrm) ER_W_OWNED(who, m.owned, &d_nrm_out, (size_t)nvk * sizeof(float4));
+  if (m.owned.alloc(&d_remap, (size_t)nv, who)) return 1;
+  if (m.owned.alloc(&d_index, (size_t)nvk, who)) return 1;
+  if (m.d_verts && m.owned.alloc(&d_verts_out, (size_t)nvk, who)) return 1;
+  if (m.d_nrm && m.owned.alloc(&d_nrm_out, (size_t)nvk, who)) return 1;
   if (vertices(1)) return 1;
   if (want_t && ntk > 0) {
-    ER_W_OWNED(who, m.owned, &d_tri_out, (size_t)ntk * 3 * sizeof(int));
+    if (m.owned.alloc(&d_tri_out, (size_t)ntk * 3, who)) return 1;
     if (triangles(1)) return 1;
   }
   c->d_verts = d_verts_out;
@@ -445,6 +423,3 @@ int mesh_cleaned_on_device(er_tsdf_t h, const char* who, long min_triangles, int
 }
 
 }  // namespace er_tsdf_k
-
-#undef ER_W_OWNED
-#undef ER_W

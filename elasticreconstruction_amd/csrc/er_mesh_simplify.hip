@@ -328,17 +328,6 @@ __global__ __launch_bounds__(kScBlock) void k_sc_cluster(const int* __restrict__
   if (v < nv) cluster[v] = rank[lead[v]];
 }
 
-#define ER_W(who, expr)                                                                         \
-  do {                                                                                          \
-    hipError_t e_ = (expr);                                                                     \
-    if (e_ != hipSuccess) return er::fail("%s: %s failed: %s", who, #expr, hipGetErrorString(e_)); \
-  } while (0)
-#define ER_W_OWNED(who, owned, pp, bytes)             \
-  do {                                                \
-    ER_W(who, hipMalloc((void**)pp, bytes));          \
-    (owned).push_back(*(pp));                         \
-  } while (0)
-
 unsigned sc_grid(long n) { return (unsigned)((n + kScBlock - 1) / kScBlock); }
 
 // slots of a table for n keys: a power of two, load at most 1/2
@@ -368,12 +357,12 @@ struct ScMesh {
 // The refusals of the input come first; then the counts and stats are set and counted(*out) refuses what the caller has to refuse (non-zero
 // ends the call with 1); then the arrays of `want` are made.  Temporaries and results go to `owned`.
 int simplify_on_device(const char* who, hipStream_t s, const float4* d_verts, const float4* d_nrm, const uchar4* d_rgba, long nv, const int* d_tri, long nt,
-                       float cell, const ScWant& want, const std::function<int(const ScMesh&)>& counted, std::vector<void*>& owned, ScMesh* out) {
+                       float cell, const ScWant& want, const std::function<int(const ScMesh&)>& counted, er::DevScope& owned, ScMesh* out) {
   // the first offenders
   unsigned long long* d_first = nullptr;
   int* d_diag = nullptr;
-  ER_W_OWNED(who, owned, &d_first, 2 * sizeof(unsigned long long));
-  ER_W_OWNED(who, owned, &d_diag, D_COUNT * sizeof(int));
+  if (owned.alloc(&d_first, 2, who)) return 1;
+  if (owned.alloc(&d_diag, D_COUNT, who)) return 1;
   ER_W(who, hipMemsetAsync(d_first, 0xFF, 2 * sizeof(unsigned long long), s));
   ER_W(who, hipMemsetAsync(d_diag, 0, D_COUNT * sizeof(int), s));
   hipLaunchKernelGGL(k_sc_check, dim3(sc_grid(std::max(nv, nt))), dim3(kScBlock), 0, s, d_verts, nv, cell, d_tri, nt, d_first);
@@ -405,14 +394,14 @@ int simplify_on_device(const char* who, hipStream_t s, const float4* d_verts, co
   unsigned *d_vslot = nullptr, *d_tslot = nullptr;
   unsigned long long *d_pos = nullptr, *d_nsum = nullptr, *d_csum = nullptr;
   long* d_blk = nullptr;                                       // [2 nbv] vertex counts, [2 nbt] triangle counts, then [nbv] and [nbt] offsets
-  ER_W_OWNED(who, owned, &d_vtable, vsize * sizeof(int));
-  ER_W_OWNED(who, owned, &d_ttable, tsize * sizeof(int));
-  ER_W_OWNED(who, owned, &d_vslot, (size_t)nv * sizeof(unsigned));
-  ER_W_OWNED(who, owned, &d_tslot, (size_t)nt * sizeof(unsigned));
-  ER_W_OWNED(who, owned, &d_lead, (size_t)nv * sizeof(int));
-  ER_W_OWNED(who, owned, &d_used, (size_t)nv * sizeof(int));
-  ER_W_OWNED(who, owned, &d_pos, (size_t)nv * 4 * sizeof(unsigned long long));
-  ER_W_OWNED(who, owned, &d_blk, (size_t)(3 * nbv + 3 * nbt) * sizeof(long));
+  if (owned.alloc(&d_vtable, vsize, who)) return 1;
+  if (owned.alloc(&d_ttable, tsize, who)) return 1;
+  if (owned.alloc(&d_vslot, (size_t)nv, who)) return 1;
+  if (owned.alloc(&d_tslot, (size_t)nt, who)) return 1;
+  if (owned.alloc(&d_lead, (size_t)nv, who)) return 1;
+  if (owned.alloc(&d_used, (size_t)nv, who)) return 1;
+  if (owned.alloc(&d_pos, (size_t)nv * 4, who)) return 1;
+  if (owned.alloc(&d_blk, (size_t)(3 * nbv + 3 * nbt), who)) return 1;
   long *d_bt = d_blk + 2 * nbv, *d_ov = d_bt + 2 * nbt, *d_ot = d_ov + nbv;
   ER_W(who, hipMemsetAsync(d_vtable, 0xFF, vsize * sizeof(int), s));
   ER_W(who, hipMemsetAsync(d_ttable, 0xFF, tsize * sizeof(int), s));
@@ -422,11 +411,11 @@ int simplify_on_device(const char* who, hipStream_t s, const float4* d_verts, co
   ER_W(who, hipMemsetAsync(d_pos, 0, (size_t)nv * 4 * sizeof(unsigned long long), s));
   const bool with_n = d_nrm && want.nrm, with_c = d_rgba && want.rgba;
   if (with_n) {
-    ER_W_OWNED(who, owned, &d_nsum, (size_t)nv * 4 * sizeof(unsigned long long));
+    if (owned.alloc(&d_nsum, (size_t)nv * 4, who)) return 1;
     ER_W(who, hipMemsetAsync(d_nsum, 0, (size_t)nv * 4 * sizeof(unsigned long long), s));
   }
   if (with_c) {
-    ER_W_OWNED(who, owned, &d_csum, (size_t)nv * 4 * sizeof(unsigned long long));
+    if (owned.alloc(&d_csum, (size_t)nv * 4, who)) return 1;
     ER_W(who, hipMemsetAsync(d_csum, 0, (size_t)nv * 4 * sizeof(unsigned long long), s));
   }
   hipLaunchKernelGGL(k_sc_insert, dim3((unsigned)nbv), dim3(kScBlock), 0, s, d_verts, nv, cell, d_vtable, vsize - 1, d_vslot, d_diag);
@@ -482,21 +471,21 @@ int simplify_on_device(const char* who, hipStream_t s, const float4* d_verts, co
 
   // the second passes
   ER_W(who, hipMemcpyAsync(d_ov, off.data(), off.size() * sizeof(long), hipMemcpyHostToDevice, s));
-  ER_W_OWNED(who, owned, &d_rank, (size_t)nv * sizeof(int));
+  if (owned.alloc(&d_rank, (size_t)nv, who)) return 1;
   if (nvk > 0) {
-    if (want.verts) ER_W_OWNED(who, owned, &d_verts_out, (size_t)nvk * sizeof(float4));
-    if (with_n) ER_W_OWNED(who, owned, &d_nrm_out, (size_t)nvk * sizeof(float4));
-    if (with_c) ER_W_OWNED(who, owned, &d_rgba_out, (size_t)nvk * sizeof(uchar4));
-    if (want.members) ER_W_OWNED(who, owned, &d_members, (size_t)nvk * sizeof(int));
+    if (want.verts && owned.alloc(&d_verts_out, (size_t)nvk, who)) return 1;
+    if (with_n && owned.alloc(&d_nrm_out, (size_t)nvk, who)) return 1;
+    if (with_c && owned.alloc(&d_rgba_out, (size_t)nvk, who)) return 1;
+    if (want.members && owned.alloc(&d_members, (size_t)nvk, who)) return 1;
   }
   if (vertices(1)) return 1;
   if (ntk > 0 && (want.tri || want.tri_index)) {
-    if (want.tri) ER_W_OWNED(who, owned, &d_tri_out, (size_t)ntk * 3 * sizeof(int));
-    if (want.tri_index) ER_W_OWNED(who, owned, &d_tri_index, (size_t)ntk * sizeof(int));
+    if (want.tri && owned.alloc(&d_tri_out, (size_t)ntk * 3, who)) return 1;
+    if (want.tri_index && owned.alloc(&d_tri_index, (size_t)ntk, who)) return 1;
     if (triangles(1)) return 1;
   }
   if (want.cluster) {
-    ER_W_OWNED(who, owned, &out->d_cluster, (size_t)nv * sizeof(int));
+    if (owned.alloc(&out->d_cluster, (size_t)nv, who)) return 1;
     hipLaunchKernelGGL(k_sc_cluster, dim3((unsigned)nbv), dim3(kScBlock), 0, s, d_lead, d_rank, nv, out->d_cluster);
     ER_W(who, hipGetLastError());
   }
@@ -522,16 +511,6 @@ int sc_copy_back(const char* who, hipStream_t s, const ScMesh& r, long nv_in, fl
   ER_W(who, hipStreamSynchronize(s));
   return 0;
 }
-
-struct Owned {
-  std::vector<void*> p;
-  Owned() = default;
-  Owned(const Owned&) = delete;
-  Owned& operator=(const Owned&) = delete;
-  ~Owned() {
-    for (void* q : p) (void)hipFree(q);
-  }
-};
 
 }  // namespace
 
@@ -565,20 +544,20 @@ int er_mesh_simplify(const float* verts_host, const float* normals_host, const u
   }
   ER_HIP_TRY(hipSetDevice(device));
   hipStream_t s = nullptr;                                     // (the null stream: the call is synchronous)
-  Owned own;
+  er::DevScope own;
   float4 *d_verts = nullptr, *d_nrm = nullptr;
   uchar4* d_rgba = nullptr;
   int* d_tri = nullptr;
-  ER_W_OWNED(who, own.p, &d_verts, (size_t)nv * sizeof(float4));
-  ER_W_OWNED(who, own.p, &d_tri, (size_t)nt * 3 * sizeof(int));
+  if (own.alloc(&d_verts, (size_t)nv, who)) return 1;
+  if (own.alloc(&d_tri, (size_t)nt * 3, who)) return 1;
   ER_W(who, hipMemcpyAsync(d_verts, verts_host, (size_t)nv * sizeof(float4), hipMemcpyHostToDevice, s));
   ER_W(who, hipMemcpyAsync(d_tri, tri_host, (size_t)nt * 3 * sizeof(int), hipMemcpyHostToDevice, s));
   if (normals_out) {
-    ER_W_OWNED(who, own.p, &d_nrm, (size_t)nv * sizeof(float4));
+    if (own.alloc(&d_nrm, (size_t)nv, who)) return 1;
     ER_W(who, hipMemcpyAsync(d_nrm, normals_host, (size_t)nv * sizeof(float4), hipMemcpyHostToDevice, s));
   }
   if (colors_out) {
-    ER_W_OWNED(who, own.p, &d_rgba, (size_t)nv * sizeof(uchar4));
+    if (own.alloc(&d_rgba, (size_t)nv, who)) return 1;
     ER_W(who, hipMemcpyAsync(d_rgba, colors_host, (size_t)nv * sizeof(uchar4), hipMemcpyHostToDevice, s));
   }
   const ScWant want{verts_out != nullptr, normals_out != nullptr, colors_out != nullptr, members_out != nullptr, tri_out != nullptr, tri_index_out != nullptr,
@@ -595,7 +574,7 @@ int er_mesh_simplify(const float* verts_host, const float* normals_host, const u
     return 0;
   };
   ScMesh r;
-  if (simplify_on_device(who, s, d_verts, d_nrm, d_rgba, nv, d_tri, nt, cell, want, counted, own.p, &r)) return 1;
+  if (simplify_on_device(who, s, d_verts, d_nrm, d_rgba, nv, d_tri, nt, cell, want, counted, own, &r)) return 1;
   return sc_copy_back(who, s, r, nv, verts_out, normals_out, colors_out, members_out, tri_out, tri_index_out, cluster_out);
 }
 
@@ -649,7 +628,7 @@ int er_tsdf_extract_mesh_simplified(er_tsdf_t h, float cell, long min_triangles,
   }
   uchar4* d_rgba = nullptr;
   if (colors_host) {                                           // the colours of the unsimplified vertices, sampled where they lie
-    ER_W_OWNED(who, m.owned, &d_rgba, (size_t)nv * sizeof(uchar4));
+    if (m.owned.alloc(&d_rgba, (size_t)nv, who)) return 1;
     if (color_sample_on_device(h, who, d_verts, nv, d_rgba)) return 1;
   }
   const ScWant want{verts_host != nullptr, normals_host != nullptr, colors_host != nullptr, members_host != nullptr, tri_host != nullptr, false, false};
@@ -668,8 +647,5 @@ int er_tsdf_extract_mesh_simplified(er_tsdf_t h, float cell, long min_triangles,
   if (simplify_on_device(who, s, d_verts, d_nrm, d_rgba, nv, d_tri, nt, cell, want, counted, m.owned, &r)) return 1;
   return sc_copy_back(who, s, r, nv, verts_host, normals_host, colors_host, members_host, tri_host, nullptr, nullptr);
 }
-
-#undef ER_W_OWNED
-#undef ER_W
 
 }  // extern "C"

@@ -16,6 +16,7 @@
 // One communicator per GPU: er_comm_create (one process per GPU; the 128-byte id travels out of band -- a file, a socket,
 // torch.distributed) or er_comm_create_local (one process driving several GPUs from one host thread each).
 #include "er_common.h"
+#include "er_mem.h"
 
 #include "er_merge_protocol.h"
 
@@ -140,12 +141,9 @@ struct er_comm_s {
   ncclComm_t comm = nullptr;
   int rank = 0, world = 1, device = 0;
   er::OwnerMergeStats last_owner;           // what the last merge moved
-  float* vbuf[2] = {nullptr, nullptr};      // incoming records of step 1 / step 3 (grow-only)
-  size_t vbuf_floats[2] = {0, 0};
-  float* xbuf = nullptr;       // outgoing records (grow-only)
-  size_t xbuf_floats = 0;
-  int* ikeys = nullptr;        // device scratch: [1 + max_keys * (world + 1)] ints (grow-only)
-  size_t ikeys_cap = 0;
+  er::Buffer<float> vbuf[2];                // incoming records of step 1 / step 3
+  er::Buffer<float> xbuf;                   // outgoing records
+  er::Buffer<int> ikeys;                    // device scratch: [1 + max_keys * (world + 1)] ints
 };
 
 
@@ -160,14 +158,8 @@ struct RcclTransport : er::MergeTransport {
   int rank() const override { return c->rank; }
   int world() const override { return c->world; }
   int scratch(size_t ints) {
-    if (c->ikeys_cap >= ints) return 0;
-    if (c->ikeys) (void)hipFree(c->ikeys);
-    c->ikeys = nullptr;
-    c->ikeys_cap = 0;
-    const size_t cap = std::max<size_t>(ints, 64);
-    ER_HIP_TRY(hipMalloc((void**)&c->ikeys, cap * sizeof(int)));
-    c->ikeys_cap = cap;
-    return 0;
+    if (c->ikeys.capacity() >= ints) return 0;
+    return c->ikeys.reserve(std::max<size_t>(ints, 64), "the RCCL key scratch");
   }
   int allreduce_max(int* v, int n) override {
     if (scratch(2 * (size_t)n)) return 1;
@@ -287,15 +279,9 @@ struct DeviceVolume : er::MergeVolume {
     return 0;
   }
   // ---- band records (er_tsdf_band.hip) ----
-  static int grow_floats(float** b, size_t* have, size_t floats) {
-    if (*have >= floats) return 0;
-    if (*b) (void)hipFree(*b);
-    *b = nullptr;
-    *have = 0;
-    const size_t cap = floats + floats / 8 + 1024;
-    ER_HIP_TRY(hipMalloc((void**)b, cap * sizeof(float)));
-    *have = cap;
-    return 0;
+  static int grow_floats(er::Buffer<float>& b, size_t floats) {
+    if (b.capacity() >= floats) return 0;
+    return b.reserve(floats + floats / 8 + 1024, "the band record buffers");
   }
   // (the protocol's "count" of a unit is its record size in words here: the owner is the toucher with the LARGEST record, the plan needs sizes only)
   int band_counts(const int* uk, int nu, int* counts) override { return er_tsdf_band_sizes(h, uk, nu, counts); }
@@ -303,12 +289,12 @@ struct DeviceVolume : er::MergeVolume {
   int export_band(const int* uk, const int* counts, int nu, float** block) override {
     size_t total = 0;
     for (int i = 0; i < nu; i++) total += band_record_floats(counts[i]);
-    if (grow_floats(&c->xbuf, &c->xbuf_floats, total)) return 1;
+    if (grow_floats(c->xbuf, total)) return 1;
     *block = c->xbuf;
     return er_tsdf_export_band(h, uk, counts, nu, c->xbuf);
   }
   int band_receive_buffer(size_t floats, int which, float** block) override {
-    if (grow_floats(&c->vbuf[which & 1], &c->vbuf_floats[which & 1], floats)) return 1;
+    if (grow_floats(c->vbuf[which & 1], floats)) return 1;
     *block = c->vbuf[which & 1];
     return 0;
   }
@@ -335,9 +321,7 @@ struct DeviceVolume : er::MergeVolume {
 // padded keys of a full 512-unit region from 100+ ranks, so er_tsdf_allreduce itself never allocates before its first collective.
 static int comm_scratch(er_comm_t c) {
   ER_HIP_TRY(hipSetDevice(c->device));
-  ER_HIP_TRY(hipMalloc((void**)&c->ikeys, (size_t)65536 * sizeof(int)));
-  c->ikeys_cap = 65536;
-  return 0;
+  return c->ikeys.reserve(65536, "er_comm_create");
 }
 
 static_assert(ER_COMM_ID_BYTES == sizeof(ncclUniqueId), "ER_COMM_ID_BYTES must equal sizeof(ncclUniqueId)");
@@ -428,10 +412,10 @@ int er_comm_create_loopback(int n, int device, er_comm_t* out) {
 int er_comm_destroy(er_comm_t c) {
   if (!c) return 0;
   (void)hipSetDevice(c->device);
-  if (c->xbuf) (void)hipFree(c->xbuf);
-  if (c->vbuf[0]) (void)hipFree(c->vbuf[0]);
-  if (c->vbuf[1]) (void)hipFree(c->vbuf[1]);
-  if (c->ikeys) (void)hipFree(c->ikeys);
+  c->xbuf.reset();
+  c->vbuf[0].reset();
+  c->vbuf[1].reset();
+  c->ikeys.reset();
   if (c->comm) {
     Rccl* R = rccl();
     if (R) (void)R->CommDestroy(c->comm);

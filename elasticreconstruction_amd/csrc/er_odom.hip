@@ -291,12 +291,14 @@ struct er_odom_s {
   er_odom_params P{};
   Layout lo{};
   int total_iters = 0;
+  er::DevScope fixed;                      // d_tables
   float* d_tables = nullptr;
   int n_depth_w = 0;
   // the window: slots of the slab and the frame each holds (valid within one call: frames are named by their index into that call's depth array)
   int window = 0;
   std::vector<int> slot_frame;
-  // per-run workspace, sized for cap_pairs pairs
+  // the slab (lo.base) and the per-run workspace, sized for cap_pairs pairs: all in `win`, replaced together when the window grows
+  er::DevScope win;
   int cap_pairs = 0;
   Todo* d_todo = nullptr;
   PairDesc* d_pairs = nullptr;
@@ -309,27 +311,17 @@ namespace {
 
 int nblk_of(const er_odom_s* h, int level) { return (h->lo.cols[level] * h->lo.rows[level] + kPix * kBlock - 1) / (kPix * kBlock); }
 
-void odom_free_window(er_odom_s* h) {
-  void* ptrs[] = {h->lo.base, h->d_todo, h->d_pairs, h->d_state, h->d_partial, h->d_trace, h->d_sums, h->d_pcount};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  h->lo.base = nullptr;
-  h->d_todo = nullptr; h->d_pairs = nullptr; h->d_state = nullptr; h->d_partial = h->d_trace = h->d_sums = nullptr; h->d_pcount = nullptr;
-  h->window = h->cap_pairs = 0;
-}
-
 // The slab of `window` slots and a workspace for up to `window` pairs per run (grow-only).
 int odom_ensure_window(er_odom_s* h, int window) {
   if (window <= h->window) return 0;
-  odom_free_window(h);
-  ER_HIP_TRY(hipMalloc((void**)&h->lo.base, h->lo.stride * (size_t)window));
-  ER_HIP_TRY(hipMalloc((void**)&h->d_todo, sizeof(Todo) * (size_t)window));
-  ER_HIP_TRY(hipMalloc((void**)&h->d_pairs, sizeof(PairDesc) * (size_t)window));
-  ER_HIP_TRY(hipMalloc((void**)&h->d_state, sizeof(OdomState) * (size_t)window));
-  ER_HIP_TRY(hipMalloc((void**)&h->d_partial, sizeof(double) * kPartial * (size_t)nblk_of(h, 0) * window));
-  ER_HIP_TRY(hipMalloc((void**)&h->d_pcount, sizeof(int) * (size_t)nblk_of(h, 0) * window));
-  ER_HIP_TRY(hipMalloc((void**)&h->d_trace, sizeof(double) * ER_ODOM_TRACE * (size_t)std::max(h->total_iters, 1) * window));
-  ER_HIP_TRY(hipMalloc((void**)&h->d_sums, sizeof(double) * er_od::kSums * (size_t)window));
+  const char* who = "the depth odometry window";
+  const size_t w = (size_t)window, nblk = (size_t)nblk_of(h, 0);
+  h->win.free_all();
+  h->window = h->cap_pairs = 0;                    // (a failure below leaves no window: the next call starts over)
+  if (h->win.alloc(&h->lo.base, h->lo.stride * w, who) || h->win.alloc(&h->d_todo, w, who) || h->win.alloc(&h->d_pairs, w, who) ||
+      h->win.alloc(&h->d_state, w, who) || h->win.alloc(&h->d_partial, kPartial * nblk * w, who) || h->win.alloc(&h->d_pcount, nblk * w, who) ||
+      h->win.alloc(&h->d_trace, ER_ODOM_TRACE * (size_t)h->total_iters * w, who) || h->win.alloc(&h->d_sums, er_od::kSums * w, who))
+    return 1;
   h->window = h->cap_pairs = window;
   h->slot_frame.assign(window, -1);
   return 0;
@@ -557,10 +549,12 @@ int er_odom_create(int cols, int rows, const float* cam4, const er_odom_params* 
   L.stride = off;
   float tab[er_od::kSpaceW + er_od::kDepthWMax];
   h->n_depth_w = er_od::build_tables(tab, tab + er_od::kSpaceW);
-  hipError_t e = hipMalloc((void**)&h->d_tables, sizeof tab);
-  if (e == hipSuccess) e = hipMemcpy(h->d_tables, tab, sizeof tab, hipMemcpyHostToDevice);
+  if (h->fixed.alloc(&h->d_tables, sizeof tab / sizeof tab[0], "er_odom_create")) {
+    delete h;
+    return 1;
+  }
+  const hipError_t e = hipMemcpy(h->d_tables, tab, sizeof tab, hipMemcpyHostToDevice);
   if (e != hipSuccess) {
-    if (h->d_tables) (void)hipFree(h->d_tables);
     delete h;
     return er::fail("er_odom_create: %s", hipGetErrorString(e));
   }
@@ -571,8 +565,8 @@ int er_odom_create(int cols, int rows, const float* cam4, const er_odom_params* 
 int er_odom_destroy(er_odom_t h) {
   if (!h) return 0;
   (void)hipSetDevice(h->device);
-  odom_free_window(h);
-  if (h->d_tables) (void)hipFree(h->d_tables);
+  h->win.free_all();
+  h->fixed.free_all();
   delete h;
   return 0;
 }

@@ -394,7 +394,7 @@ __global__ __launch_bounds__(256) void k_pgo_commit(const PgoState* st, int n_po
 struct er_pgo_s {
   int device = 0, n_poses = 0, n_loops = 0, n_edges = 0, n = 0, np = 0, nb = 0, n_lists = 0;
   hipStream_t stream = nullptr;
-  std::vector<void*> allocs;
+  er::DevScope mem;                       // every device array below
   double *Z = nullptr, *Om = nullptr, *scale = nullptr, *poses = nullptr, *poses_c = nullptr, *sw = nullptr, *sw_c = nullptr, *lk = nullptr;
   double *rec = nullptr, *H = nullptr, *M = nullptr, *b = nullptr, *y = nullptr, *cost = nullptr, *chi2 = nullptr, *ds = nullptr, *den = nullptr;
   double* consts = nullptr;                // [0] = 0 (linearisation for lambda_0), [1] = the hooks' lambda
@@ -408,14 +408,6 @@ struct er_pgo_s {
 
 namespace {
 
-template <class T>
-int pgo_alloc(er_pgo_s* h, T** p, size_t count) {
-  void* v = nullptr;
-  ER_HIP_TRY(hipMalloc(&v, std::max<size_t>(count, 1) * sizeof(T)));
-  h->allocs.push_back(v);
-  *p = (T*)v;
-  return 0;
-}
 
 EdgeArgs edge_args(const er_pgo_s* h) { return EdgeArgs{h->n_edges, h->n_poses - 1, h->Z, h->Om, h->scale, h->ids}; }
 int blocks64(int n) { return std::max(1, (n + 63) / 64); }
@@ -584,14 +576,14 @@ int er_pgo_create(int n_poses, int n_loops, const double* odo_T, const double* o
 
   int rc = 0;
   const size_t mat = (size_t)h->np * h->np;
-  rc = rc || pgo_alloc(h, &h->Z, Z.size()) || pgo_alloc(h, &h->Om, Om.size()) || pgo_alloc(h, &h->scale, (size_t)E) || pgo_alloc(h, &h->ids, ids.size());
-  rc = rc || pgo_alloc(h, &h->poses, (size_t)n_poses * 16) || pgo_alloc(h, &h->poses_c, (size_t)n_poses * 16);
-  rc = rc || pgo_alloc(h, &h->sw, (size_t)n_loops) || pgo_alloc(h, &h->sw_c, (size_t)n_loops) || pgo_alloc(h, &h->lk, (size_t)n_loops);
-  rc = rc || pgo_alloc(h, &h->ds, (size_t)n_loops) || pgo_alloc(h, &h->den, (size_t)n_loops);
-  rc = rc || pgo_alloc(h, &h->rec, (size_t)E * er_pgo::kEdgeRec) || pgo_alloc(h, &h->cost, (size_t)E) || pgo_alloc(h, &h->chi2, (size_t)E);
-  rc = rc || pgo_alloc(h, &h->H, mat) || pgo_alloc(h, &h->M, mat) || pgo_alloc(h, &h->b, (size_t)h->np) || pgo_alloc(h, &h->y, (size_t)h->np);
-  rc = rc || pgo_alloc(h, &h->consts, 2) || pgo_alloc(h, &h->st, 1);
-  rc = rc || pgo_alloc(h, &h->ptr, ptr.size()) || pgo_alloc(h, &h->ent, ent.size()) || pgo_alloc(h, &h->blk, blk.size());
+  rc = rc || h->mem.alloc(&h->Z, Z.size(), who) || h->mem.alloc(&h->Om, Om.size(), who) || h->mem.alloc(&h->scale, (size_t)E, who) || h->mem.alloc(&h->ids, ids.size(), who);
+  rc = rc || h->mem.alloc(&h->poses, (size_t)n_poses * 16, who) || h->mem.alloc(&h->poses_c, (size_t)n_poses * 16, who);
+  rc = rc || h->mem.alloc(&h->sw, (size_t)n_loops, who) || h->mem.alloc(&h->sw_c, (size_t)n_loops, who) || h->mem.alloc(&h->lk, (size_t)n_loops, who);
+  rc = rc || h->mem.alloc(&h->ds, (size_t)n_loops, who) || h->mem.alloc(&h->den, (size_t)n_loops, who);
+  rc = rc || h->mem.alloc(&h->rec, (size_t)E * er_pgo::kEdgeRec, who) || h->mem.alloc(&h->cost, (size_t)E, who) || h->mem.alloc(&h->chi2, (size_t)E, who);
+  rc = rc || h->mem.alloc(&h->H, mat, who) || h->mem.alloc(&h->M, mat, who) || h->mem.alloc(&h->b, (size_t)h->np, who) || h->mem.alloc(&h->y, (size_t)h->np, who);
+  rc = rc || h->mem.alloc(&h->consts, 2, who) || h->mem.alloc(&h->st, 1, who);
+  rc = rc || h->mem.alloc(&h->ptr, ptr.size(), who) || h->mem.alloc(&h->ent, ent.size(), who) || h->mem.alloc(&h->blk, blk.size(), who);
   hipError_t e = hipSuccess;
   if (!rc) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
   auto up = [&](void* d, const void* s, size_t bytes) { if (e == hipSuccess && bytes) e = hipMemcpy(d, s, bytes, hipMemcpyHostToDevice); };
@@ -613,7 +605,7 @@ int er_pgo_create(int n_poses, int n_loops, const double* odo_T, const double* o
     if (e == hipSuccess) e = hipMemset(h->b, 0, (size_t)h->np * sizeof(double));
     if (e == hipSuccess) e = hipMemset(h->consts, 0, 2 * sizeof(double));
     if (e == hipSuccess) e = hipMemset(h->st, 0, sizeof(PgoState));
-    if (e == hipSuccess) e = hipMemset(h->lk, 0, std::max<size_t>(n_loops, 1) * sizeof(double));
+    if (e == hipSuccess && n_loops > 0) e = hipMemset(h->lk, 0, (size_t)n_loops * sizeof(double));
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);                // the uploads and memsets above, on the default stream
   }
   if (rc || e != hipSuccess) {
@@ -631,7 +623,7 @@ int er_pgo_destroy(er_pgo_t h) {
   if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
   for (hipEvent_t e : h->ev)
     if (e) (void)hipEventDestroy(e);
-  for (void* p : h->allocs) (void)hipFree(p);
+  h->mem.free_all();
   delete h;
   return 0;
 }

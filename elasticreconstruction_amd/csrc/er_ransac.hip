@@ -611,9 +611,9 @@ int ransac_run(int n_pairs, const er_cloud_t* src, const er_cloud_t* tgt, const 
   StreamLease L;
   if (L.acquire(src[0]->device)) return 1;
   hipStream_t S = L.stream;
-  DevBufs B;
+  DevScope B;
   char* ws;
-  if (B.alloc(&ws, total) != hipSuccess) {
+  if (B.alloc(&ws, total, "the RANSAC search")) {
     (void)hipGetLastError();
     return er::fail("the RANSAC search: %zu MB of workspace for %d pairs in flight could not be allocated", total >> 20, mc);
   }
@@ -741,9 +741,11 @@ int er_features_create(const float* feat_host, int n, int dim, int device, er_fe
   ER_HIP_TRY(hipSetDevice(device));
   er_features_s* f = new er_features_s();
   f->device = device; f->n = n; f->dim = dim; f->dp = dp;
-  if (hipMalloc((void**)&f->d, pad.size() * sizeof(float)) != hipSuccess ||
-      hipMemcpy(f->d, pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-    if (f->d) (void)hipFree(f->d);
+  if (f->d.reserve(pad.size(), "er_features_create")) {
+    delete f;
+    return 1;
+  }
+  if (hipMemcpy(f->d, pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
     delete f;
     return er::fail("er_features_create: %s", hipGetErrorString(hipGetLastError()));
   }
@@ -754,7 +756,6 @@ int er_features_create(const float* feat_host, int n, int dim, int device, er_fe
 int er_features_destroy(er_features_t f) {
   if (!f) return 0;
   (void)hipSetDevice(f->device);
-  if (f->d) (void)hipFree(f->d);
   delete f;
   return 0;
 }
@@ -766,14 +767,14 @@ int er_feature_knn(er_features_t src, er_features_t tgt, int k, int* idx_host, f
   if (check_features(src, tgt, k, "er_feature_knn")) return 1;
   StreamLease L;
   if (L.acquire(src->device)) return 1;
-  DevBufs B;
+  DevScope B;
   int *d_idx, *pi;
   float *d_dist, *pd;
   const size_t m = (size_t)src->n * k, part = knn_plan(src->n, tgt->n, k, nullptr, nullptr);
-  ER_HIP_TRY(B.alloc(&d_idx, m * sizeof(int)));
-  ER_HIP_TRY(B.alloc(&d_dist, m * sizeof(float)));
-  ER_HIP_TRY(B.alloc(&pd, part * sizeof(float)));
-  ER_HIP_TRY(B.alloc(&pi, part * sizeof(int)));
+  if (B.alloc(&d_idx, m, "er_feature_knn")) return 1;
+  if (B.alloc(&d_dist, m, "er_feature_knn")) return 1;
+  if (B.alloc(&pd, part, "er_feature_knn")) return 1;
+  if (B.alloc(&pi, part, "er_feature_knn")) return 1;
   if (feature_knn_device(src, tgt, k, L.stream, d_idx, d_dist, pd, pi)) return 1;
   if (idx_host) ER_HIP_TRY(hipMemcpyAsync(idx_host, d_idx, m * sizeof(int), hipMemcpyDeviceToHost, L.stream));
   if (sqdist_host) ER_HIP_TRY(hipMemcpyAsync(sqdist_host, d_dist, m * sizeof(float), hipMemcpyDeviceToHost, L.stream));
@@ -797,13 +798,13 @@ int er_ransac_hypotheses(er_cloud_t src, er_cloud_t tgt, int n_hyp, int nr_sampl
   StreamLease L;
   if (L.acquire(src->device)) return 1;
   hipStream_t S = L.stream;
-  DevBufs B;
+  DevScope B;
   int *d_s, *d_c, *d_st;
   float* d_M;
-  ER_HIP_TRY(B.alloc(&d_s, m * sizeof(int)));
-  ER_HIP_TRY(B.alloc(&d_c, m * sizeof(int)));
-  ER_HIP_TRY(B.alloc(&d_st, (size_t)n_hyp * sizeof(int)));
-  ER_HIP_TRY(B.alloc(&d_M, (size_t)n_hyp * 16 * sizeof(float)));
+  if (B.alloc(&d_s, m, "er_ransac_hypotheses")) return 1;
+  if (B.alloc(&d_c, m, "er_ransac_hypotheses")) return 1;
+  if (B.alloc(&d_st, (size_t)n_hyp, "er_ransac_hypotheses")) return 1;
+  if (B.alloc(&d_M, (size_t)n_hyp * 16, "er_ransac_hypotheses")) return 1;
   ER_HIP_TRY(hipMemcpyAsync(d_s, sample_idx, m * sizeof(int), hipMemcpyHostToDevice, S));
   ER_HIP_TRY(hipMemcpyAsync(d_c, corr_idx, m * sizeof(int), hipMemcpyHostToDevice, S));
   const float simsq = similarity * similarity;

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "er_common.h"
+#include "er_mem.h"
 #include "er_tsdf_math.h"
 
 #include "../../include/er_hip.h"
@@ -134,8 +135,20 @@ extern template __global__ void k_integrate<true>(float2* __restrict__, const Pl
 extern template __global__ void k_integrate<false>(float2* __restrict__, const PlanRec* __restrict__, Plan* __restrict__, const FrameXform* __restrict__, const float* __restrict__, const float* __restrict__, const float* __restrict__, const float* __restrict__, int, int, Camera, int, int);
 }  // namespace er_tsdf_k
 
+// The device memory of a handle.  A fresh er_tsdf_mem assigned over it frees all of it, at that point (er_tsdf_destroy: before own_stream goes).
+struct er_tsdf_mem {
+  er::DevScope fixed;                                   // what er_tsdf_create allocates: the arrays behind the handle's plain pointers
+  // colour (er_tsdf_color.hip): per voxel two 64-bit words (r | g << 32), (b | n << 32) = uint32 r_sum, g_sum, b_sum, n; indexed like the pool, by the
+  // unit's slot.  Empty until er_tsdf_color_enable: a volume that never enables colour allocates nothing.
+  er::Buffer<unsigned long long> color;
+  er::Buffer<int> key_scratch, slot_scratch;            // grow together (ensure_key_scratch)
+  er::Buffer<float> ctr_dev[2];                         // the caller's lattices by call parity (upload_ctr)
+  er::Buffer<char> band_scratch;                        // of the band kernels (owner merge)
+  er::Buffer<char> color_scratch;                       // staging of the colour calls' inputs (frames, points), their own so that no pre-pass buffer is shared
+};
+
 // (the handle is a type of the C ABI, so it lives in the global namespace)
-struct er_tsdf_s {
+struct er_tsdf_s : er_tsdf_mem {
   int device = 0, cols = 0, rows = 0, pixels = 0, max_units = 0;
   er::Camera cam{};
   er::CameraInv cami{};
@@ -166,14 +179,12 @@ struct er_tsdf_s {
   er::FrameXform* frames[er_tsdf_k::kDepth] = {};              // = &dstage[q]->fx
   void* dstage[er_tsdf_k::kDepth] = {};                        // device twin of the pinned per-batch constants (struct Staging)
   hipEvent_t pre_done[er_tsdf_k::kDepth] = {}, int_done[er_tsdf_k::kDepth] = {};
-  void* pinned[er_tsdf_k::kDepth] = {};                              // host staging of the per-batch constants
+  er::PinnedBuffer<char> pinned[er_tsdf_k::kDepth];                  // host staging of the per-batch constants (struct Staging)
   int ht_cap = 0, ht_shift = 0;
   float *lambda = nullptr, *ctr = nullptr;
   // The caller's lattices, double-buffered by call parity on the host (page-locked staging) AND on the device, so that the
   // upload of call c (copy stream) never waits for the pre-passes of call c-1 that still read the other buffer.
-  float* ctr_pinned[2] = {nullptr, nullptr};
-  float* ctr_dev[2] = {nullptr, nullptr};
-  size_t ctr_pinned_cap[2] = {0, 0}, ctr_dev_cap[2] = {0, 0};
+  er::PinnedBuffer<float> ctr_pinned[2];                    // (the device side is er_tsdf_mem::ctr_dev)
   hipEvent_t ctr_ev[2] = {nullptr, nullptr};                // upload of the buffer done
   hipEvent_t ctr_rd[2][er_tsdf_k::kAux] = {};                          // last pre-pass reader of the buffer, per pre-pass stream
   bool ctr_rd_set[2] = {false, false};
@@ -182,10 +193,9 @@ struct er_tsdf_s {
   uint32_t *zbuf[er_tsdf_k::kAux] = {}, *lastzero[er_tsdf_k::kAux] = {}, *zfix[er_tsdf_k::kAux] = {};  // Reproject's z-buffer and replay state, one per pre-pass stream
   uint32_t zepoch[er_tsdf_k::kAux + 1] = {};              // use counters of zbuf[0], zbuf[1] and of the colour calls' z-buffer (kZColor); next_ztag advances them
   double *T12 = nullptr, *seg12 = nullptr, *madj12 = nullptr, *dsum = nullptr;
-  int *grid_index = nullptr, *key_scratch = nullptr, *slot_scratch = nullptr;
+  int* grid_index = nullptr;
   er_tsdf_k::PlanRec* plan_rec[er_tsdf_k::kDepth] = {};
   er_tsdf_k::Plan* plan[er_tsdf_k::kDepth] = {};
-  size_t key_scratch_cap = 0;
   // profiling
   int prof_stride = 0;                              // 0 = off, n = time every n-th k_integrate launch
   long prof_tick = 0;
@@ -205,16 +215,8 @@ struct er_tsdf_s {
   std::vector<TimelineRow> tl_rows;
   std::vector<hipEvent_t> tl_free;                  // timing events of rows already read, for the next rows
   // round 6 (owner merge): units this GPU handed to their owner -- zeroed, still in the table, hidden from every key / count / extraction query until
-  // the next frame is integrated or the unit is imported again -- and the grow-only device scratch of the band kernels
+  // the next frame is integrated or the unit is imported again
   std::vector<int> dropped;                         // sorted
-  void* band_scratch = nullptr;
-  size_t band_scratch_cap = 0;
-  // colour (er_tsdf_color.hip): per voxel two 64-bit words (r | g << 32), (b | n << 32) = uint32 r_sum, g_sum, b_sum, n; indexed like the pool, by the
-  // unit's slot.  nullptr until er_tsdf_color_enable: a volume that never enables colour allocates nothing.  color_scratch: the grow-only device
-  // staging of the colour calls' inputs (frames, points), their own so that no pre-pass buffer is shared.
-  unsigned long long* color = nullptr;
-  void* color_scratch = nullptr;
-  size_t color_scratch_cap = 0;
 };
 
 // ---- er_tsdf.hip: host functions the other files call (hidden: not part of the library's interface) ----
@@ -239,13 +241,7 @@ struct DeviceMesh {
   long nv = 0, ntri = 0;
   float4 *d_verts = nullptr, *d_nrm = nullptr;
   int* d_tri = nullptr;
-  std::vector<void*> owned;
-  DeviceMesh() = default;
-  DeviceMesh(const DeviceMesh&) = delete;
-  DeviceMesh& operator=(const DeviceMesh&) = delete;
-  ~DeviceMesh() {
-    for (void* p : owned) (void)hipFree(p);
-  }
+  DevScope owned;
 };
 // Lists the units (*n_vertices = *n_triangles = 0 from then on), counts the mesh of the resident volume, sets the two counts, calls
 // counted(nv, ntri) -- which refuses what the caller has to refuse, reporting it (non-zero ends the call with 1) -- and then enqueues on

@@ -265,14 +265,12 @@ int join_voxel(er_tsdf_t h) {
 }
 
 int ensure_key_scratch(er_tsdf_t h, size_t n) {
-  if (n <= h->key_scratch_cap) return 0;
-  if (h->key_scratch) (void)hipFree(h->key_scratch);
-  if (h->slot_scratch) (void)hipFree(h->slot_scratch);
-  h->key_scratch = h->slot_scratch = nullptr;
-  size_t cap = std::max<size_t>(n, 1024);
-  ER_HIP_TRY(hipMalloc(&h->key_scratch, cap * sizeof(int)));
-  ER_HIP_TRY(hipMalloc(&h->slot_scratch, cap * sizeof(int)));
-  h->key_scratch_cap = cap;
+  if (n <= h->key_scratch.capacity()) return 0;
+  const size_t cap = std::max<size_t>(n, 1024);
+  if (h->key_scratch.reserve(cap, "the TSDF key scratch") || h->slot_scratch.reserve(cap, "the TSDF key scratch")) {
+    h->key_scratch.reset();
+    return 1;
+  }
   return 0;
 }
 
@@ -467,7 +465,7 @@ int run_batch(er_tsdf_t h, int n, const uint16_t* depth_dev, const double* T, co
   // pass and runs up to three batches ahead (host-frame copies and pre-passes queue up behind the events).
   if (h->used[p]) ER_HIP_TRY(hipEventSynchronize(h->consts_done[p]));
   if (tl) tl->host_ms[1] = host_now_ms() - h->tl_host0;
-  Staging* st = static_cast<Staging*>(h->pinned[p]);
+  Staging* st = reinterpret_cast<Staging*>(h->pinned[p].get());
   for (int f = 0; f < n; f++) {
     const double* Tf = T + (size_t)f * 16;
     double Tinv[16];
@@ -612,15 +610,6 @@ int er_tsdf_create(int cols, int rows, const float cam6[6], int max_units, int d
   h->ht_cap = cap;
   h->ht_shift = 32 - lg;
   const size_t px = (size_t)h->pixels, B = ER_MAX_BATCH;
-#define ER_ALLOC(ptr, bytes)                                                                         \
-  do {                                                                                               \
-    hipError_t e_ = hipMalloc((void**)&(ptr), (bytes));                                              \
-    if (e_ != hipSuccess) {                                                                          \
-      er::fail("er_tsdf_create: hipMalloc(%zu bytes) for " #ptr " failed: %s", (size_t)(bytes), hipGetErrorString(e_)); \
-      er_tsdf_destroy(h);                                                                            \
-      return 1;                                                                                      \
-    }                                                                                                \
-  } while (0)
   if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess ||
       aux_create(&h->aux_stream[0]) != hipSuccess || (kAux > 1 && aux_create(&h->aux_stream[kAux - 1]) != hipSuccess) ||
       false) {
@@ -638,39 +627,47 @@ int er_tsdf_create(int cols, int rows, const float cam6[6], int max_units, int d
         hipEventCreateWithFlags(&h->int_done[q], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->copy_done[q], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->consts_done[q], hipEventDisableTiming) != hipSuccess ||
-        hipHostMalloc(&h->pinned[q], sizeof(Staging), hipHostMallocDefault) != hipSuccess) {
+        h->pinned[q].reserve(sizeof(Staging), "er_tsdf_create")) {
       er_tsdf_destroy(h);
       return er::fail("er_tsdf_create: event / pinned staging allocation failed");
     }
   }
-  ER_ALLOC(h->pool, (size_t)max_units * er::kUnitVox * sizeof(float2));
-  ER_ALLOC(h->ht_key, (size_t)cap * sizeof(int));
-  ER_ALLOC(h->ht_slot, (size_t)cap * sizeof(int));
-  for (int q = 0; q < kDepth; q++) ER_ALLOC(h->ht_mask[q], (size_t)cap * sizeof(unsigned long long));
-  ER_ALLOC(h->unit_key, (size_t)max_units * sizeof(int));
-  ER_ALLOC(h->counters, C_COUNT * sizeof(int));
-  ER_ALLOC(h->stats, 4 * sizeof(unsigned long long));
-  for (int q = 0; q < kDepth; q++) ER_ALLOC(h->batch[q], (size_t)cap * sizeof(int));
-  ER_ALLOC(h->lambda, px * sizeof(float));
-  for (int q = 0; q < kDepth; q++) ER_ALLOC(h->scaled[q], B * (px + kScaledPad) * sizeof(float));
-  for (int q = 0; q < kDepth; q++) ER_ALLOC(h->depth_stage[q], B * px * sizeof(uint16_t));
-  for (int q = 0; q < kAux; q++) ER_ALLOC(h->zbuf[q], B * px * sizeof(uint32_t));
-  for (int q = 0; q < kAux; q++) ER_ALLOC(h->lastzero[q], B * px * sizeof(uint32_t));
-  for (int q = 0; q < kAux; q++) ER_ALLOC(h->zfix[q], B * px * sizeof(uint32_t));
-  for (int q = 0; q < kDepth; q++) ER_ALLOC(h->dstage[q], sizeof(Staging));   // device twin of the pinned staging block: ONE copy per batch
+  // the fixed allocations: a failure has er::fail's text, and er_tsdf_destroy frees what came before it
+  const char* who = "er_tsdf_create";
+  er::DevScope& M = h->fixed;
+  const size_t tiles = B * (size_t)((cols + kTile - 1) / kTile) * ((rows + kTile - 1) / kTile);
+  const size_t tiles_fine = B * (size_t)((cols + (1 << kLoShift) - 1) >> kLoShift) * ((rows + (1 << kLoShift) - 1) >> kLoShift);
+  bool bad = false;
+  bad = bad || M.alloc(&h->pool, (size_t)max_units * er::kUnitVox, who);
+  bad = bad || M.alloc(&h->ht_key, (size_t)cap, who);
+  bad = bad || M.alloc(&h->ht_slot, (size_t)cap, who);
+  for (int q = 0; q < kDepth; q++) bad = bad || M.alloc(&h->ht_mask[q], (size_t)cap, who);
+  bad = bad || M.alloc(&h->unit_key, (size_t)max_units, who);
+  bad = bad || M.alloc(&h->counters, C_COUNT, who);
+  bad = bad || M.alloc(&h->stats, 4, who);
+  for (int q = 0; q < kDepth; q++) bad = bad || M.alloc(&h->batch[q], (size_t)cap, who);
+  bad = bad || M.alloc(&h->lambda, px, who);
+  for (int q = 0; q < kDepth; q++) bad = bad || M.alloc(&h->scaled[q], B * (px + kScaledPad), who);
+  for (int q = 0; q < kDepth; q++) bad = bad || M.alloc(&h->depth_stage[q], B * px, who);
+  for (int q = 0; q < kAux; q++) bad = bad || M.alloc(&h->zbuf[q], B * px, who);
+  for (int q = 0; q < kAux; q++) bad = bad || M.alloc(&h->lastzero[q], B * px, who);
+  for (int q = 0; q < kAux; q++) bad = bad || M.alloc(&h->zfix[q], B * px, who);
+  for (int q = 0; q < kDepth; q++) bad = bad || M.alloc(&h->dstage[q], sizeof(Staging), who);   // device twin of the pinned staging block: ONE copy per batch
+  bad = bad || M.alloc(&h->T12, B * 12, who);
+  bad = bad || M.alloc(&h->seg12, B * 16, who);
+  bad = bad || M.alloc(&h->madj12, B * 12, who);
+  bad = bad || M.alloc(&h->grid_index, B, who);
+  bad = bad || M.alloc(&h->dsum, 1, who);
+  for (int q = 0; q < kDepth; q++) bad = bad || M.alloc(&h->tile_max[q], tiles, who);
+  for (int q = 0; q < kDepth; q++) bad = bad || M.alloc(&h->tile_lo[q], tiles, who);
+  for (int q = 0; q < kDepth; q++) bad = bad || M.alloc(&h->tile_lo_fine[q], tiles_fine, who);
+  for (int q = 0; q < kDepth; q++) bad = bad || M.alloc(&h->plan_rec[q], (size_t)cap, who);
+  for (int q = 0; q < kDepth; q++) bad = bad || M.alloc(&h->plan[q], 1, who);
+  if (bad) {
+    er_tsdf_destroy(h);
+    return 1;
+  }
   for (int q = 0; q < kDepth; q++) h->frames[q] = reinterpret_cast<er::FrameXform*>(reinterpret_cast<char*>(h->dstage[q]) + offsetof(Staging, fx));
-  ER_ALLOC(h->T12, B * 12 * sizeof(double));
-  ER_ALLOC(h->seg12, B * 16 * sizeof(double));
-  ER_ALLOC(h->madj12, B * 12 * sizeof(double));
-  ER_ALLOC(h->grid_index, B * sizeof(int));
-  ER_ALLOC(h->dsum, sizeof(double));
-  for (int q = 0; q < kDepth; q++) ER_ALLOC(h->tile_max[q], B * (size_t)((cols + kTile - 1) / kTile) * ((rows + kTile - 1) / kTile) * sizeof(float));
-  for (int q = 0; q < kDepth; q++) ER_ALLOC(h->tile_lo[q], B * (size_t)((cols + kTile - 1) / kTile) * ((rows + kTile - 1) / kTile) * sizeof(float));
-  for (int q = 0; q < kDepth; q++)
-    ER_ALLOC(h->tile_lo_fine[q], B * (size_t)((cols + (1 << kLoShift) - 1) >> kLoShift) * ((rows + (1 << kLoShift) - 1) >> kLoShift) * sizeof(float));
-  for (int q = 0; q < kDepth; q++) ER_ALLOC(h->plan_rec[q], (size_t)cap * sizeof(PlanRec));
-  for (int q = 0; q < kDepth; q++) ER_ALLOC(h->plan[q], sizeof(Plan));
-#undef ER_ALLOC
   hipStream_t s = h->stream;
   bool ok = hipMemsetAsync(h->pool, 0, (size_t)max_units * er::kUnitVox * sizeof(float2), s) == hipSuccess &&
             hipMemsetAsync(h->ht_key, 0xFF, (size_t)cap * sizeof(int), s) == hipSuccess &&
@@ -714,24 +711,12 @@ int er_tsdf_destroy(er_tsdf_t h) {
       if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->tl_free) (void)hipEventDestroy(e);
   if (h->tl_base) (void)hipEventDestroy(h->tl_base);
-  std::vector<void*> ptrs = {h->pool, h->ht_key, h->ht_slot, h->unit_key, h->counters, h->stats, h->lambda, h->T12, h->seg12, h->madj12,
-                             h->grid_index, h->dsum, h->ctr_dev[0], h->ctr_dev[1], h->key_scratch,
-                             h->slot_scratch, h->band_scratch, h->color, h->color_scratch};
-  for (int q = 0; q < kDepth; q++)
-    for (void* x : {(void*)h->ht_mask[q], (void*)h->batch[q], (void*)h->scaled[q], (void*)h->depth_stage[q], h->dstage[q], (void*)h->tile_max[q], (void*)h->tile_lo[q], (void*)h->tile_lo_fine[q],
-                    (void*)h->plan_rec[q], (void*)h->plan[q]})
-      ptrs.push_back(x);
-  for (int q = 0; q < kAux; q++) {
-    ptrs.push_back(h->zbuf[q]);
-    ptrs.push_back(h->lastzero[q]);
-    ptrs.push_back(h->zfix[q]);
-  }
   for (int q = 0; q < kDepth; q++) {
     if (h->pre_done[q]) (void)hipEventDestroy(h->pre_done[q]);
     if (h->int_done[q]) (void)hipEventDestroy(h->int_done[q]);
     if (h->copy_done[q]) (void)hipEventDestroy(h->copy_done[q]);
     if (h->consts_done[q]) (void)hipEventDestroy(h->consts_done[q]);
-    if (h->pinned[q]) (void)hipHostFree(h->pinned[q]);
+    h->pinned[q].reset();
   }
   for (int a = 0; a < kAux; a++)
     if (h->aux_stream[a]) (void)hipStreamDestroy(h->aux_stream[a]);
@@ -743,10 +728,9 @@ int er_tsdf_destroy(er_tsdf_t h) {
     if (h->ctr_ev[q]) (void)hipEventDestroy(h->ctr_ev[q]);
     for (int a = 0; a < kAux; a++)
       if (h->ctr_rd[q][a]) (void)hipEventDestroy(h->ctr_rd[q][a]);
-    if (h->ctr_pinned[q]) (void)hipHostFree(h->ctr_pinned[q]);
+    h->ctr_pinned[q].reset();
   }
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
+  static_cast<er_tsdf_mem&>(*h) = er_tsdf_mem();
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
   delete h;
   return 0;
@@ -789,13 +773,9 @@ static int upload_ctr(er_tsdf_t h, const float* ctr, int res, int num_grids, hip
   const size_t floats = verts * 3 * (size_t)num_grids;
   const int q = h->ctr_parity;
   h->ctr_parity ^= 1;
-  if (floats > h->ctr_dev_cap[q]) {
+  if (floats > h->ctr_dev[q].capacity()) {
     if (sync_all(h)) return 1;                       // nobody may still be reading the old buffer
-    if (h->ctr_dev[q]) (void)hipFree(h->ctr_dev[q]);
-    h->ctr_dev[q] = nullptr;
-    h->ctr_dev_cap[q] = 0;
-    ER_HIP_TRY(hipMalloc((void**)&h->ctr_dev[q], floats * sizeof(float)));
-    h->ctr_dev_cap[q] = floats;
+    if (h->ctr_dev[q].reserve(floats, "er_tsdf_integrate_frames")) return 1;
   }
   // The lattices travel through a page-locked block of the handle: the copy is then truly asynchronous (a copy from the
   // caller's pageable memory would make the host wait for everything queued on this stream at every call) and the caller's
@@ -806,13 +786,7 @@ static int upload_ctr(er_tsdf_t h, const float* ctr, int res, int num_grids, hip
   } else {
     ER_HIP_TRY(hipEventSynchronize(h->ctr_ev[q]));          // the upload of two calls ago (pinned block free again)
   }
-  if (floats > h->ctr_pinned_cap[q]) {
-    if (h->ctr_pinned[q]) (void)hipHostFree(h->ctr_pinned[q]);
-    h->ctr_pinned[q] = nullptr;
-    h->ctr_pinned_cap[q] = 0;
-    ER_HIP_TRY(hipHostMalloc((void**)&h->ctr_pinned[q], floats * sizeof(float), hipHostMallocDefault));
-    h->ctr_pinned_cap[q] = floats;
-  }
+  if (floats > h->ctr_pinned[q].capacity() && h->ctr_pinned[q].reserve(floats, "er_tsdf_integrate_frames")) return 1;
   memcpy(h->ctr_pinned[q], ctr, floats * sizeof(float));
   const int a0 = (int)(h->batch_no % kAux);
   hipStream_t C = h->aux_stream[a0];

@@ -213,14 +213,8 @@ __global__ __launch_bounds__(256) void k_zero_units(float2* __restrict__ pool, c
 }
 
 int ensure_band_scratch(er_tsdf_t h, size_t bytes) {
-  if (bytes <= h->band_scratch_cap) return 0;
-  if (h->band_scratch) (void)hipFree(h->band_scratch);
-  h->band_scratch = nullptr;
-  h->band_scratch_cap = 0;
-  const size_t cap = std::max<size_t>(bytes, (size_t)1 << 20);
-  ER_HIP_TRY(hipMalloc(&h->band_scratch, cap));
-  h->band_scratch_cap = cap;
-  return 0;
+  if (bytes <= h->band_scratch.capacity()) return 0;
+  return h->band_scratch.reserve(std::max<size_t>(bytes, (size_t)1 << 20), "the band scratch");
 }
 
 void undrop(er_tsdf_t h, const int* keys, int n) {
@@ -277,8 +271,8 @@ static int band_unit_counts(er_tsdf_t h, const int* keys_host, int n, std::vecto
   if (resolve_slots(h, keys_host, n, false)) return 1;
   const size_t cnt_bytes = (size_t)n * 2 * kBandChunks * sizeof(int), wide_bytes = ((size_t)n * sizeof(int) + 15) & ~(size_t)15;
   if (ensure_band_scratch(h, cnt_bytes + wide_bytes + (size_t)n * sizeof(long) + 64)) return 1;
-  int* d_cnt = (int*)h->band_scratch;
-  int* d_wide = (int*)((char*)h->band_scratch + cnt_bytes);
+  int* d_cnt = (int*)h->band_scratch.get();
+  int* d_wide = (int*)(h->band_scratch + cnt_bytes);
   ER_HIP_TRY(hipMemsetAsync(d_wide, 0, (size_t)n * sizeof(int), h->stream));
   hipLaunchKernelGGL(k_band_count, dim3(kBandChunks / 4, n), dim3(256), 0, h->stream, h->pool, h->slot_scratch, d_cnt, d_wide);
   ER_HIP_TRY(hipGetLastError());
@@ -325,9 +319,9 @@ int er_tsdf_export_band(er_tsdf_t h, const int* keys_host, const int* words_host
     at += w;
   }
   const size_t cnt_bytes = (size_t)n * 2 * kBandChunks * sizeof(int), wide_bytes = ((size_t)n * sizeof(int) + 15) & ~(size_t)15;
-  int* d_cnt = (int*)h->band_scratch;                            // (still holds the counts of exactly this key list)
-  int* d_wide = (int*)((char*)h->band_scratch + cnt_bytes);
-  long* d_off = (long*)((char*)h->band_scratch + cnt_bytes + wide_bytes);
+  int* d_cnt = (int*)h->band_scratch.get();                            // (still holds the counts of exactly this key list)
+  int* d_wide = (int*)(h->band_scratch + cnt_bytes);
+  long* d_off = (long*)(h->band_scratch + cnt_bytes + wide_bytes);
   ER_HIP_TRY(hipMemcpyAsync(d_off, off.data(), (size_t)n * sizeof(long), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_band_pack, dim3(kBandChunks / 4, n), dim3(256), 0, h->stream, h->pool, h->slot_scratch, d_cnt, d_wide, d_off, (uint32_t*)dev_block);
   ER_HIP_TRY(hipGetLastError());
@@ -357,7 +351,7 @@ int er_tsdf_merge_band(er_tsdf_t h, const int* keys_host, int n, const int* nsrc
   }
   if (ensure_band_scratch(h, items.size() * sizeof(BandItem))) return 1;
   ER_HIP_TRY(hipMemcpyAsync(h->band_scratch, items.data(), items.size() * sizeof(BandItem), hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(k_band_merge, dim3(kBandChunks / 4, n), dim3(256), 0, h->stream, h->pool, (const BandItem*)h->band_scratch);
+  hipLaunchKernelGGL(k_band_merge, dim3(kBandChunks / 4, n), dim3(256), 0, h->stream, h->pool, (const BandItem*)h->band_scratch.get());
   ER_HIP_TRY(hipGetLastError());
   ER_HIP_TRY(hipStreamSynchronize(h->stream));
   return 0;
@@ -371,7 +365,7 @@ int er_tsdf_import_band(er_tsdf_t h, const int* keys_host, int n, const void* co
   if (resolve_slots(h, keys_host, n, true)) return 1;
   if (ensure_band_scratch(h, (size_t)n * sizeof(void*))) return 1;
   ER_HIP_TRY(hipMemcpyAsync(h->band_scratch, recs, (size_t)n * sizeof(void*), hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(k_band_import, dim3(kBandChunks / 4, n), dim3(256), 0, h->stream, h->pool, h->slot_scratch, (const uint32_t* const*)h->band_scratch);
+  hipLaunchKernelGGL(k_band_import, dim3(kBandChunks / 4, n), dim3(256), 0, h->stream, h->pool, h->slot_scratch, (const uint32_t* const*)h->band_scratch.get());
   ER_HIP_TRY(hipGetLastError());
   return check_flags(h);                                         // (synchronises: recs may be a host temporary)
 }

@@ -182,15 +182,10 @@ __global__ __launch_bounds__(256) void k_zero_unit_colors(unsigned long long* __
 size_t round256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 int ensure_color_scratch(er_tsdf_t h, size_t bytes) {
-  if (bytes <= h->color_scratch_cap) return 0;
-  if (h->color_scratch) (void)hipFree(h->color_scratch);
-  h->color_scratch = nullptr;
-  h->color_scratch_cap = 0;
-  if (hipMalloc(&h->color_scratch, bytes) != hipSuccess) {
+  if (h->color_scratch.reserve(bytes, "colour staging")) {
     (void)hipGetLastError();
     return er::fail("colour staging: cannot allocate %zu bytes of device memory", bytes);
   }
-  h->color_scratch_cap = bytes;
   return 0;
 }
 
@@ -239,7 +234,7 @@ int color_run(er_tsdf_t h, const char* who, int n, const uint16_t* depth, const 
   const size_t o_zbuf = take(warp ? px * 4 : 0), o_lz = take(warp ? px * 4 : 0), o_zfix = take(warp ? px * 4 : 0), o_win = take(warp ? px * 4 : 0);
   const size_t o_Z = take(warp ? px * sizeof(uint16_t) : 0), o_C = take(warp ? px * 3 : 0);
   if (ensure_color_scratch(h, off)) return 1;
-  char* S = static_cast<char*>(h->color_scratch);
+  char* S = h->color_scratch;
   hipStream_t X = h->stream;
   unsigned long long* d_stats = reinterpret_cast<unsigned long long*>(S + o_stats);
   double* d_T = reinterpret_cast<double*>(S + o_T);
@@ -335,7 +330,7 @@ int color_sample_on_device(er_tsdf_t h, const char* who, const float4* d_points,
   if (n == 0) return 0;
   if (n < 0 || n > 0x7FFFFFFFL) return er::fail("%s: %ld points are more than the 2^31 - 1 a colour call takes", who, n);
   if (ensure_color_scratch(h, 256)) return 1;                // (the level counts, which nobody reads here)
-  unsigned long long* d_counts = static_cast<unsigned long long*>(h->color_scratch);
+  unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(h->color_scratch.get());
   ER_HIP_TRY(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), h->stream));
   hipLaunchKernelGGL(k_color_sample, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, h->color, h->ht_key, h->ht_slot,
                      h->ht_cap - 1, h->ht_shift, h->max_units, d_points, n, d_rgba, d_counts);
@@ -353,17 +348,15 @@ int er_tsdf_color_enable(er_tsdf_t h) {
   if (h->color) return 0;
   ER_HIP_TRY(hipSetDevice(h->device));
   const size_t bytes = (size_t)h->max_units * kUnitVox * 16;
-  unsigned long long* c = nullptr;
-  if (hipMalloc(&c, bytes) != hipSuccess) {
+  if (h->color.reserve(bytes / sizeof(unsigned long long), "er_tsdf_color_enable")) {
     (void)hipGetLastError();
     return er::fail("er_tsdf_color_enable: cannot allocate %zu bytes of device memory for the colour of %d units", bytes, h->max_units);
   }
-  if (hipMemsetAsync(c, 0, bytes, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) {
+  if (hipMemsetAsync(h->color, 0, bytes, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) {
     (void)hipGetLastError();
-    (void)hipFree(c);
+    h->color.reset();                                          // (enabled only once the block is zero)
     return er::fail("er_tsdf_color_enable: cannot zero %zu bytes of device memory", bytes);
   }
-  h->color = c;
   return 0;
 }
 
@@ -419,7 +412,7 @@ int er_tsdf_sample_colors(er_tsdf_t h, const float* points_host, long n, uint8_t
   if (n == 0) return 0;
   const size_t off_p = 256, off_o = off_p + round256((size_t)n * 16);
   if (ensure_color_scratch(h, off_o + round256((size_t)n * 4))) return 1;
-  char* S = static_cast<char*>(h->color_scratch);
+  char* S = h->color_scratch;
   unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(S);
   ER_HIP_TRY(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), h->stream));
   ER_HIP_TRY(hipMemcpyAsync(S + off_p, points_host, (size_t)n * 16, hipMemcpyHostToDevice, h->stream));

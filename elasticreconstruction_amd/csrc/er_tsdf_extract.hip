@@ -556,46 +556,24 @@ __global__ __launch_bounds__(256) void k_import_world(float2* __restrict__ pool,
   *v = make_float2(p.w, 1.0f);
 }
 
-// One HIP call of an entry point: a failure is reported under the entry point's name and ends the function.
-#define ER_W(who, expr)                                                                         \
-  do {                                                                                          \
-    hipError_t e_ = (expr);                                                                     \
-    if (e_ != hipSuccess) return er::fail("%s: %s failed: %s", who, #expr, hipGetErrorString(e_)); \
-  } while (0)
-// hipMalloc of a device temporary that the call's SlabPass t frees: pp = the address of the caller's pointer.
-#define ER_W_OWNED(who, t, pp, bytes)                 \
-  do {                                                \
-    ER_W(who, hipMalloc((void**)pp, bytes));          \
-    (t).more.push_back(*(pp));                        \
-  } while (0)
-
-// The device temporaries of one extraction call, freed when the call leaves, whichever way, and the first of its two passes.
+// The first of the two passes of one extraction call over the device temporaries of that call: they live in `scope`, the call's own (freed when
+// the call leaves, whichever way) or the one of the DeviceMesh that the call fills, and so does what the caller adds (its output, a table).
 // d_keys / d_slots: the units in ascending key order; d_cnt / d_off: per slab (64 per unit) what the count pass found and where the write
-// pass starts; more: what the caller adds with ER_W_OWNED (its output, a table).
+// pass starts.
 struct SlabPass {
+  DevScope& scope;
   int n = 0, nslab = 0;
   int *d_keys = nullptr, *d_slots = nullptr;
   long *d_cnt = nullptr, *d_off = nullptr;
   std::vector<long> off;                       // the offsets on the host (count)
-  std::vector<void*> more;
 
-  SlabPass() = default;
-  SlabPass(const SlabPass&) = delete;
-  SlabPass& operator=(const SlabPass&) = delete;
-  ~SlabPass() {
-    for (void* p : {(void*)d_keys, (void*)d_slots, (void*)d_cnt, (void*)d_off})
-      if (p) (void)hipFree(p);
-    for (void* p : more) (void)hipFree(p);
-  }
+  explicit SlabPass(DevScope& s) : scope(s) {}
 
   int alloc(const char* who, int n_units) {
     n = n_units;
     nslab = n * 64;
-    ER_W(who, hipMalloc((void**)&d_keys, (size_t)n * sizeof(int)));
-    ER_W(who, hipMalloc((void**)&d_slots, (size_t)n * sizeof(int)));
-    ER_W(who, hipMalloc((void**)&d_cnt, (size_t)nslab * sizeof(long)));
-    ER_W(who, hipMalloc((void**)&d_off, (size_t)nslab * sizeof(long)));
-    return 0;
+    return scope.alloc(&d_keys, (size_t)n, who) || scope.alloc(&d_slots, (size_t)n, who) || scope.alloc(&d_cnt, (size_t)nslab, who) ||
+           scope.alloc(&d_off, (size_t)nslab, who);
   }
 
   // Uploads the unit list, runs the caller's count launch (-> 0, or non-zero after reporting its failure), reads the slab counts back and
@@ -634,7 +612,8 @@ int extract_points(er_tsdf_t h, float* out_host, long capacity, long* count, int
   *count = 0;
   if (n == 0) return 0;
   const int nslab = n * 64;
-  SlabPass t;
+  DevScope own;
+  SlabPass t(own);
   float4* d_out = nullptr;
   long total = 0;
   auto launch = [&](float4* out, int pass) {
@@ -650,7 +629,7 @@ int extract_points(er_tsdf_t h, float* out_host, long capacity, long* count, int
   *count = total;
   if (out_host && total > 0) {
     if (capacity < total) return er::fail("er_tsdf_extract_world: capacity %ld < %ld points", capacity, total);
-    ER_W_OWNED(who, t, &d_out, (size_t)total * sizeof(float4));
+    if (t.scope.alloc(&d_out, (size_t)total, who)) return 1;
     if (t.upload_offsets(h, who) || launch(d_out, 1)) return 1;
     ER_W(who, hipMemcpyAsync(out_host, d_out, (size_t)total * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
     ER_W(who, hipStreamSynchronize(h->stream));
@@ -678,8 +657,8 @@ int oriented_on_device(er_tsdf_t h, const char* who, bool want, SlabPass& t, flo
   if (t.alloc(who, n) || t.count(h, who, keys, slots, [&] { return launch(nullptr, 0); }, &total)) return 1;
   *total_out = total;
   if (want && total > 0) {
-    ER_W_OWNED(who, t, d_pts, (size_t)total * sizeof(float4));
-    ER_W_OWNED(who, t, d_nrm, (size_t)total * sizeof(float4));
+    if (t.scope.alloc(d_pts, (size_t)total, who)) return 1;
+    if (t.scope.alloc(d_nrm, (size_t)total, who)) return 1;
     if (t.upload_offsets(h, who) || launch(*d_pts, 1)) return 1;
     hipLaunchKernelGGL(k_surface_normals, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->pool, h->ht_key, h->ht_slot, h->ht_cap - 1,
                        h->ht_shift, *d_pts, total, *d_nrm);
@@ -703,7 +682,8 @@ int er_tsdf_extract_oriented(er_tsdf_t h, float* points_host, float* normals_hos
   if (!h || !count) return er::fail("er_tsdf_extract_oriented: NULL argument");
   ER_HIP_TRY(hipSetDevice(h->device));
   const bool want = points_host && normals_host;
-  SlabPass t;
+  DevScope own;
+  SlabPass t(own);
   float4 *d_pts = nullptr, *d_nrm = nullptr;
   *count = 0;
   if (oriented_on_device(h, "er_tsdf_extract_oriented", want, t, &d_pts, &d_nrm, count)) return 1;
@@ -728,7 +708,8 @@ int er_cloud_create_from_tsdf(er_tsdf_t h, float cube_length, float grid_cell, e
   if (n_points) *n_points = 0;
   if (!(grid_cell > 0.f)) return er::fail("er_cloud_create_from_tsdf: grid_cell must be positive");
   ER_HIP_TRY(hipSetDevice(h->device));
-  SlabPass t;
+  DevScope own;
+  SlabPass t(own);
   float4 *d_pts = nullptr, *d_nrm = nullptr;
   long total = 0, kept = 0;
   if (oriented_on_device(h, who, true, t, &d_pts, &d_nrm, &total)) return 1;
@@ -737,7 +718,7 @@ int er_cloud_create_from_tsdf(er_tsdf_t h, float cube_length, float grid_cell, e
   const long nblk = (total + 63) / 64;
   std::vector<long> blk((size_t)nblk * 2);
   if (total > 0) {
-    ER_W_OWNED(who, t, &d_blk, (size_t)nblk * 2 * sizeof(long));
+    if (t.scope.alloc(&d_blk, (size_t)nblk * 2, who)) return 1;
     hipLaunchKernelGGL(k_oriented_keep, dim3((unsigned)nblk), dim3(64), 0, h->stream, d_pts, d_nrm, total, cube_length, d_blk, d_blk + nblk,
                        (float*)nullptr, (float*)nullptr, 0);
     ER_W(who, hipGetLastError());
@@ -750,7 +731,7 @@ int er_cloud_create_from_tsdf(er_tsdf_t h, float cube_length, float grid_cell, e
     if (kept >= (1L << 27))
       return er::fail("er_cloud_create_from_tsdf: %ld points; the limit is 2^27 - 1 (32-bit byte offsets in the search kernels)", kept);
     if (kept > 0) {
-      ER_W_OWNED(who, t, &d_rows, (size_t)kept * 6 * sizeof(float));
+      if (t.scope.alloc(&d_rows, (size_t)kept * 6, who)) return 1;
       ER_W(who, hipMemcpyAsync(d_blk + nblk, blk.data() + nblk, (size_t)nblk * sizeof(long), hipMemcpyHostToDevice, h->stream));
       hipLaunchKernelGGL(k_oriented_keep, dim3((unsigned)nblk), dim3(64), 0, h->stream, d_pts, d_nrm, total, cube_length, d_blk, d_blk + nblk,
                          d_rows, d_rows + (size_t)kept * 3, 1);
@@ -779,7 +760,8 @@ int er_tsdf_extract_mesh(er_tsdf_t h, float* tri_host, long capacity_triangles, 
   *n_triangles = 0;
   if (n == 0) return 0;
   const int nslab = n * 64;
-  SlabPass t;
+  DevScope own;
+  SlabPass t(own);
   unsigned char* d_tab = nullptr;
   float* d_out = nullptr;
   long total = 0;
@@ -790,7 +772,7 @@ int er_tsdf_extract_mesh(er_tsdf_t h, float* tri_host, long capacity_triangles, 
     return 0;
   };
   if (t.alloc(who, n)) return 1;
-  ER_W_OWNED(who, t, &d_tab, 256 * 16);
+  if (t.scope.alloc(&d_tab, 256 * 16, who)) return 1;
   auto count_launch = [&] {
     ER_W(who, hipMemcpyAsync(d_tab, er::mc_table().tri, 256 * 16, hipMemcpyHostToDevice, h->stream));
     return launch(nullptr, 0);
@@ -799,7 +781,7 @@ int er_tsdf_extract_mesh(er_tsdf_t h, float* tri_host, long capacity_triangles, 
   *n_triangles = total;
   if (tri_host && total > 0) {
     if (capacity_triangles < total) return er::fail("er_tsdf_extract_mesh: capacity %ld < %ld triangles", capacity_triangles, total);
-    ER_W_OWNED(who, t, &d_out, (size_t)total * 9 * sizeof(float));
+    if (t.scope.alloc(&d_out, (size_t)total * 9, who)) return 1;
     if (t.upload_offsets(h, who) || launch(d_out, 1)) return 1;
     ER_W(who, hipMemcpyAsync(tri_host, d_out, (size_t)total * 9 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     ER_W(who, hipStreamSynchronize(h->stream));
@@ -841,7 +823,7 @@ int er_tsdf_k::mesh_indexed_on_device(er_tsdf_t h, const char* who, bool want_v,
   if (n == 0) return 0;                                     // (an empty volume: 0 and 0)
   const int nslab = n * 64;
   const size_t nrow = (size_t)nslab * 64;
-  SlabPass t;
+  SlabPass t(m->owned);                   // every temporary belongs to the caller's mesh: the kernels that read them are in flight on return
   unsigned char* d_tab = nullptr;
   unsigned long long* d_bm = nullptr;     // [row][axis]: the edge bitmap
   int *d_rank = nullptr, *d_rowoff = nullptr;
@@ -856,12 +838,12 @@ int er_tsdf_k::mesh_indexed_on_device(er_tsdf_t h, const char* who, bool want_v,
     return 0;
   };
   if (t.alloc(who, n)) return 1;
-  ER_W_OWNED(who, t, &d_tab, 256 * 16);
-  ER_W_OWNED(who, t, &d_bm, nrow * 3 * sizeof(unsigned long long));
-  ER_W_OWNED(who, t, &d_rank, rank.size() * sizeof(int));
-  ER_W_OWNED(who, t, &d_rowoff, nrow * sizeof(int));
-  ER_W_OWNED(who, t, &d_vcnt, (size_t)nslab * sizeof(long));
-  ER_W_OWNED(who, t, &d_voff, (size_t)nslab * sizeof(long));
+  if (t.scope.alloc(&d_tab, 256 * 16, who)) return 1;
+  if (t.scope.alloc(&d_bm, nrow * 3, who)) return 1;
+  if (t.scope.alloc(&d_rank, rank.size(), who)) return 1;
+  if (t.scope.alloc(&d_rowoff, nrow, who)) return 1;
+  if (t.scope.alloc(&d_vcnt, (size_t)nslab, who)) return 1;
+  if (t.scope.alloc(&d_voff, (size_t)nslab, who)) return 1;
   auto count_launch = [&] {
     ER_W(who, hipMemcpyAsync(d_tab, er::mc_table().tri, 256 * 16, hipMemcpyHostToDevice, h->stream));
     ER_W(who, hipMemcpyAsync(d_rank, rank.data(), rank.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -886,28 +868,22 @@ int er_tsdf_k::mesh_indexed_on_device(er_tsdf_t h, const char* who, bool want_v,
   if (nv == 0 || (!want_v && !want_t)) return 0;
   ER_W(who, hipMemcpyAsync(d_voff, vcnt.data(), (size_t)nslab * sizeof(long), hipMemcpyHostToDevice, h->stream));
   if (want_v) {
-    ER_W_OWNED(who, t, &m->d_verts, (size_t)nv * sizeof(float4));
+    if (t.scope.alloc(&m->d_verts, (size_t)nv, who)) return 1;
     hipLaunchKernelGGL(k_mesh_verts, dim3(nslab), dim3(64), 0, h->stream, h->pool, t.d_slots, t.d_keys, h->ht_key, h->ht_slot, h->ht_cap - 1, h->ht_shift,
                        d_bm, d_rowoff, d_voff, m->d_verts);
     ER_W(who, hipGetLastError());
     if (want_n) {
-      ER_W_OWNED(who, t, &m->d_nrm, (size_t)nv * sizeof(float4));
+      if (t.scope.alloc(&m->d_nrm, (size_t)nv, who)) return 1;
       hipLaunchKernelGGL(k_surface_normals, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, h->stream, h->pool, h->ht_key, h->ht_slot, h->ht_cap - 1,
                          h->ht_shift, m->d_verts, nv, m->d_nrm);
       ER_W(who, hipGetLastError());
     }
   }
   if (want_t) {
-    ER_W_OWNED(who, t, &m->d_tri, (size_t)ntri * 3 * sizeof(int));
+    if (t.scope.alloc(&m->d_tri, (size_t)ntri * 3, who)) return 1;
     if (t.upload_offsets(h, who) || launch(m->d_tri, 1)) return 1;
   }
-  // the kernels are still in flight on h->stream: everything they read or write now belongs to the caller's DeviceMesh
-  for (void* p : {(void*)t.d_keys, (void*)t.d_slots, (void*)t.d_cnt, (void*)t.d_off}) m->owned.push_back(p);
-  m->owned.insert(m->owned.end(), t.more.begin(), t.more.end());
-  t.d_keys = t.d_slots = nullptr;
-  t.d_cnt = t.d_off = nullptr;
-  t.more.clear();
-  return 0;
+  return 0;                                                  // (the kernels are still in flight on h->stream: what they read or write is m's)
 }
 
 extern "C" {
@@ -953,10 +929,10 @@ int er_tsdf_import_world(er_tsdf_t h, const float* xyzi_host, long n, int* n_uni
     bool armed = true;
     ~Undo() { if (armed) (void)er_tsdf_reset(h); }
   } undo{h};
-  SlabPass t;                                                // (only as the owner of the staging buffer)
+  DevScope own;
   const long chunk = std::min<long>(n, 1L << 22);            // 64 MiB of rows at a time
-  float4* d_rows = nullptr;
-  ER_W_OWNED(who, t, &d_rows, (size_t)chunk * sizeof(float4));
+  float4* d_rows = nullptr;                                  // the staging buffer
+  if (own.alloc(&d_rows, (size_t)chunk, who)) return 1;
   // the units: fresh ones of an empty volume are (+0, 0) everywhere (er_tsdf_create, er_tsdf_reset)
   if (resolve_slots(h, ukeys.data(), (int)ukeys.size(), true) || check_flags(h)) return 1;
   for (long r0 = 0; r0 < n; r0 += chunk) {
@@ -991,8 +967,5 @@ int er_tsdf_import_world(er_tsdf_t h, const float* xyzi_host, long n, int* n_uni
   if (n_units) *n_units = (int)ukeys.size();
   return 0;
 }
-
-#undef ER_W_OWNED
-#undef ER_W
 
 }  // extern "C"

@@ -119,22 +119,24 @@ constexpr int kMaxJobs = 65535;               // jobs sit on blockIdx.z
 struct JobTable {
   std::mutex lock;
   int device = -1;
-  size_t cap = 0;
-  RayJob *host = nullptr, *dev = nullptr;
+  er::PinnedBuffer<RayJob> host;
+  er::Buffer<RayJob> dev;
 };
-JobTable g_jobs;
+JobTable& job_table() {
+  static JobTable* t = new JobTable();     // intentionally leaked: its memory is never freed behind the HIP runtime's back at exit
+  return *t;
+}
 
 int job_table_reserve(JobTable& t, int device, size_t n) {
-  if (t.device == device && n <= t.cap) return 0;
-  if (t.host) (void)hipHostFree(t.host);
-  if (t.dev) (void)hipFree(t.dev);
-  t.host = t.dev = nullptr;
-  t.cap = 0;
+  if (t.device == device && n <= t.dev.capacity()) return 0;
+  t.host.reset();                                        // (another device's table goes whatever its size)
+  t.dev.reset();
   t.device = -1;
   const size_t cap = std::max<size_t>(n, 256);
-  ER_HIP_TRY(hipHostMalloc((void**)&t.host, cap * sizeof(RayJob), hipHostMallocDefault));
-  ER_HIP_TRY(hipMalloc((void**)&t.dev, cap * sizeof(RayJob)));
-  t.cap = cap;
+  if (t.host.reserve(cap, "er_tsdf_raycast_batch") || t.dev.reserve(cap, "er_tsdf_raycast_batch")) {
+    t.dev.reset();
+    return 1;
+  }
   t.device = device;
   return 0;
 }
@@ -175,11 +177,12 @@ int er_tsdf_raycast(er_tsdf_t h, int cols, int rows, const float cam4[4], const 
   const size_t npix = (size_t)cols * rows;
   float4* d_rec = out_on_device ? (float4*)rec_out : nullptr;
   uint16_t* d_depth = out_on_device ? depth_out : nullptr;
-  void* tmp = nullptr;                                   // host outputs: one device temporary, records then depth
+  er::DevScope own;
+  char* tmp = nullptr;                                   // host outputs: one device temporary, records then depth
   if (!out_on_device) {
-    ER_HIP_TRY(hipMalloc(&tmp, npix * (2 * sizeof(float4) + sizeof(uint16_t))));
+    if (own.alloc(&tmp, npix * (2 * sizeof(float4) + sizeof(uint16_t)), who)) return 1;
     if (rec_out) d_rec = (float4*)tmp;
-    if (depth_out) d_depth = (uint16_t*)((char*)tmp + npix * 2 * sizeof(float4));
+    if (depth_out) d_depth = (uint16_t*)(tmp + npix * 2 * sizeof(float4));
   }
   hipLaunchKernelGGL(k_raycast, dim3((cols + kGroupPx - 1) / kGroupPx, (rows + kGroupPx - 1) / kGroupPx), dim3(kGroupPx * kGroupPx), 0, h->stream,
                      h->pool, h->ht_key, h->ht_slot, h->ht_cap - 1, h->ht_shift, h->max_units, I, cols, rows, d_rec, d_depth);
@@ -187,7 +190,6 @@ int er_tsdf_raycast(er_tsdf_t h, int cols, int rows, const float cam4[4], const 
   if (e == hipSuccess && !out_on_device && rec_out) e = hipMemcpyAsync(rec_out, d_rec, npix * 2 * sizeof(float4), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess && !out_on_device && depth_out) e = hipMemcpyAsync(depth_out, d_depth, npix * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (tmp) (void)hipFree(tmp);
   if (e != hipSuccess) return er::fail("%s: %s", who, hipGetErrorString(e));
   return 0;
 }
@@ -230,14 +232,15 @@ int er_tsdf_raycast_batch(int n_jobs, const er_tsdf_t* vol, const int* cols, con
     for (int q = 0; q < j && !seen; q++) seen = vol[q] == vol[j];
     if (!seen && check_flags(vol[j])) return 1;
   }
-  std::lock_guard<std::mutex> guard(g_jobs.lock);
-  if (job_table_reserve(g_jobs, device, (size_t)n_jobs)) return 1;
+  std::lock_guard<std::mutex> guard(job_table().lock);
+  JobTable& jobs = job_table();
+  if (job_table_reserve(jobs, device, (size_t)n_jobs)) return 1;
   for (int j = 0; j < n_jobs; j++) {
     er_raycast_params P;
     er_raycast_params_default(&P);
     if (params) P = params[j];
     er_tsdf_t h = vol[j];
-    RayJob& J = g_jobs.host[j];
+    RayJob& J = jobs.host[j];
     J.pool = h->pool;
     J.ht_key = h->ht_key;
     J.ht_slot = h->ht_slot;
@@ -253,9 +256,9 @@ int er_tsdf_raycast_batch(int n_jobs, const er_tsdf_t* vol, const int* cols, con
   er::StreamLease lease;                                   // a stream of the call's own; its destructor drains it
   if (lease.acquire(device)) return 1;
   hipStream_t st = lease.stream;
-  ER_HIP_TRY(hipMemcpyAsync(g_jobs.dev, g_jobs.host, sizeof(RayJob) * (size_t)n_jobs, hipMemcpyHostToDevice, st));
+  ER_HIP_TRY(hipMemcpyAsync(jobs.dev, jobs.host, sizeof(RayJob) * (size_t)n_jobs, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_raycast_batch, dim3((max_cols + kGroupPx - 1) / kGroupPx, (max_rows + kGroupPx - 1) / kGroupPx, n_jobs), dim3(kGroupPx * kGroupPx),
-                     0, st, g_jobs.dev);
+                     0, st, jobs.dev);
   ER_HIP_TRY(hipGetLastError());
   ER_HIP_TRY(hipStreamSynchronize(st));
   return 0;
