@@ -14,7 +14,7 @@ struct CleanedMesh {
   long stats[4] = {0, 0, 0, 0};            // components found, components kept, vertices dropped, triangles dropped
   float4 *d_verts = nullptr, *d_nrm = nullptr;
   int *d_index = nullptr, *d_tri = nullptr;
-  std::vector<long> off;                   // the host's block offsets: a copy enqueued on h->stream reads them, so they live as long as this
+  TwoPass lists;                           // the vertex and the triangle list between their passes (er_compact.h)
 };
 
 // ---- er_mesh_cc.hip ----

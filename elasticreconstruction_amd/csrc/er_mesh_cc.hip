@@ -113,46 +113,28 @@ __device__ __forceinline__ bool cc_keep(const unsigned long long* __restrict__ c
   return (long)cnt[l] >= min_tri && (best < 0 || l == best);
 }
 
-// Vertices, two passes like k_oriented_keep.  pass 0: blk[3 b ..] = kept vertices, roots, kept roots of block b.  pass 1: behind the host's
-// prefix over the first of these (off[b]) the kept vertices move, in their order: remap[v] = the new index or -1, index_out[new] = v, and the
-// float4 rows of verts / nrm where those arrays exist.
+// Vertices, the two passes of er_compact.h with three tallies.  pass 0: blk[3 b ..] = kept vertices, roots, kept roots of block b.  pass 1: behind
+// the host's prefix over the first of these (off[b]) the kept vertices move, in their order: remap[v] = the new index or -1, index_out[new] = v,
+// and the float4 rows of verts / nrm where those arrays exist.
 __global__ __launch_bounds__(kCcBlock) void k_cc_vertices(const int* __restrict__ label, const unsigned long long* __restrict__ cnt, long nv, long min_tri,
                                                           int best, long* __restrict__ blk, const long* __restrict__ off, int pass,
                                                           int* __restrict__ remap, int* __restrict__ index_out, const float4* __restrict__ verts,
                                                           float4* __restrict__ verts_out, const float4* __restrict__ nrm, float4* __restrict__ nrm_out) {
-  __shared__ int s_keep[kCcBlock / 64], s_root[kCcBlock / 64], s_kroot[kCcBlock / 64];
+  __shared__ int s_tally[3][kCcBlock / 64];
   const long v = (long)blockIdx.x * kCcBlock + threadIdx.x;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   bool keep = false, root = false;
   if (v < nv) {
     const int l = label[v];
     keep = cc_keep(cnt, l, min_tri, best);
     root = l == (int)v;
   }
-  const unsigned long long bk = __ballot(keep), br = __ballot(root), bkr = __ballot(keep && root);
-  if (lane == 0) {
-    s_keep[w] = __popcll(bk);
-    s_root[w] = __popcll(br);
-    s_kroot[w] = __popcll(bkr);
-  }
-  __syncthreads();
+  const BlockTally<kCcBlock, 3> tally(s_tally, {keep, root, keep && root});
   if (!pass) {
-    if (threadIdx.x == 0) {
-      long k = 0, r = 0, kr = 0;
-      for (int q = 0; q < kCcBlock / 64; q++) {
-        k += s_keep[q];
-        r += s_root[q];
-        kr += s_kroot[q];
-      }
-      blk[3 * (long)blockIdx.x] = k;
-      blk[3 * (long)blockIdx.x + 1] = r;
-      blk[3 * (long)blockIdx.x + 2] = kr;
-    }
+    tally.block_totals(blk);
     return;
   }
   if (v >= nv) return;
-  long o = off[blockIdx.x] + __popcll(bk & ((1ull << lane) - 1ull));
-  for (int q = 0; q < w; q++) o += s_keep[q];
+  const long o = tally.rank_in_block(off[blockIdx.x]);
   remap[v] = keep ? (int)o : -1;
   if (keep) {
     index_out[o] = (int)v;
@@ -166,9 +148,8 @@ __global__ __launch_bounds__(kCcBlock) void k_cc_vertices(const int* __restrict_
 __global__ __launch_bounds__(kCcBlock) void k_cc_triangles(const int* __restrict__ tri, long nt, const int* __restrict__ label,
                                                            const unsigned long long* __restrict__ cnt, long min_tri, int best, long* __restrict__ blk,
                                                            const long* __restrict__ off, int pass, const int* __restrict__ remap, int* __restrict__ out) {
-  __shared__ int s_keep[kCcBlock / 64];
+  __shared__ int s_tally[1][kCcBlock / 64];
   const long t = (long)blockIdx.x * kCcBlock + threadIdx.x;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   int a = 0, b = 0, c = 0;
   bool keep = false;
   if (t < nt) {
@@ -177,20 +158,13 @@ __global__ __launch_bounds__(kCcBlock) void k_cc_triangles(const int* __restrict
     c = tri[3 * t + 2];
     keep = cc_keep(cnt, label[a], min_tri, best);
   }
-  const unsigned long long bk = __ballot(keep);
-  if (lane == 0) s_keep[w] = __popcll(bk);
-  __syncthreads();
+  const BlockTally<kCcBlock, 1> tally(s_tally, {keep});
   if (!pass) {
-    if (threadIdx.x == 0) {
-      long k = 0;
-      for (int q = 0; q < kCcBlock / 64; q++) k += s_keep[q];
-      blk[blockIdx.x] = k;
-    }
+    tally.block_totals(blk);
     return;
   }
   if (!keep) return;
-  long o = off[blockIdx.x] + __popcll(bk & ((1ull << lane) - 1ull));
-  for (int q = 0; q < w; q++) o += s_keep[q];
+  const long o = tally.rank_in_block(off[blockIdx.x]);
   out[3 * o] = remap[a];
   out[3 * o + 1] = remap[b];
   out[3 * o + 2] = remap[c];
@@ -257,24 +231,25 @@ int er_mesh_components(const int* tri_host, long n_triangles, long n_vertices, i
   }
   ER_HIP_TRY(hipSetDevice(device));
   hipStream_t s = nullptr;                                   // (the null stream: the call is synchronous)
+  TwoPass lists;                                             // (only the count pass: the roots are its second tally; outlives `own`)
   er::DevScope own;
   int *d_tri = nullptr, *d_label = nullptr, *d_word = nullptr;
   unsigned long long* d_cnt = nullptr;
-  long *d_vcnt = nullptr, *d_blk = nullptr;
+  long* d_vcnt = nullptr;
   const long nblk = (long)cc_grid(nv);
+  const int lv = lists.add(nblk, 3);
   if (own.alloc(&d_tri, (size_t)nt * 3, who)) return 1;
   if (own.alloc(&d_label, (size_t)nv, who)) return 1;
   if (own.alloc(&d_cnt, (size_t)nv, who)) return 1;
   if (own.alloc(&d_word, 1, who)) return 1;
-  if (own.alloc(&d_blk, (size_t)nblk * 3, who)) return 1;
+  if (lists.alloc(own, who)) return 1;
   ER_W(who, hipMemcpyAsync(d_tri, tri_host, (size_t)nt * 3 * sizeof(int), hipMemcpyHostToDevice, s));
   int r = 0;
   if (cc_label(who, s, d_tri, nt, nv, d_label, d_cnt, d_word, &r)) return 1;
-  hipLaunchKernelGGL(k_cc_vertices, dim3((unsigned)nblk), dim3(kCcBlock), 0, s, d_label, d_cnt, nv, 0L, -1, d_blk, (const long*)nullptr, 0,
+  hipLaunchKernelGGL(k_cc_vertices, dim3((unsigned)nblk), dim3(kCcBlock), 0, s, d_label, d_cnt, nv, 0L, -1, lists.blk(lv), lists.off(lv), 0,
                      (int*)nullptr, (int*)nullptr, (const float4*)nullptr, (float4*)nullptr, (const float4*)nullptr, (float4*)nullptr);
   ER_W(who, hipGetLastError());
-  std::vector<long> blk((size_t)nblk * 3);
-  ER_W(who, hipMemcpyAsync(blk.data(), d_blk, blk.size() * sizeof(long), hipMemcpyDeviceToHost, s));
+  if (lists.read_counts(who, s)) return 1;
   if (count_host) {
     if (own.alloc(&d_vcnt, (size_t)nv, who)) return 1;
     hipLaunchKernelGGL(k_cc_vertex_count, dim3((unsigned)nblk), dim3(kCcBlock), 0, s, d_label, d_cnt, nv, d_vcnt);
@@ -283,9 +258,8 @@ int er_mesh_components(const int* tri_host, long n_triangles, long n_vertices, i
   }
   if (label_host) ER_W(who, hipMemcpyAsync(label_host, d_label, (size_t)nv * sizeof(int), hipMemcpyDeviceToHost, s));
   ER_W(who, hipStreamSynchronize(s));
-  long roots = 0;
-  for (long b = 0; b < nblk; b++) roots += blk[(size_t)(3 * b + 1)];
-  *n_components = roots;
+  lists.prefix();
+  *n_components = lists.total(lv, 1);
   if (rounds) *rounds = r;
   return 0;
 }
@@ -303,8 +277,8 @@ int er_tsdf_extract_mesh_cleaned(er_tsdf_t h, long min_triangles, int largest_on
   if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
   const bool want_v = verts_host || normals_host, want_rows = want_v || index_host;
   hipStream_t s = h->stream;
+  CleanedMesh c;                                             // (before m: its lists outlive the copies that m's hipFree waits for)
   DeviceMesh m;
-  CleanedMesh c;
   auto counted = [&](const CleanedMesh& k) {
     *n_vertices = k.nv;
     *n_triangles = k.ntri;
@@ -361,51 +335,39 @@ int mesh_cleaned_on_device(er_tsdf_t h, const char* who, long min_triangles, int
 
   // what stays: counts per block, offsets on the host
   const long nbv = (long)cc_grid(nv), nbt = (long)cc_grid(nt);
-  long* d_blk = nullptr;                                      // [3 nbv] vertex counts, [nbt] triangle counts, then [nbv] and [nbt] offsets
-  if (m.owned.alloc(&d_blk, (size_t)(4 * nbv + 2 * nbt), who)) return 1;
-  long *d_bt = d_blk + 3 * nbv, *d_ov = d_bt + nbt, *d_ot = d_ov + nbv;
+  TwoPass& lists = c->lists;
+  const int lv = lists.add(nbv, 3), lt = lists.add(nbt, 1);
+  if (lists.alloc(m.owned, who)) return 1;
   int *d_remap = nullptr, *d_index = nullptr, *d_tri_out = nullptr;
   float4 *d_verts_out = nullptr, *d_nrm_out = nullptr;
   auto vertices = [&](int pass) {
-    hipLaunchKernelGGL(k_cc_vertices, dim3((unsigned)nbv), dim3(kCcBlock), 0, s, d_label, d_cnt, nv, min_triangles, best, d_blk, d_ov, pass, d_remap, d_index,
-                       m.d_verts, d_verts_out, m.d_nrm, d_nrm_out);
+    hipLaunchKernelGGL(k_cc_vertices, dim3((unsigned)nbv), dim3(kCcBlock), 0, s, d_label, d_cnt, nv, min_triangles, best, lists.blk(lv), lists.off(lv), pass,
+                       d_remap, d_index, m.d_verts, d_verts_out, m.d_nrm, d_nrm_out);
     ER_W(who, hipGetLastError());
     return 0;
   };
   auto triangles = [&](int pass) {
-    hipLaunchKernelGGL(k_cc_triangles, dim3((unsigned)nbt), dim3(kCcBlock), 0, s, m.d_tri, nt, d_label, d_cnt, min_triangles, best, d_bt, d_ot, pass, d_remap,
-                       d_tri_out);
+    hipLaunchKernelGGL(k_cc_triangles, dim3((unsigned)nbt), dim3(kCcBlock), 0, s, m.d_tri, nt, d_label, d_cnt, min_triangles, best, lists.blk(lt), lists.off(lt), pass,
+                       d_remap, d_tri_out);
     ER_W(who, hipGetLastError());
     return 0;
   };
   if (vertices(0) || triangles(0)) return 1;
-  std::vector<long> blk((size_t)(3 * nbv + nbt));
-  std::vector<long>& off = c->off;                           // (read by a copy that is still in flight on return)
-  off.assign((size_t)(nbv + nbt), 0);
-  ER_W(who, hipMemcpyAsync(blk.data(), d_blk, blk.size() * sizeof(long), hipMemcpyDeviceToHost, s));
+  if (lists.read_counts(who, s)) return 1;
   ER_W(who, hipStreamSynchronize(s));
-  long nvk = 0, ntk = 0, found = 0, kept = 0;
-  for (long b = 0; b < nbv; b++) {
-    off[(size_t)b] = nvk;
-    nvk += blk[(size_t)(3 * b)];
-    found += blk[(size_t)(3 * b + 1)];
-    kept += blk[(size_t)(3 * b + 2)];
-  }
-  for (long b = 0; b < nbt; b++) {
-    off[(size_t)(nbv + b)] = ntk;
-    ntk += blk[(size_t)(3 * nbv + b)];
-  }
+  lists.prefix();
+  const long nvk = lists.total(lv), ntk = lists.total(lt);
   c->nv = nvk;
   c->ntri = ntk;
-  c->stats[0] = found;
-  c->stats[1] = kept;
+  c->stats[0] = lists.total(lv, 1);                          // roots
+  c->stats[1] = lists.total(lv, 2);                          // kept roots
   c->stats[2] = nv - nvk;
   c->stats[3] = nt - ntk;
   if (counted(*c)) return 1;
   if (nvk == 0 || (!want_rows && !want_t)) return 0;
 
   // the second passes
-  ER_W(who, hipMemcpyAsync(d_ov, off.data(), off.size() * sizeof(long), hipMemcpyHostToDevice, s));
+  if (lists.upload_offsets(who, s)) return 1;
   if (m.owned.alloc(&d_remap, (size_t)nv, who)) return 1;
   if (m.owned.alloc(&d_index, (size_t)nvk, who)) return 1;
   if (m.d_verts && m.owned.alloc(&d_verts_out, (size_t)nvk, who)) return 1;

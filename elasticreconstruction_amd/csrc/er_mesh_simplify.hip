@@ -12,7 +12,7 @@
 //     mostly share a cell, so a wave first adds up its runs of equal lead (a segmented scan) and sends one add per run and word.
 //   - Duplicate triangles meet in a second table of the same kind, keyed by the canonical rotation of the triple of leads and holding the
 //     lowest TRIANGLE INDEX.
-//   - Vertices and triangles are compacted in two passes with the host's prefix over the block counts between them, as in er_mesh_cc.hip.
+//   - Vertices and triangles are compacted in two passes with the host's prefix over the block counts between them (er_compact.h).
 #include "er_mesh.h"
 #include "er_mesh_simplify_math.h"
 
@@ -215,16 +215,15 @@ __global__ __launch_bounds__(kScBlock) void k_st_insert(const int* __restrict__ 
   sc_report(probes, placed, active, diag, D_PROBE_T);
 }
 
-// Triangles, two passes.  A triangle is kept iff it is not degenerate and its slot holds its own index.  pass 0: used[L] = 1 for the leads a kept
+// Triangles, the two passes of er_compact.h.  A triangle is kept iff it is not degenerate and its slot holds its own index.  pass 0: used[L] = 1 for the leads a kept
 // triangle names, blk[2 b ..] = kept and degenerate triangles of block b.  pass 1: behind the host's prefix (off[b]) the kept triangles in their
 // order, with their own rotation: out = the ranks of their clusters, index_out = their input index.
 __global__ __launch_bounds__(kScBlock) void k_st_compact(const int* __restrict__ tri, long nt, const int* __restrict__ lead, const int* __restrict__ table,
                                                          const unsigned* __restrict__ slot, int* __restrict__ used, long* __restrict__ blk,
                                                          const long* __restrict__ off, int pass, const int* __restrict__ rank, int* __restrict__ out,
                                                          int* __restrict__ index_out) {
-  __shared__ int s_keep[kScBlock / 64], s_deg[kScBlock / 64];
+  __shared__ int s_tally[2][kScBlock / 64];
   const long t = (long)blockIdx.x * kScBlock + threadIdx.x;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   int A = 0, B = 0, C = 0;
   bool keep = false, deg = false;
   if (t < nt) {
@@ -234,28 +233,14 @@ __global__ __launch_bounds__(kScBlock) void k_st_compact(const int* __restrict__
     deg = A == B || B == C || A == C;
     keep = !deg && table[slot[t]] == (int)t;
   }
-  const unsigned long long bk = __ballot(keep), bd = __ballot(deg);
-  if (lane == 0) {
-    s_keep[w] = __popcll(bk);
-    s_deg[w] = __popcll(bd);
-  }
-  __syncthreads();
+  const BlockTally<kScBlock, 2> tally(s_tally, {keep, deg});
   if (!pass) {
     if (keep) used[A] = used[B] = used[C] = 1;
-    if (threadIdx.x == 0) {
-      long k = 0, d = 0;
-      for (int q = 0; q < kScBlock / 64; q++) {
-        k += s_keep[q];
-        d += s_deg[q];
-      }
-      blk[2 * (long)blockIdx.x] = k;
-      blk[2 * (long)blockIdx.x + 1] = d;
-    }
+    tally.block_totals(blk);
     return;
   }
   if (!keep) return;
-  long o = off[blockIdx.x] + __popcll(bk & ((1ull << lane) - 1ull));
-  for (int q = 0; q < w; q++) o += s_keep[q];
+  const long o = tally.rank_in_block(off[blockIdx.x]);
   if (out) {
     out[3 * o] = rank[A];
     out[3 * o + 1] = rank[B];
@@ -264,7 +249,7 @@ __global__ __launch_bounds__(kScBlock) void k_st_compact(const int* __restrict__
   if (index_out) index_out[o] = (int)t;
 }
 
-// Vertices, two passes.  A cluster is an output vertex iff a kept triangle names it; it is counted and written by its lead, so the output is in
+// Vertices, the same two passes.  A cluster is an output vertex iff a kept triangle names it; it is counted and written by its lead, so the output is in
 // ascending order of lead.  pass 0: blk[2 b ..] = output vertices and leads (= occupied cells) of block b.  pass 1: rank[v] = the output index
 // of the cluster v leads, or -1 (also for every v that leads nothing), and the finished rows where their arrays exist.
 __global__ __launch_bounds__(kScBlock) void k_sv_compact(const int* __restrict__ lead, const int* __restrict__ used, long nv, long* __restrict__ blk,
@@ -272,35 +257,20 @@ __global__ __launch_bounds__(kScBlock) void k_sv_compact(const int* __restrict__
                                                          const unsigned long long* __restrict__ pos, const unsigned long long* __restrict__ nsum,
                                                          const unsigned long long* __restrict__ csum, float4* __restrict__ verts_out,
                                                          float4* __restrict__ nrm_out, uchar4* __restrict__ rgba_out, int* __restrict__ members_out) {
-  __shared__ int s_keep[kScBlock / 64], s_lead[kScBlock / 64];
+  __shared__ int s_tally[2][kScBlock / 64];
   const long v = (long)blockIdx.x * kScBlock + threadIdx.x;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   bool keep = false, leads = false;
   if (v < nv) {
     leads = lead[v] == (int)v;
     keep = leads && used[v] != 0;
   }
-  const unsigned long long bk = __ballot(keep), bl = __ballot(leads);
-  if (lane == 0) {
-    s_keep[w] = __popcll(bk);
-    s_lead[w] = __popcll(bl);
-  }
-  __syncthreads();
+  const BlockTally<kScBlock, 2> tally(s_tally, {keep, leads});
   if (!pass) {
-    if (threadIdx.x == 0) {
-      long k = 0, l = 0;
-      for (int q = 0; q < kScBlock / 64; q++) {
-        k += s_keep[q];
-        l += s_lead[q];
-      }
-      blk[2 * (long)blockIdx.x] = k;
-      blk[2 * (long)blockIdx.x + 1] = l;
-    }
+    tally.block_totals(blk);
     return;
   }
   if (v >= nv) return;
-  long o = off[blockIdx.x] + __popcll(bk & ((1ull << lane) - 1ull));
-  for (int q = 0; q < w; q++) o += s_keep[q];
+  const long o = tally.rank_in_block(off[blockIdx.x]);
   rank[v] = keep ? (int)o : -1;
   if (!keep) return;
   const long long n = (long long)pos[4 * v + 3];
@@ -350,7 +320,7 @@ struct ScMesh {
   float4 *d_verts = nullptr, *d_nrm = nullptr;
   uchar4* d_rgba = nullptr;
   int *d_members = nullptr, *d_tri = nullptr, *d_tri_index = nullptr, *d_cluster = nullptr;
-  std::vector<long> off;                                       // the host's block offsets: a copy enqueued on the stream reads them
+  TwoPass lists;                                               // the vertex and the triangle list between their passes
 };
 
 // The clustering of nv > 0 vertices (d_nrm, d_rgba nullable) and nt > 0 triangles in device memory, on stream s, which it synchronises twice.
@@ -393,7 +363,8 @@ int simplify_on_device(const char* who, hipStream_t s, const float4* d_verts, co
   int *d_vtable = nullptr, *d_ttable = nullptr, *d_lead = nullptr, *d_used = nullptr, *d_rank = nullptr;
   unsigned *d_vslot = nullptr, *d_tslot = nullptr;
   unsigned long long *d_pos = nullptr, *d_nsum = nullptr, *d_csum = nullptr;
-  long* d_blk = nullptr;                                       // [2 nbv] vertex counts, [2 nbt] triangle counts, then [nbv] and [nbt] offsets
+  TwoPass& lists = out->lists;
+  const int lv = lists.add(nbv, 2), lt = lists.add(nbt, 2);
   if (owned.alloc(&d_vtable, vsize, who)) return 1;
   if (owned.alloc(&d_ttable, tsize, who)) return 1;
   if (owned.alloc(&d_vslot, (size_t)nv, who)) return 1;
@@ -401,8 +372,7 @@ int simplify_on_device(const char* who, hipStream_t s, const float4* d_verts, co
   if (owned.alloc(&d_lead, (size_t)nv, who)) return 1;
   if (owned.alloc(&d_used, (size_t)nv, who)) return 1;
   if (owned.alloc(&d_pos, (size_t)nv * 4, who)) return 1;
-  if (owned.alloc(&d_blk, (size_t)(3 * nbv + 3 * nbt), who)) return 1;
-  long *d_bt = d_blk + 2 * nbv, *d_ov = d_bt + 2 * nbt, *d_ot = d_ov + nbv;
+  if (lists.alloc(owned, who)) return 1;
   ER_W(who, hipMemsetAsync(d_vtable, 0xFF, vsize * sizeof(int), s));
   ER_W(who, hipMemsetAsync(d_ttable, 0xFF, tsize * sizeof(int), s));
   ER_W(who, hipMemsetAsync(d_vslot, 0, (size_t)nv * sizeof(unsigned), s));   // (a slot that an overflowing table leaves unset is still an address)
@@ -427,37 +397,25 @@ int simplify_on_device(const char* who, hipStream_t s, const float4* d_verts, co
   uchar4* d_rgba_out = nullptr;
   int *d_members = nullptr, *d_tri_out = nullptr, *d_tri_index = nullptr;
   auto triangles = [&](int pass) {
-    hipLaunchKernelGGL(k_st_compact, dim3((unsigned)nbt), dim3(kScBlock), 0, s, d_tri, nt, d_lead, d_ttable, d_tslot, d_used, d_bt, d_ot, pass, d_rank, d_tri_out,
-                       d_tri_index);
+    hipLaunchKernelGGL(k_st_compact, dim3((unsigned)nbt), dim3(kScBlock), 0, s, d_tri, nt, d_lead, d_ttable, d_tslot, d_used, lists.blk(lt), lists.off(lt), pass, d_rank,
+                       d_tri_out, d_tri_index);
     ER_W(who, hipGetLastError());
     return 0;
   };
   auto vertices = [&](int pass) {
-    hipLaunchKernelGGL(k_sv_compact, dim3((unsigned)nbv), dim3(kScBlock), 0, s, d_lead, d_used, nv, d_blk, d_ov, pass, d_rank, d_pos, d_nsum, d_csum, d_verts_out,
-                       d_nrm_out, d_rgba_out, d_members);
+    hipLaunchKernelGGL(k_sv_compact, dim3((unsigned)nbv), dim3(kScBlock), 0, s, d_lead, d_used, nv, lists.blk(lv), lists.off(lv), pass, d_rank, d_pos, d_nsum, d_csum,
+                       d_verts_out, d_nrm_out, d_rgba_out, d_members);
     ER_W(who, hipGetLastError());
     return 0;
   };
   if (triangles(0) || vertices(0)) return 1;
-  std::vector<long> blk((size_t)(2 * nbv + 2 * nbt));
-  std::vector<long>& off = out->off;
-  off.assign((size_t)(nbv + nbt), 0);
   int diag[D_COUNT] = {0, 0, 0, 0};
-  ER_W(who, hipMemcpyAsync(blk.data(), d_blk, blk.size() * sizeof(long), hipMemcpyDeviceToHost, s));
+  if (lists.read_counts(who, s)) return 1;
   ER_W(who, hipMemcpyAsync(diag, d_diag, sizeof diag, hipMemcpyDeviceToHost, s));
   ER_W(who, hipStreamSynchronize(s));
   if (diag[D_FULL]) return er::fail("%s: a probe sequence ran through its whole table (%lu and %lu slots)", who, vsize, tsize);
-  long nvk = 0, ntk = 0, cells = 0, degenerate = 0;
-  for (long b = 0; b < nbv; b++) {
-    off[(size_t)b] = nvk;
-    nvk += blk[(size_t)(2 * b)];
-    cells += blk[(size_t)(2 * b + 1)];
-  }
-  for (long b = 0; b < nbt; b++) {
-    off[(size_t)(nbv + b)] = ntk;
-    ntk += blk[(size_t)(2 * nbv + 2 * b)];
-    degenerate += blk[(size_t)(2 * nbv + 2 * b + 1)];
-  }
+  lists.prefix();
+  const long nvk = lists.total(lv), ntk = lists.total(lt), cells = lists.total(lv, 1), degenerate = lists.total(lt, 1);
   out->nv = nvk;
   out->ntri = ntk;
   out->stats[0] = cells;
@@ -470,7 +428,7 @@ int simplify_on_device(const char* who, hipStream_t s, const float4* d_verts, co
   if (!want.any()) return 0;
 
   // the second passes
-  ER_W(who, hipMemcpyAsync(d_ov, off.data(), off.size() * sizeof(long), hipMemcpyHostToDevice, s));
+  if (lists.upload_offsets(who, s)) return 1;
   if (owned.alloc(&d_rank, (size_t)nv, who)) return 1;
   if (nvk > 0) {
     if (want.verts && owned.alloc(&d_verts_out, (size_t)nvk, who)) return 1;
@@ -544,6 +502,7 @@ int er_mesh_simplify(const float* verts_host, const float* normals_host, const u
   }
   ER_HIP_TRY(hipSetDevice(device));
   hipStream_t s = nullptr;                                     // (the null stream: the call is synchronous)
+  ScMesh r;                                                    // (before own: its lists outlive the copies that own's hipFree waits for)
   er::DevScope own;
   float4 *d_verts = nullptr, *d_nrm = nullptr;
   uchar4* d_rgba = nullptr;
@@ -573,7 +532,6 @@ int er_mesh_simplify(const float* verts_host, const float* normals_host, const u
       return er::fail("er_mesh_simplify: capacity %ld < %ld triangles", capacity_triangles, r.ntri);
     return 0;
   };
-  ScMesh r;
   if (simplify_on_device(who, s, d_verts, d_nrm, d_rgba, nv, d_tri, nt, cell, want, counted, own, &r)) return 1;
   return sc_copy_back(who, s, r, nv, verts_out, normals_out, colors_out, members_out, tri_out, tri_index_out, cluster_out);
 }
@@ -598,8 +556,9 @@ int er_tsdf_extract_mesh_simplified(er_tsdf_t h, float cell, long min_triangles,
   hipStream_t s = h->stream;
 
   // the unsimplified mesh, cleaned where that is asked for: it stays in device memory
-  DeviceMesh m;
+  ScMesh r;                                                    // (r and c before m: their lists outlive the copies that m's hipFree waits for)
   CleanedMesh c;
+  DeviceMesh m;
   const float4 *d_verts = nullptr, *d_nrm = nullptr;
   const int* d_tri = nullptr;
   long nv = 0, nt = 0;
@@ -643,7 +602,6 @@ int er_tsdf_extract_mesh_simplified(er_tsdf_t h, float cell, long min_triangles,
       return er::fail("er_tsdf_extract_mesh_simplified: capacity %ld < %ld triangles", capacity_triangles, r.ntri);
     return 0;
   };
-  ScMesh r;
   if (simplify_on_device(who, s, d_verts, d_nrm, d_rgba, nv, d_tri, nt, cell, want, counted, m.owned, &r)) return 1;
   return sc_copy_back(who, s, r, nv, verts_host, normals_host, colors_host, members_host, tri_host, nullptr, nullptr);
 }

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "er_common.h"
+#include "er_compact.h"
 #include "er_mem.h"
 #include "er_tsdf_math.h"
 
@@ -241,6 +242,7 @@ struct DeviceMesh {
   long nv = 0, ntri = 0;
   float4 *d_verts = nullptr, *d_nrm = nullptr;
   int* d_tri = nullptr;
+  TwoPass lists;                           // the triangle and the vertex slabs between their passes (er_compact.h); outlives `owned`
   DevScope owned;
 };
 // Lists the units (*n_vertices = *n_triangles = 0 from then on), counts the mesh of the resident volume, sets the two counts, calls

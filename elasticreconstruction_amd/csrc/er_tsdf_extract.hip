@@ -32,7 +32,7 @@ __global__ __launch_bounds__(64) void k_world(const float2* __restrict__ pool, c
     const bool keep = world_keep(v);
     const unsigned long long b = __ballot(keep);
     if (pass && keep) {
-      const long o = base + total + __popcll(b & ((1ull << lane) - 1ull));
+      const long o = base + total + wave_rank(b, lane);
       out[o] = make_float4((float)(i + (xi - 256) * 64), (float)(j + (yi - 256) * 64), (float)(lane + (zi - 256) * 64), v.x);
     }
     total += __popcll(b);
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void k_surface_normals(const float2* __restric
 
 // The rows CCorresApp::LoadData keeps (CorresApp.cpp:93-98: normal_x is not NaN) that also lie in the fragment's cube 0 <= x, y, z < cube
 // (PointCloud::GetCoordinate; cube <= 0: no cube test), compacted in order into packed xyz / normal rows -- er_cloud_create's input layout.
-// One wave per 64 rows, two passes (count, then write at the block's offset) like the extraction kernels.
+// One wave per 64 rows -- a block of one wave, so its ballot is the block's tally -- in the two passes of er_compact.h.
 __global__ __launch_bounds__(64) void k_oriented_keep(const float4* __restrict__ pts, const float4* __restrict__ nrm, long n, float cube,
                                                       long* __restrict__ blk_count, const long* __restrict__ blk_offset,
                                                       float* __restrict__ xyz_out, float* __restrict__ nrm_out, int pass) {
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(64) void k_oriented_keep(const float4* __restrict__
     return;
   }
   if (keep) {
-    const size_t o = (size_t)(blk_offset[blockIdx.x] + __popcll(b & ((1ull << lane) - 1ull))) * 3;
+    const size_t o = (size_t)(blk_offset[blockIdx.x] + wave_rank(b, lane)) * 3;
     xyz_out[o] = p.x;
     xyz_out[o + 1] = p.y;
     xyz_out[o + 2] = p.z;
@@ -558,48 +558,41 @@ __global__ __launch_bounds__(256) void k_import_world(float2* __restrict__ pool,
 
 // The first of the two passes of one extraction call over the device temporaries of that call: they live in `scope`, the call's own (freed when
 // the call leaves, whichever way) or the one of the DeviceMesh that the call fills, and so does what the caller adds (its output, a table).
-// d_keys / d_slots: the units in ascending key order; d_cnt / d_off: per slab (64 per unit) what the count pass found and where the write
-// pass starts.
+// d_keys / d_slots: the units in ascending key order; cnt() / off(): per slab (64 per unit, one block each) what the count pass found and where
+// the write pass starts -- a list of `lists` (er_compact.h), which lives with the scope.  A call with n_lists = 2 compacts a second list over
+// the same slabs (the indexed mesh's vertices), counted and uploaded with the first.
 struct SlabPass {
   DevScope& scope;
+  TwoPass& lists;
   int n = 0, nslab = 0;
   int *d_keys = nullptr, *d_slots = nullptr;
-  long *d_cnt = nullptr, *d_off = nullptr;
-  std::vector<long> off;                       // the offsets on the host (count)
 
-  explicit SlabPass(DevScope& s) : scope(s) {}
+  SlabPass(DevScope& s, TwoPass& l) : scope(s), lists(l) {}
+  long* cnt(int list = 0) const { return lists.blk(list); }
+  const long* off(int list = 0) const { return lists.off(list); }
 
-  int alloc(const char* who, int n_units) {
+  int alloc(const char* who, int n_units, int n_lists = 1) {
     n = n_units;
     nslab = n * 64;
-    return scope.alloc(&d_keys, (size_t)n, who) || scope.alloc(&d_slots, (size_t)n, who) || scope.alloc(&d_cnt, (size_t)nslab, who) ||
-           scope.alloc(&d_off, (size_t)nslab, who);
+    for (int l = 0; l < n_lists; l++) lists.add(nslab, 1);
+    return scope.alloc(&d_keys, (size_t)n, who) || scope.alloc(&d_slots, (size_t)n, who) || lists.alloc(scope, who);
   }
 
   // Uploads the unit list, runs the caller's count launch (-> 0, or non-zero after reporting its failure), reads the slab counts back and
-  // sums them on the host: -> *total, and `off` for upload_offsets.  Synchronises h->stream.
+  // sums them on the host: -> *total (and lists.total(1)).  Synchronises h->stream.
   template <typename Launch>
   int count(er_tsdf_t h, const char* who, const std::vector<int>& keys, const std::vector<int>& slots, Launch count_launch, long* total) {
-    std::vector<long> cnt((size_t)nslab);
     ER_W(who, hipMemcpyAsync(d_keys, keys.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
     ER_W(who, hipMemcpyAsync(d_slots, slots.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    if (count_launch()) return 1;
-    ER_W(who, hipMemcpyAsync(cnt.data(), d_cnt, (size_t)nslab * sizeof(long), hipMemcpyDeviceToHost, h->stream));
+    if (count_launch() || lists.read_counts(who, h->stream)) return 1;
     ER_W(who, hipStreamSynchronize(h->stream));
-    off.resize((size_t)nslab);
-    *total = 0;
-    for (int s = 0; s < nslab; s++) {
-      off[(size_t)s] = *total;
-      *total += cnt[(size_t)s];
-    }
+    lists.prefix();
+    *total = lists.total(0);
     return 0;
   }
 
   // (only once the caller knows that there is something to write and room for it, behind the allocation of its output)
-  int upload_offsets(er_tsdf_t h, const char* who) {
-    ER_W(who, hipMemcpyAsync(d_off, off.data(), (size_t)nslab * sizeof(long), hipMemcpyHostToDevice, h->stream));
-    return 0;
-  }
+  int upload_offsets(er_tsdf_t h, const char* who) { return lists.upload_offsets(who, h->stream); }
 };
 
 int extract_points(er_tsdf_t h, float* out_host, long capacity, long* count, int surface) {
@@ -612,16 +605,17 @@ int extract_points(er_tsdf_t h, float* out_host, long capacity, long* count, int
   *count = 0;
   if (n == 0) return 0;
   const int nslab = n * 64;
+  TwoPass lists;                               // (in this frame, outliving `own`: the call synchronises before it returns)
   DevScope own;
-  SlabPass t(own);
+  SlabPass t(own, lists);
   float4* d_out = nullptr;
   long total = 0;
   auto launch = [&](float4* out, int pass) {
     if (surface)
       hipLaunchKernelGGL(k_surface, dim3(nslab), dim3(64), 0, h->stream, h->pool, t.d_slots, t.d_keys, h->ht_key, h->ht_slot, h->ht_cap - 1, h->ht_shift,
-                         t.d_cnt, t.d_off, out, pass);
+                         t.cnt(), t.off(), out, pass);
     else
-      hipLaunchKernelGGL(k_world, dim3(nslab), dim3(64), 0, h->stream, h->pool, t.d_slots, t.d_keys, t.d_cnt, t.d_off, out, pass);
+      hipLaunchKernelGGL(k_world, dim3(nslab), dim3(64), 0, h->stream, h->pool, t.d_slots, t.d_keys, t.cnt(), t.off(), out, pass);
     ER_W(who, hipGetLastError());
     return 0;
   };
@@ -650,7 +644,7 @@ int oriented_on_device(er_tsdf_t h, const char* who, bool want, SlabPass& t, flo
   long total = 0;
   auto launch = [&](float4* out, int pass) {
     hipLaunchKernelGGL(k_surface, dim3(nslab), dim3(64), 0, h->stream, h->pool, t.d_slots, t.d_keys, h->ht_key, h->ht_slot, h->ht_cap - 1, h->ht_shift,
-                       t.d_cnt, t.d_off, out, pass);
+                       t.cnt(), t.off(), out, pass);
     ER_W(who, hipGetLastError());
     return 0;
   };
@@ -682,8 +676,9 @@ int er_tsdf_extract_oriented(er_tsdf_t h, float* points_host, float* normals_hos
   if (!h || !count) return er::fail("er_tsdf_extract_oriented: NULL argument");
   ER_HIP_TRY(hipSetDevice(h->device));
   const bool want = points_host && normals_host;
+  TwoPass lists;                               // (in this frame, outliving `own`: the call synchronises before it returns)
   DevScope own;
-  SlabPass t(own);
+  SlabPass t(own, lists);
   float4 *d_pts = nullptr, *d_nrm = nullptr;
   *count = 0;
   if (oriented_on_device(h, "er_tsdf_extract_oriented", want, t, &d_pts, &d_nrm, count)) return 1;
@@ -708,34 +703,32 @@ int er_cloud_create_from_tsdf(er_tsdf_t h, float cube_length, float grid_cell, e
   if (n_points) *n_points = 0;
   if (!(grid_cell > 0.f)) return er::fail("er_cloud_create_from_tsdf: grid_cell must be positive");
   ER_HIP_TRY(hipSetDevice(h->device));
+  TwoPass lists, rows;                         // the slabs of the oriented list, then its rows (in this frame, outliving `own`: as above)
   DevScope own;
-  SlabPass t(own);
+  SlabPass t(own, lists);
   float4 *d_pts = nullptr, *d_nrm = nullptr;
   long total = 0, kept = 0;
   if (oriented_on_device(h, who, true, t, &d_pts, &d_nrm, &total)) return 1;
-  long* d_blk = nullptr;          // [2 nblk]: counts, then offsets
   float* d_rows = nullptr;        // [kept][3] coordinates, then [kept][3] normals
   const long nblk = (total + 63) / 64;
-  std::vector<long> blk((size_t)nblk * 2);
   if (total > 0) {
-    if (t.scope.alloc(&d_blk, (size_t)nblk * 2, who)) return 1;
-    hipLaunchKernelGGL(k_oriented_keep, dim3((unsigned)nblk), dim3(64), 0, h->stream, d_pts, d_nrm, total, cube_length, d_blk, d_blk + nblk,
-                       (float*)nullptr, (float*)nullptr, 0);
-    ER_W(who, hipGetLastError());
-    ER_W(who, hipMemcpyAsync(blk.data(), d_blk, (size_t)nblk * sizeof(long), hipMemcpyDeviceToHost, h->stream));
+    const int lk = rows.add(nblk, 1);
+    if (rows.alloc(t.scope, who)) return 1;
+    auto keep = [&](int pass) {
+      hipLaunchKernelGGL(k_oriented_keep, dim3((unsigned)nblk), dim3(64), 0, h->stream, d_pts, d_nrm, total, cube_length, rows.blk(lk), rows.off(lk),
+                         d_rows, d_rows + (size_t)kept * 3, pass);
+      ER_W(who, hipGetLastError());
+      return 0;
+    };
+    if (keep(0) || rows.read_counts(who, h->stream)) return 1;
     ER_W(who, hipStreamSynchronize(h->stream));
-    for (long b = 0; b < nblk; b++) {
-      blk[(size_t)(nblk + b)] = kept;
-      kept += blk[(size_t)b];
-    }
+    rows.prefix();
+    kept = rows.total(lk);
     if (kept >= (1L << 27))
       return er::fail("er_cloud_create_from_tsdf: %ld points; the limit is 2^27 - 1 (32-bit byte offsets in the search kernels)", kept);
     if (kept > 0) {
       if (t.scope.alloc(&d_rows, (size_t)kept * 6, who)) return 1;
-      ER_W(who, hipMemcpyAsync(d_blk + nblk, blk.data() + nblk, (size_t)nblk * sizeof(long), hipMemcpyHostToDevice, h->stream));
-      hipLaunchKernelGGL(k_oriented_keep, dim3((unsigned)nblk), dim3(64), 0, h->stream, d_pts, d_nrm, total, cube_length, d_blk, d_blk + nblk,
-                         d_rows, d_rows + (size_t)kept * 3, 1);
-      ER_W(who, hipGetLastError());
+      if (rows.upload_offsets(who, h->stream) || keep(1)) return 1;
       ER_W(who, hipStreamSynchronize(h->stream));     // the cloud builder works on streams of its own: the rows are complete before it starts
     }
   }
@@ -760,14 +753,15 @@ int er_tsdf_extract_mesh(er_tsdf_t h, float* tri_host, long capacity_triangles, 
   *n_triangles = 0;
   if (n == 0) return 0;
   const int nslab = n * 64;
+  TwoPass lists;                               // (in this frame, outliving `own`: the call synchronises before it returns)
   DevScope own;
-  SlabPass t(own);
+  SlabPass t(own, lists);
   unsigned char* d_tab = nullptr;
   float* d_out = nullptr;
   long total = 0;
   auto launch = [&](float* out, int pass) {
     hipLaunchKernelGGL(k_mesh, dim3(nslab), dim3(64), 0, h->stream, h->pool, t.d_slots, t.d_keys, h->ht_key, h->ht_slot, h->ht_cap - 1, h->ht_shift, d_tab,
-                       t.d_cnt, t.d_off, out, pass);
+                       t.cnt(), t.off(), out, pass);
     ER_W(who, hipGetLastError());
     return 0;
   };
@@ -823,54 +817,44 @@ int er_tsdf_k::mesh_indexed_on_device(er_tsdf_t h, const char* who, bool want_v,
   if (n == 0) return 0;                                     // (an empty volume: 0 and 0)
   const int nslab = n * 64;
   const size_t nrow = (size_t)nslab * 64;
-  SlabPass t(m->owned);                   // every temporary belongs to the caller's mesh: the kernels that read them are in flight on return
+  SlabPass t(m->owned, m->lists);         // every temporary belongs to the caller's mesh: the kernels that read them are in flight on return
   unsigned char* d_tab = nullptr;
   unsigned long long* d_bm = nullptr;     // [row][axis]: the edge bitmap
   int *d_rank = nullptr, *d_rowoff = nullptr;
-  long *d_vcnt = nullptr, *d_voff = nullptr;
   std::vector<int> rank((size_t)h->max_units, -1);           // pool slot -> position in the key order; -1: a dropped unit's slot
   for (int r = 0; r < n; r++) rank[(size_t)slots[(size_t)r]] = r;
   long ntri = 0, nv = 0;
   auto launch = [&](int* out, int pass) {
     hipLaunchKernelGGL(k_mesh_index, dim3(nslab), dim3(64), 0, h->stream, h->pool, t.d_slots, t.d_keys, h->ht_key, h->ht_slot, h->ht_cap - 1, h->ht_shift,
-                       d_tab, d_rank, d_bm, d_rowoff, d_voff, t.d_cnt, t.d_off, out, pass);
+                       d_tab, d_rank, d_bm, d_rowoff, t.off(1), t.cnt(), t.off(), out, pass);
     ER_W(who, hipGetLastError());
     return 0;
   };
-  if (t.alloc(who, n)) return 1;
+  if (t.alloc(who, n, 2)) return 1;                          // (the second list: the vertices of a slab)
   if (t.scope.alloc(&d_tab, 256 * 16, who)) return 1;
   if (t.scope.alloc(&d_bm, nrow * 3, who)) return 1;
   if (t.scope.alloc(&d_rank, rank.size(), who)) return 1;
   if (t.scope.alloc(&d_rowoff, nrow, who)) return 1;
-  if (t.scope.alloc(&d_vcnt, (size_t)nslab, who)) return 1;
-  if (t.scope.alloc(&d_voff, (size_t)nslab, who)) return 1;
   auto count_launch = [&] {
     ER_W(who, hipMemcpyAsync(d_tab, er::mc_table().tri, 256 * 16, hipMemcpyHostToDevice, h->stream));
     ER_W(who, hipMemcpyAsync(d_rank, rank.data(), rank.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
     ER_W(who, hipMemsetAsync(d_bm, 0, nrow * 3 * sizeof(unsigned long long), h->stream));
     if (launch(nullptr, 0)) return 1;                        // marks the bitmap, counts the triangles
-    hipLaunchKernelGGL(k_mesh_rows, dim3(nslab), dim3(64), 0, h->stream, d_bm, d_rowoff, d_vcnt);
+    hipLaunchKernelGGL(k_mesh_rows, dim3(nslab), dim3(64), 0, h->stream, d_bm, d_rowoff, t.cnt(1));
     ER_W(who, hipGetLastError());
     return 0;
   };
   if (t.count(h, who, keys, slots, count_launch, &ntri)) return 1;
-  std::vector<long> vcnt((size_t)nslab);
-  ER_W(who, hipMemcpyAsync(vcnt.data(), d_vcnt, (size_t)nslab * sizeof(long), hipMemcpyDeviceToHost, h->stream));
-  ER_W(who, hipStreamSynchronize(h->stream));
-  for (int s = 0; s < nslab; s++) {
-    const long c = vcnt[(size_t)s];
-    vcnt[(size_t)s] = nv;                                    // (now the slab's offset)
-    nv += c;
-  }
+  nv = t.lists.total(1);
   *n_vertices = m->nv = nv;
   *n_triangles = m->ntri = ntri;
   if (counted(nv, ntri)) return 1;
   if (nv == 0 || (!want_v && !want_t)) return 0;
-  ER_W(who, hipMemcpyAsync(d_voff, vcnt.data(), (size_t)nslab * sizeof(long), hipMemcpyHostToDevice, h->stream));
+  if (t.upload_offsets(h, who)) return 1;                    // (of both lists)
   if (want_v) {
     if (t.scope.alloc(&m->d_verts, (size_t)nv, who)) return 1;
     hipLaunchKernelGGL(k_mesh_verts, dim3(nslab), dim3(64), 0, h->stream, h->pool, t.d_slots, t.d_keys, h->ht_key, h->ht_slot, h->ht_cap - 1, h->ht_shift,
-                       d_bm, d_rowoff, d_voff, m->d_verts);
+                       d_bm, d_rowoff, t.off(1), m->d_verts);
     ER_W(who, hipGetLastError());
     if (want_n) {
       if (t.scope.alloc(&m->d_nrm, (size_t)nv, who)) return 1;
@@ -881,7 +865,7 @@ int er_tsdf_k::mesh_indexed_on_device(er_tsdf_t h, const char* who, bool want_v,
   }
   if (want_t) {
     if (t.scope.alloc(&m->d_tri, (size_t)ntri * 3, who)) return 1;
-    if (t.upload_offsets(h, who) || launch(m->d_tri, 1)) return 1;
+    if (launch(m->d_tri, 1)) return 1;
   }
   return 0;                                                  // (the kernels are still in flight on h->stream: what they read or write is m's)
 }
