@@ -15,6 +15,16 @@ namespace er {
 // The set bits of a wave's ballot below `lane`: the rank of this lane's element among those the wave keeps.
 __device__ __forceinline__ int wave_rank(unsigned long long ballot, int lane) { return __popcll(ballot & ((1ull << lane) - 1ull)); }
 
+// x summed over lanes 0 .. lane of the wave (every lane calls it): where a lane keeps a COUNT of elements, not one -- its elements start at this
+// minus its own x, and lane 63 holds the wave's total.
+__device__ __forceinline__ int wave_inclusive_sum(int x, int lane) {
+  for (int sft = 1; sft < 64; sft <<= 1) {
+    const int t = __shfl_up(x, sft);
+    if (lane >= sft) x += t;
+  }
+  return x;
+}
+
 // N predicates per thread of a kBlock-thread block (one element per thread, in thread order), tallied per block: the first is the one that
 // compacts, the others are side tallies that ride along.  EVERY thread of the block reaches the constructor -- it holds the kernel's one
 // __syncthreads() -- so a thread without an element comes with all-false predicates, and the kernel's early returns stand behind it.

@@ -43,6 +43,21 @@ constexpr int kAux = 2;                  // stream = the round-1 pipeline: profi
                                          // batch b runs on stream b mod kAux
 constexpr int kZColor = kAux;            // index of the colour calls' z-buffer counter in er_tsdf_s::zepoch, behind the kAux pre-pass buffers'
 
+// The unit hash map as a kernel that runs when nobody inserts reads it (the extraction kernels, the ray caster, the colour kernels): passed by
+// value, built by er_tsdf_s::view.  slot (er_tsdf_dev.h): the unit's pool slot, -1 = no such unit.
+struct UnitMap {
+  const int* __restrict__ ht_key;
+  const int* __restrict__ ht_slot;
+  int cap_mask, shift;
+  __device__ int slot(int key) const;
+};
+// ... and the sdf pool it indexes: what a reader of {sdf, weight} takes.  (The colour kernels index the accumulators, by the same slots: the map alone.)
+struct VolumeView {
+  const float2* __restrict__ pool;
+  UnitMap map;
+  __device__ const float2* unit(int slot) const { return pool + (size_t)slot * kUnitVox; }
+};
+
 // ------------------------------------------------------------------------------------------------
 // Reproject, IntegrateApp.cpp:247-268: every source pixel is warped through its fragment's control
 // grid and scattered into the frame's z-buffer.  The reference's sequential "write if empty or
@@ -182,6 +197,7 @@ struct er_tsdf_s : er_tsdf_mem {
   hipEvent_t pre_done[er_tsdf_k::kDepth] = {}, int_done[er_tsdf_k::kDepth] = {};
   er::PinnedBuffer<char> pinned[er_tsdf_k::kDepth];                  // host staging of the per-batch constants (struct Staging)
   int ht_cap = 0, ht_shift = 0;
+  er_tsdf_k::VolumeView view() const { return {pool, {ht_key, ht_slot, ht_cap - 1, ht_shift}}; }   // for the kernels that only read the unit table
   float *lambda = nullptr, *ctr = nullptr;
   // The caller's lattices, double-buffered by call parity on the host (page-locked staging) AND on the device, so that the
   // upload of call c (copy stream) never waits for the pre-passes of call c-1 that still read the other buffer.

@@ -31,8 +31,7 @@ constexpr double kLatticeLo = -(256.0 * 64.0), kLatticeHi = 256.0 * 64.0;
 // The exact chain with its six float64 divisions: only the VOXEL index is observable, but nothing has asked for a faster form yet.
 // stats: added, no_unit, out_of_range -- one atomic per wave and counter.
 __global__ __launch_bounds__(kBlock) void k_color_splat(const uint16_t* __restrict__ depth, const uint8_t* __restrict__ rgb, int pixels, int cols,
-                                                        Camera cam, const double* __restrict__ T16, const int* __restrict__ ht_key,
-                                                        const int* __restrict__ ht_slot, int cap_mask, int shift, int max_units,
+                                                        Camera cam, const double* __restrict__ T16, UnitMap map, int max_units,
                                                         unsigned long long* __restrict__ color, unsigned long long* __restrict__ stats) {
   const int p = blockIdx.x * kBlock + threadIdx.x;
   const int f = blockIdx.y;
@@ -54,12 +53,11 @@ __global__ __launch_bounds__(kBlock) void k_color_splat(const uint16_t* __restri
         verdict = 3;
       } else {
         const int a0 = (int)g0 + 256 * 64, a1 = (int)g1 + 256 * 64, a2 = (int)g2 + 256 * 64;      // 0 .. 32767
-        const int key = (a0 >> 6) << 18 | (a1 >> 6) << 9 | (a2 >> 6);                               // key_from_voxels
-        const int slot = ht_lookup_slot(ht_key, ht_slot, cap_mask, shift, key);
+        const int slot = map.slot(unit_key_of(a0, a1, a2));                                         // key_from_voxels
         if ((unsigned)slot >= (unsigned)max_units) {
           verdict = 2;
         } else {
-          const size_t l = (size_t)slot * kUnitVox + (size_t)((a0 & 63) * 4096 + (a1 & 63) * 64 + (a2 & 63));
+          const size_t l = (size_t)slot * kUnitVox + unit_offset_of(a0, a1, a2);
           const uint8_t* c = rgb + o * 3;
           const unsigned long long rg = (unsigned long long)c[0] | (unsigned long long)c[1] << 32;
           const unsigned long long bn = (unsigned long long)c[2] | 1ull << 32;
@@ -81,16 +79,16 @@ __global__ __launch_bounds__(kBlock) void k_color_splat(const uint16_t* __restri
 
 // The accumulators of voxel (gx, gy, gz) of the 0-based lattice added to s[4] (64-bit r, g, b, n); nothing for a voxel off the lattice or in a unit that does
 // not exist.  *key / *slot cache the last unit looked up (a 3 x 3 x 3 neighbourhood spans at most eight).
-__device__ __forceinline__ void color_gather(const unsigned long long* __restrict__ color, const int* __restrict__ ht_key, const int* __restrict__ ht_slot,
-                                             int cap_mask, int shift, int max_units, int gx, int gy, int gz, int* key, int* slot, unsigned long long s[4]) {
-  if ((unsigned)gx >= 512u * 64u || (unsigned)gy >= 512u * 64u || (unsigned)gz >= 512u * 64u) return;
-  const int k = (gx >> 6) << 18 | (gy >> 6) << 9 | (gz >> 6);
+__device__ __forceinline__ void color_gather(const unsigned long long* __restrict__ color, const UnitMap& map, int max_units, int gx, int gy, int gz,
+                                             int* key, int* slot, unsigned long long s[4]) {
+  if (!on_lattice(gx, gy, gz)) return;
+  const int k = unit_key_of(gx, gy, gz);
   if (k != *key) {
     *key = k;
-    *slot = ht_lookup_slot(ht_key, ht_slot, cap_mask, shift, k);
+    *slot = map.slot(k);
   }
   if ((unsigned)*slot >= (unsigned)max_units) return;
-  const size_t l = (size_t)*slot * kUnitVox + (size_t)((gx & 63) * 4096 + (gy & 63) * 64 + (gz & 63));
+  const size_t l = (size_t)*slot * kUnitVox + unit_offset_of(gx, gy, gz);
   const unsigned long long rg = color[2 * l], bn = color[2 * l + 1];
   s[0] += rg & 0xFFFFFFFFull;
   s[1] += rg >> 32;
@@ -102,8 +100,7 @@ __device__ __forceinline__ void color_gather(const unsigned long long* __restric
 // k_surface_normals' nearest voxel.  Level 0: v itself if it has samples; level 1: the 64-bit sums over the 27 voxels v + {-1, 0, 1}^3 that lie
 // on the lattice in existing units, across unit borders.  Channel = (2 sum + n) / (2 n), integer division (round half up), a = 255.
 // No sample, a non-finite coordinate or v off the lattice: 0 0 0 0.  counts: points coloured at level 0 and at level 1.
-__global__ __launch_bounds__(kBlock) void k_color_sample(const unsigned long long* __restrict__ color, const int* __restrict__ ht_key,
-                                                         const int* __restrict__ ht_slot, int cap_mask, int shift, int max_units,
+__global__ __launch_bounds__(kBlock) void k_color_sample(const unsigned long long* __restrict__ color, UnitMap map, int max_units,
                                                          const float4* __restrict__ pts, long n, uchar4* __restrict__ out,
                                                          unsigned long long* __restrict__ counts) {
   const long r = (long)blockIdx.x * kBlock + threadIdx.x;
@@ -116,13 +113,13 @@ __global__ __launch_bounds__(kBlock) void k_color_sample(const unsigned long lon
     if (v0 >= kLatticeLo && v0 < kLatticeHi && v1 >= kLatticeLo && v1 < kLatticeHi && v2 >= kLatticeLo && v2 < kLatticeHi) {
       const int gx = (int)v0 + 256 * 64, gy = (int)v1 + 256 * 64, gz = (int)v2 + 256 * 64;
       int key = -2, slot = -1;
-      color_gather(color, ht_key, ht_slot, cap_mask, shift, max_units, gx, gy, gz, &key, &slot, s);
+      color_gather(color, map, max_units, gx, gy, gz, &key, &slot, s);
       if (s[3] > 0) {
         level = 0;
       } else {
         for (int dx = -1; dx <= 1; dx++)
           for (int dy = -1; dy <= 1; dy++)
-            for (int dz = -1; dz <= 1; dz++) color_gather(color, ht_key, ht_slot, cap_mask, shift, max_units, gx + dx, gy + dy, gz + dz, &key, &slot, s);
+            for (int dz = -1; dz <= 1; dz++) color_gather(color, map, max_units, gx + dx, gy + dy, gz + dz, &key, &slot, s);
         if (s[3] > 0) level = 1;
       }
     }
@@ -275,7 +272,7 @@ int color_run(er_tsdf_t h, const char* who, int n, const uint16_t* depth, const 
     }
     if (!warp) {
       hipLaunchKernelGGL(k_color_splat, dim3(blocks, (unsigned)nb), dim3(kBlock), 0, X, dd, dc, h->pixels, h->cols, h->cam, d_T + (size_t)start * 16,
-                         h->ht_key, h->ht_slot, h->ht_cap - 1, h->ht_shift, h->max_units, h->color, d_stats);
+                         h->view().map, h->max_units, h->color, d_stats);
       ER_HIP_TRY(hipGetLastError());
       continue;
     }
@@ -299,8 +296,8 @@ int color_run(er_tsdf_t h, const char* who, int n, const uint16_t* depth, const 
         ER_HIP_TRY(hipMemcpyAsync(z_host, Z, px * sizeof(uint16_t), hipMemcpyDeviceToHost, X));
         ER_HIP_TRY(hipMemcpyAsync(c_host, Cw, px * 3, hipMemcpyDeviceToHost, X));
       } else {
-        hipLaunchKernelGGL(k_color_splat, dim3(blocks, 1u), dim3(kBlock), 0, X, Z, Cw, h->pixels, h->cols, h->cam, d_T + F * 16, h->ht_key, h->ht_slot,
-                           h->ht_cap - 1, h->ht_shift, h->max_units, h->color, d_stats);
+        hipLaunchKernelGGL(k_color_splat, dim3(blocks, 1u), dim3(kBlock), 0, X, Z, Cw, h->pixels, h->cols, h->cam, d_T + F * 16, h->view().map, h->max_units,
+                           h->color, d_stats);
         ER_HIP_TRY(hipGetLastError());
       }
     }
@@ -332,8 +329,8 @@ int color_sample_on_device(er_tsdf_t h, const char* who, const float4* d_points,
   if (ensure_color_scratch(h, 256)) return 1;                // (the level counts, which nobody reads here)
   unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(h->color_scratch.get());
   ER_HIP_TRY(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), h->stream));
-  hipLaunchKernelGGL(k_color_sample, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, h->color, h->ht_key, h->ht_slot,
-                     h->ht_cap - 1, h->ht_shift, h->max_units, d_points, n, d_rgba, d_counts);
+  hipLaunchKernelGGL(k_color_sample, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, h->color, h->view().map, h->max_units,
+                     d_points, n, d_rgba, d_counts);
   ER_HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -416,8 +413,8 @@ int er_tsdf_sample_colors(er_tsdf_t h, const float* points_host, long n, uint8_t
   unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(S);
   ER_HIP_TRY(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), h->stream));
   ER_HIP_TRY(hipMemcpyAsync(S + off_p, points_host, (size_t)n * 16, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(k_color_sample, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, h->color, h->ht_key, h->ht_slot,
-                     h->ht_cap - 1, h->ht_shift, h->max_units, reinterpret_cast<const float4*>(S + off_p), n, reinterpret_cast<uchar4*>(S + off_o), d_counts);
+  hipLaunchKernelGGL(k_color_sample, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, h->color, h->view().map, h->max_units,
+                     reinterpret_cast<const float4*>(S + off_p), n, reinterpret_cast<uchar4*>(S + off_o), d_counts);
   ER_HIP_TRY(hipGetLastError());
   unsigned long long ct[2] = {0, 0};
   ER_HIP_TRY(hipMemcpyAsync(rgba_host, S + off_o, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));

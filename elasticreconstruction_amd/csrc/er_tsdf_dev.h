@@ -1,11 +1,27 @@
-// er_tsdf_dev.h -- the __device__ helpers of path A that kernels in more than one file use: the unit hash map (er_tsdf.hip, er_tsdf_pre.hip,
-// er_tsdf_extract.hip, er_tsdf_raycast.hip) and the two halves of Reproject's scatter with its replay (er_tsdf.hip, er_tsdf_pre.hip).  Internal linkage: each is
-// compiled where it is used.  A helper with one user sits next to that user.
+// er_tsdf_dev.h -- the __device__ helpers of path A that kernels in more than one file use: the writers' side of the unit hash map (er_tsdf.hip,
+// er_tsdf_pre.hip), the readers' side -- UnitMap::slot and the arithmetic of the voxel lattice (er_tsdf_extract.hip, er_tsdf_raycast.hip,
+// er_tsdf_color.hip) -- and the two halves of Reproject's scatter with its replay (er_tsdf.hip, er_tsdf_pre.hip).  Internal
+// linkage: each is compiled where it is used.  A helper with one user sits next to that user.
 #pragma once
 
 #include "er_tsdf.h"
 
 namespace er_tsdf_k {
+
+// The voxel lattice as a reader addresses it: 512 units of 64 voxels per axis, g = 0-based voxel index on the whole lattice (metres / kUnitLength
+// + 256 * 64).  Host and device: er_tsdf_import_world packs keys too.
+constexpr int kLatticeVox = 512 * 64;
+__host__ __device__ __forceinline__ bool on_lattice(int gx, int gy, int gz) {
+  return (unsigned)gx < (unsigned)kLatticeVox && (unsigned)gy < (unsigned)kLatticeVox && (unsigned)gz < (unsigned)kLatticeVox;
+}
+// the hash_key (TSDFVolume.h:62-64) of the unit that holds voxel g, and the voxel's offset inside that unit
+__host__ __device__ __forceinline__ int unit_key_of(int gx, int gy, int gz) { return (gx >> 6) << 18 | (gy >> 6) << 9 | (gz >> 6); }
+__host__ __device__ __forceinline__ size_t unit_offset_of(int gx, int gy, int gz) {
+  return (size_t)(gx & 63) * 4096 + (size_t)(gy & 63) * 64 + (size_t)(gz & 63);
+}
+// float32 position of voxel a (0 .. 64: one past the end is voxel 0 of the next unit) of unit coordinate u along one axis
+__host__ __device__ __forceinline__ float lattice_pos(int a, int u) { return (float)((double)(a + (u - 256) * 64) * kUnitLength); }
+
 namespace {
 
 __device__ __forceinline__ unsigned hash_unit_key(int key, int shift) { return ((unsigned)key * 2654435761u) >> shift; }
@@ -25,8 +41,11 @@ __device__ int ht_find_or_insert(int* __restrict__ ht_key, int cap_mask, int shi
   return -1;
 }
 
-// Read-only lookup for kernels that run when nobody inserts (the extraction kernels, the ray caster): the unit's pool slot, -1 = no such unit.
-__device__ __forceinline__ int ht_lookup_slot(const int* __restrict__ ht_key, const int* __restrict__ ht_slot, int cap_mask, int shift, int key) {
+}  // namespace
+
+// Read-only lookup for kernels that run when nobody inserts (er_tsdf.h: UnitMap): the unit's pool slot, -1 = no such unit.  What "no unit" means
+// beyond that is the caller's: the extraction kernels test slot < 0, the ray caster and the colour kernels (unsigned)slot >= (unsigned)max_units.
+__device__ __forceinline__ int UnitMap::slot(int key) const {
   unsigned h = hash_unit_key(key, shift);
   for (int probe = 0; probe <= cap_mask; ++probe) {
     const int e = (int)((h + (unsigned)probe) & (unsigned)cap_mask);
@@ -36,6 +55,8 @@ __device__ __forceinline__ int ht_lookup_slot(const int* __restrict__ ht_key, co
   }
   return -1;
 }
+
+namespace {
 
 // The write half of one source pixel p of frame f that landed on `cell` with depth dd (IntegrateApp.cpp:260-263).
 __device__ __forceinline__ void scatter_px(const ReprojArgs& A, int f, int p, int cell, uint16_t dd, int replay) {

@@ -12,6 +12,18 @@ namespace {
 
 using namespace er_tsdf_k;
 
+// The frame of the five kernels that run one wave per (unit, i-slab) -- k_world, k_surface, k_mesh, k_mesh_index, k_mesh_verts: block 64 * rank + i,
+// rank = the unit's place in ascending key order, lane = k; the wave walks the slab's 64 rows j.
+struct Slab {
+  int rank, i, lane, key, xi, yi, zi;
+  __device__ __forceinline__ explicit Slab(const int* __restrict__ keys)
+      : rank(blockIdx.x >> 6), i(blockIdx.x & 63), lane(threadIdx.x), key(keys[rank]), xi(key >> 18), yi((key >> 9) & 511), zi(key & 511) {}
+  // float32 position of the lane's voxel (i, j, k); d = 1: of the voxel one step up that axis
+  __device__ __forceinline__ float x(int d = 0) const { return lattice_pos(i + d, xi); }
+  __device__ __forceinline__ float y(int j) const { return lattice_pos(j, yi); }
+  __device__ __forceinline__ float z(int d = 0) const { return lattice_pos(lane + d, zi); }
+};
+
 // SaveWorld's filter (TSDFVolume.cpp:118).  One wave per (unit, i-slab); pass 0 counts, pass 1 writes
 // the points in i,j,k order at the slab's offset (stable compaction by ballot prefix).
 __device__ __forceinline__ bool world_keep(float2 v) { return v.y != 0.0f && v.x < 0.98f && v.x >= -0.98f; }
@@ -19,12 +31,9 @@ __device__ __forceinline__ bool world_keep(float2 v) { return v.y != 0.0f && v.x
 __global__ __launch_bounds__(64) void k_world(const float2* __restrict__ pool, const int* __restrict__ slots,
                                               const int* __restrict__ keys, long* __restrict__ slab_count,
                                               const long* __restrict__ slab_offset, float4* __restrict__ out, int pass) {
-  const int rank = blockIdx.x >> 6;          // unit in ascending key order
-  const int i = blockIdx.x & 63;
-  const int lane = threadIdx.x;
-  const float2* slab = pool + (size_t)slots[rank] * kUnitVox + (size_t)i * 4096;
-  const int key = keys[rank];
-  const int xi = key >> 18, yi = (key >> 9) & 511, zi = key & 511;
+  const Slab S(keys);
+  const int i = S.i, lane = S.lane;
+  const float2* slab = pool + (size_t)slots[S.rank] * kUnitVox + (size_t)i * 4096;
   long base = pass ? slab_offset[blockIdx.x] : 0;
   long total = 0;
   for (int j = 0; j < 64; j++) {
@@ -33,7 +42,7 @@ __global__ __launch_bounds__(64) void k_world(const float2* __restrict__ pool, c
     const unsigned long long b = __ballot(keep);
     if (pass && keep) {
       const long o = base + total + wave_rank(b, lane);
-      out[o] = make_float4((float)(i + (xi - 256) * 64), (float)(j + (yi - 256) * 64), (float)(lane + (zi - 256) * 64), v.x);
+      out[o] = make_float4((float)(i + (S.xi - 256) * 64), (float)(j + (S.yi - 256) * 64), (float)(lane + (S.zi - 256) * 64), v.x);
     }
     total += __popcll(b);
   }
@@ -52,51 +61,64 @@ __device__ __forceinline__ bool crosses(float2 a, float2 b) {
   return a.y != 0.0f && b.y != 0.0f && ((a.x > 0.0f && b.x < 0.0f) || (a.x < 0.0f && b.x > 0.0f));
 }
 
-__global__ __launch_bounds__(64) void k_surface(const float2* __restrict__ pool, const int* __restrict__ slots, const int* __restrict__ keys,
-                                                const int* __restrict__ ht_key, const int* __restrict__ ht_slot, int cap_mask, int shift,
-                                                long* __restrict__ slab_count, const long* __restrict__ slab_offset,
-                                                float4* __restrict__ out, int pass) {
-  const int rank = blockIdx.x >> 6;          // unit in ascending key order
-  const int i = blockIdx.x & 63;
-  const int lane = threadIdx.x;              // = k
-  const int key = keys[rank];
-  const int xi = key >> 18, yi = (key >> 9) & 511, zi = key & 511;
-  const float2* unit = pool + (size_t)slots[rank] * kUnitVox;
-  const float2* slab = unit + (size_t)i * 4096;
-  // neighbours that live in adjacent units (wave-uniform lookups; -1 = that unit does not exist)
-  const int sx = (i == 63 && xi < 511) ? ht_lookup_slot(ht_key, ht_slot, cap_mask, shift, key + 512 * 512) : -1;
-  const int sy = yi < 511 ? ht_lookup_slot(ht_key, ht_slot, cap_mask, shift, key + 512) : -1;
-  const int sz = zi < 511 ? ht_lookup_slot(ht_key, ht_slot, cap_mask, shift, key + 1) : -1;
-  const float2 none = make_float2(0.0f, 0.0f);
-  const float2* slab_x = i < 63 ? slab + 4096 : (sx >= 0 ? pool + (size_t)sx * kUnitVox : nullptr);              // i + 1 (slab 0 of the next unit)
-  const float2* unit_y = sy >= 0 ? pool + (size_t)sy * kUnitVox + (size_t)i * 4096 : nullptr;                      // j + 1 == 64: row 0 there
-  const float2* unit_z = sz >= 0 ? pool + (size_t)sz * kUnitVox + (size_t)i * 4096 : nullptr;                      // k + 1 == 64: voxel 0 there
-  const float ulf = (float)kUnitLength;
-  const float gx = (float)((double)(i + (xi - 256) * 64) * kUnitLength);
-  const float gz = (float)((double)(lane + (zi - 256) * 64) * kUnitLength);
-  const unsigned long long lt = (1ull << lane) - 1ull;
-  long base = pass ? slab_offset[blockIdx.x] : 0;
-  long total = 0;
-  for (int j = 0; j < 64; j++) {
-    const float2 v = slab[j * 64 + lane];
-    const float2 nx = slab_x ? slab_x[j * 64 + lane] : none;
-    const float2 ny = j < 63 ? slab[(j + 1) * 64 + lane] : (unit_y ? unit_y[lane] : none);
+// A slab's voxels and their +x / +y / +z neighbours, inside the unit or in the adjacent one (wave-uniform look-ups): a voxel of a unit that does
+// not exist or lies beyond the lattice reads as unobserved, {0, 0}.  k_surface's and k_mesh_verts' reading of the volume.
+struct SlabVoxels {
+  const float2 *slab, *slab_x, *unit_y, *unit_z;
+  int lane;
+  __device__ __forceinline__ SlabVoxels(const VolumeView& vol, const Slab& S, int slot) : lane(S.lane) {
+    slab = vol.unit(slot) + (size_t)S.i * 4096;
+    const int sx = (S.i == 63 && S.xi < 511) ? vol.map.slot(S.key + 512 * 512) : -1;
+    const int sy = S.yi < 511 ? vol.map.slot(S.key + 512) : -1;
+    const int sz = S.zi < 511 ? vol.map.slot(S.key + 1) : -1;
+    slab_x = S.i < 63 ? slab + 4096 : (sx >= 0 ? vol.unit(sx) : nullptr);              // i + 1 (slab 0 of the next unit)
+    unit_y = sy >= 0 ? vol.unit(sy) + (size_t)S.i * 4096 : nullptr;                     // j + 1 == 64: row 0 there
+    unit_z = sz >= 0 ? vol.unit(sz) + (size_t)S.i * 4096 : nullptr;                     // k + 1 == 64: voxel 0 there
+  }
+  __device__ __forceinline__ float2 at(int j) const { return slab[j * 64 + lane]; }
+  __device__ __forceinline__ float2 up_x(int j) const { return slab_x ? slab_x[j * 64 + lane] : make_float2(0.0f, 0.0f); }
+  __device__ __forceinline__ float2 up_y(int j) const { return j < 63 ? slab[(j + 1) * 64 + lane] : (unit_y ? unit_y[lane] : make_float2(0.0f, 0.0f)); }
+  // (every lane of the wave calls it: v = at(j), the neighbour is the next lane's)
+  __device__ __forceinline__ float2 up_z(int j, float2 v) const {
     float2 nz;
     nz.x = __shfl_down(v.x, 1);
     nz.y = __shfl_down(v.y, 1);
-    if (lane == 63) nz = unit_z ? unit_z[j * 64] : none;
+    if (lane == 63) nz = unit_z ? unit_z[j * 64] : make_float2(0.0f, 0.0f);
+    return nz;
+  }
+};
+
+// Where the surface crosses the lattice edge that leaves the voxel at (px, py, pz) along `axis`: F / (F - Fn) of a voxel up that axis, F and Fn the
+// sdf of the voxel and of its neighbour there; w = the axis.  The one statement of k_surface's point, the indexed mesh's vertex and k_mesh's corner.
+__device__ __forceinline__ float4 edge_point(float px, float py, float pz, int axis, float F, float Fn) {
+  const float d = (F / (F - Fn)) * (float)kUnitLength;
+  return make_float4(axis == 0 ? px + d : px, axis == 1 ? py + d : py, axis == 2 ? pz + d : pz, (float)axis);
+}
+
+__global__ __launch_bounds__(64) void k_surface(VolumeView vol, const int* __restrict__ slots, const int* __restrict__ keys,
+                                                long* __restrict__ slab_count, const long* __restrict__ slab_offset,
+                                                float4* __restrict__ out, int pass) {
+  const Slab S(keys);
+  const SlabVoxels V(vol, S, slots[S.rank]);
+  const float gx = S.x(), gz = S.z();
+  const unsigned long long lt = (1ull << S.lane) - 1ull;
+  long base = pass ? slab_offset[blockIdx.x] : 0;
+  long total = 0;
+  for (int j = 0; j < 64; j++) {
+    const float2 v = V.at(j);
+    const float2 nx = V.up_x(j), ny = V.up_y(j), nz = V.up_z(j, v);
     const bool cx = crosses(v, nx), cy = crosses(v, ny), cz = crosses(v, nz);
     const unsigned long long bx = __ballot(cx), by = __ballot(cy), bz = __ballot(cz);
     if (pass) {
       long o = base + total + __popcll(bx & lt) + __popcll(by & lt) + __popcll(bz & lt);
-      const float gy = (float)((double)(j + (yi - 256) * 64) * kUnitLength);
-      if (cx) out[o++] = make_float4(gx + (v.x / (v.x - nx.x)) * ulf, gy, gz, 0.0f);
-      if (cy) out[o++] = make_float4(gx, gy + (v.x / (v.x - ny.x)) * ulf, gz, 1.0f);
-      if (cz) out[o++] = make_float4(gx, gy, gz + (v.x / (v.x - nz.x)) * ulf, 2.0f);
+      const float gy = S.y(j);
+      if (cx) out[o++] = edge_point(gx, gy, gz, 0, v.x, nx.x);
+      if (cy) out[o++] = edge_point(gx, gy, gz, 1, v.x, ny.x);
+      if (cz) out[o++] = edge_point(gx, gy, gz, 2, v.x, nz.x);
     }
     total += __popcll(bx) + __popcll(by) + __popcll(bz);
   }
-  if (!pass && lane == 0) slab_count[blockIdx.x] = total;
+  if (!pass && S.lane == 0) slab_count[blockIdx.x] = total;
 }
 
 // Oriented extraction (what the kinfu fragment step leaves in cloud_bin_<i>.pcd and CorresApp.cpp:82-99 reads back: the zero crossings WITH
@@ -112,32 +134,30 @@ __global__ __launch_bounds__(64) void k_surface(const float2* __restrict__ pool,
 // more dependent round trips to memory, 523 us against k_surface's 160 us on a 147-unit fragment (profiles/oriented_extraction.txt).  Here
 // every point is independent: one hash-map lookup for the unit of v, direct addresses for the neighbours that stay in it, a lookup of their
 // own for those across a unit border.  g = voxel index on the whole lattice, 0 .. 512 * 64 - 1 per axis.
-__device__ __forceinline__ float2 fetch_voxel(const float2* __restrict__ pool, const float2* __restrict__ unit, int key, const int* __restrict__ ht_key,
-                                              const int* __restrict__ ht_slot, int cap_mask, int shift, int gx, int gy, int gz) {
-  if ((unsigned)gx >= 512u * 64u || (unsigned)gy >= 512u * 64u || (unsigned)gz >= 512u * 64u) return make_float2(0.0f, 0.0f);
-  const int k = (gx >> 6) << 18 | (gy >> 6) << 9 | (gz >> 6);
-  const size_t l = (size_t)(gx & 63) * 4096 + (size_t)(gy & 63) * 64 + (size_t)(gz & 63);
+__device__ __forceinline__ float2 fetch_voxel(const VolumeView& vol, const float2* __restrict__ unit, int key, int gx, int gy, int gz) {
+  if (!on_lattice(gx, gy, gz)) return make_float2(0.0f, 0.0f);
+  const int k = unit_key_of(gx, gy, gz);
+  const size_t l = unit_offset_of(gx, gy, gz);
   if (k == key) return unit[l];
-  const int s = ht_lookup_slot(ht_key, ht_slot, cap_mask, shift, k);
-  return s >= 0 ? pool[(size_t)s * kUnitVox + l] : make_float2(0.0f, 0.0f);
+  const int s = vol.map.slot(k);
+  return s >= 0 ? vol.unit(s)[l] : make_float2(0.0f, 0.0f);
 }
 
 // the nearest voxel's index: rint((double)p / unit length), round half to even, on the 0-based lattice
 __device__ __forceinline__ int nearest_index(float p) { return (int)rint((double)p / kUnitLength) + 256 * 64; }
 
-__global__ __launch_bounds__(256) void k_surface_normals(const float2* __restrict__ pool, const int* __restrict__ ht_key, const int* __restrict__ ht_slot,
-                                                         int cap_mask, int shift, const float4* __restrict__ pts, long n, float4* __restrict__ out_n) {
+__global__ __launch_bounds__(256) void k_surface_normals(VolumeView vol, const float4* __restrict__ pts, long n, float4* __restrict__ out_n) {
   const long r = (long)blockIdx.x * 256 + threadIdx.x;
   if (r >= n) return;
   const float4 p = pts[r];
   const int gx = nearest_index(p.x), gy = nearest_index(p.y), gz = nearest_index(p.z);
   // the unit of v: key -1 (matches no voxel) if v is outside the lattice or its unit does not exist -- the fetches then find that out themselves
-  const bool in = (unsigned)gx < 512u * 64u && (unsigned)gy < 512u * 64u && (unsigned)gz < 512u * 64u;
-  int key = in ? ((gx >> 6) << 18 | (gy >> 6) << 9 | (gz >> 6)) : -1;
-  const int slot = in ? ht_lookup_slot(ht_key, ht_slot, cap_mask, shift, key) : -1;
+  const bool in = on_lattice(gx, gy, gz);
+  int key = in ? unit_key_of(gx, gy, gz) : -1;
+  const int slot = in ? vol.map.slot(key) : -1;
   if (slot < 0) key = -1;
-  const float2* unit = pool + (size_t)(slot < 0 ? 0 : slot) * kUnitVox;
-#define ER_F(dx, dy, dz) fetch_voxel(pool, unit, key, ht_key, ht_slot, cap_mask, shift, gx + (dx), gy + (dy), gz + (dz))
+  const float2* unit = vol.unit(slot < 0 ? 0 : slot);
+#define ER_F(dx, dy, dz) fetch_voxel(vol, unit, key, gx + (dx), gy + (dy), gz + (dz))
   const float2 c = ER_F(0, 0, 0);
   const float2 xl = ER_F(-1, 0, 0), xh = ER_F(1, 0, 0), yl = ER_F(0, -1, 0), yh = ER_F(0, 1, 0), zl = ER_F(0, 0, -1), zh = ER_F(0, 0, 1);
 #undef ER_F
@@ -189,107 +209,144 @@ __global__ __launch_bounds__(64) void k_oriented_keep(const float4* __restrict__
 // 3/512)) -- evaluated from the edge's LOWER end whichever cell asks, so the cells that share the edge produce the same bits and
 // the triangle soup is watertight by vertex equality.  Order: units by ascending key, cells in i, j, k order, triangles in table
 // order; two passes (count, then write at the slab's offset: a stable ballot-prefix compaction) like k_world / k_surface.
-__global__ __launch_bounds__(64) void k_mesh(const float2* __restrict__ pool, const int* __restrict__ slots, const int* __restrict__ keys,
-                                             const int* __restrict__ ht_key, const int* __restrict__ ht_slot, int cap_mask, int shift,
-                                             const unsigned char* __restrict__ table, long* __restrict__ slab_count,
-                                             const long* __restrict__ slab_offset, float* __restrict__ out, int pass) {
-  __shared__ unsigned char s_tab[256 * 16];
-  for (int t = threadIdx.x; t < 256 * 16 / 4; t += 64) reinterpret_cast<unsigned*>(s_tab)[t] = reinterpret_cast<const unsigned*>(table)[t];
-  __syncthreads();
-  const int rank = blockIdx.x >> 6;          // unit in ascending key order
-  const int i = blockIdx.x & 63;
-  const int lane = threadIdx.x;              // = k
-  const int key = keys[rank];
-  const int xi = key >> 18, yi = (key >> 9) & 511, zi = key & 511;
-  // the (up to) eight units a slab of cells can touch: [dx][dy][dz]; -1 = that unit does not exist (its voxels count as unobserved)
-  int us[2][2][2];
-  for (int dx = 0; dx < 2; dx++)
-    for (int dy = 0; dy < 2; dy++)
-      for (int dz = 0; dz < 2; dz++) {
-        const bool need = (dx == 0 || i == 63);
-        const bool ok = xi + dx < 512 && yi + dy < 512 && zi + dz < 512;
-        us[dx][dy][dz] = (dx | dy | dz) == 0 ? slots[rank]
-                         : (need && ok ? ht_lookup_slot(ht_key, ht_slot, cap_mask, shift, key + dx * 512 * 512 + dy * 512 + dz) : -1);
-      }
-  const int ia[2] = {i, i == 63 ? 0 : i + 1}, ux[2] = {0, i == 63 ? 1 : 0};      // slab index and unit offset of the two i layers
-  const float2 none = make_float2(0.0f, 0.0f);
-  const float ulf = (float)kUnitLength;
-  const float gx = (float)((double)(i + (xi - 256) * 64) * kUnitLength);
-  const float gz = (float)((double)(lane + (zi - 256) * 64) * kUnitLength);
-  const unsigned long long lt = (1ull << lane) - 1ull;
-  long base = pass ? slab_offset[blockIdx.x] : 0;
-  long total = 0;
-  for (int j = 0; j < 64; j++) {
-    // the eight corners of this lane's cell: f[a][b][c] = voxel (i + a, j + b, k + c)
-    float2 f[2][2][2];
+
+// element idx of a table of eight that lives in registers: a select chain over the VALUES (a run-time index, or a chain over references to
+// the array's elements, which the compiler folds back into one, sends the table through scratch)
+__device__ __forceinline__ int pick8v(int t0, int t1, int t2, int t3, int t4, int t5, int t6, int t7, int idx) {
+  int r = t0;
+  r = idx == 1 ? t1 : r;
+  r = idx == 2 ? t2 : r;
+  r = idx == 3 ? t3 : r;
+  r = idx == 4 ? t4 : r;
+  r = idx == 5 ? t5 : r;
+  r = idx == 6 ? t6 : r;
+  r = idx == 7 ? t7 : r;
+  return r;
+}
+#define ER_PICK8(t, idx) pick8v(t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], idx)
+
+// Edge id e of the case table: its axis and the cell corner (a0, b0, c0) it STARTS at -- coordinate 0 along its axis; it ends one step up the axis.
+struct CellEdge {
+  int axis, a0, b0, c0;
+  __device__ __forceinline__ explicit CellEdge(int e) {
+    const int u = e & 1, v = (e >> 1) & 1;
+    axis = e >> 2;
+    a0 = axis == 0 ? 0 : u, b0 = axis == 1 ? 0 : (axis == 0 ? u : v), c0 = axis == 2 ? 0 : v;
+  }
+  __device__ __forceinline__ int corner() const { return a0 | b0 << 1 | c0 << 2; }
+};
+
+// The walk of k_mesh and k_mesh_index over a slab's cells, one row j of 64 cells at a time: what the two kernels know before they do their own
+// thing with a cell's triangles (emit positions; mark the bitmap or emit indices).  The constructor holds the kernel's one __syncthreads().
+// kRanks: also the units' ranks (position in key order; -1: none, or dropped), for the kernel that addresses per-unit arrays of its own.
+template <bool kRanks>
+struct CellWalk {
+  const unsigned char* tab;                    // the case table, staged in LDS
+  const float2* pool;
+  int lane;
+  // the (up to) eight units a slab of cells can touch: pool slots and ranks, [dx << 2 | dy << 1 | dz]; -1 = that unit does not exist (its voxels
+  // count as unobserved).  Constant indices and ER_PICK8 only.
+  int us[8], rk[8];
+  int ia[2], ux[2];                            // slab index and unit offset dx of the two i layers
+
+  __device__ __forceinline__ CellWalk(const VolumeView& vol, const Slab& S, int own_slot, const unsigned char* __restrict__ table,
+                                      const int* __restrict__ slot_rank)
+      : pool(vol.pool), lane(S.lane) {
+    __shared__ unsigned char s_tab[256 * 16];
+    for (int t = threadIdx.x; t < 256 * 16 / 4; t += 64) reinterpret_cast<unsigned*>(s_tab)[t] = reinterpret_cast<const unsigned*>(table)[t];
+    __syncthreads();
+    tab = s_tab;
+#pragma unroll
+    for (int dx = 0; dx < 2; dx++)
+#pragma unroll
+      for (int dy = 0; dy < 2; dy++)
+#pragma unroll
+        for (int dz = 0; dz < 2; dz++) {
+          const bool need = (dx == 0 || S.i == 63);
+          const bool ok = S.xi + dx < 512 && S.yi + dy < 512 && S.zi + dz < 512;
+          const int s = (dx | dy | dz) == 0 ? own_slot : (need && ok ? vol.map.slot(S.key + dx * 512 * 512 + dy * 512 + dz) : -1);
+          us[dx << 2 | dy << 1 | dz] = s;
+          if (kRanks) rk[dx << 2 | dy << 1 | dz] = s >= 0 ? slot_rank[s] : -1;
+        }
+    ia[0] = S.i, ia[1] = S.i == 63 ? 0 : S.i + 1;
+    ux[0] = 0, ux[1] = S.i == 63 ? 1 : 0;
+  }
+
+  // index into us / rk of the unit that holds row jj = j + b (0 .. 64) of i layer a, at dz = 0; | 1: its +z neighbour
+  __device__ __forceinline__ int unit_at(int a, int jj) const { return ux[a] << 2 | (jj >> 6) << 1; }
+  __device__ __forceinline__ int rank_at(int idx) const { return ER_PICK8(rk, idx); }
+
+  // Row j: the eight corners of this lane's cell, f[a | b << 1 | c << 2] = voxel (i + a, j + b, k + c), and the cell's row of the case table;
+  // -> its number of triangles, 0 unless all eight corners are observed.  Every lane of the wave calls it.
+  __device__ __forceinline__ int cell(int j, float2 (&f)[8], const unsigned char*& row) const {
+    // (the unobserved voxel is a VALUE in these conditionals: between two named objects the compiler selects an address, and one is in scratch)
 #pragma unroll
     for (int a = 0; a < 2; a++)
 #pragma unroll
       for (int b = 0; b < 2; b++) {
-        const int jb = (j + b) & 63, uy = (j + b) >> 6;
-        const int s0 = us[ux[a]][uy][0], s1 = us[ux[a]][uy][1];
+        const int jb = (j + b) & 63;
+        const int s0 = ER_PICK8(us, unit_at(a, j + b)), s1 = ER_PICK8(us, unit_at(a, j + b) | 1);
         const size_t ro = (size_t)ia[a] * 4096 + (size_t)jb * 64;
-        const float2 v = s0 >= 0 ? pool[(size_t)s0 * kUnitVox + ro + lane] : none;
-        f[a][b][0] = v;
+        const float2 v = s0 >= 0 ? pool[(size_t)s0 * kUnitVox + ro + lane] : make_float2(0.0f, 0.0f);
+        f[a | b << 1] = v;
         float2 w;
         w.x = __shfl_down(v.x, 1);
         w.y = __shfl_down(v.y, 1);
-        if (lane == 63) w = s1 >= 0 ? pool[(size_t)s1 * kUnitVox + ro] : none;
-        f[a][b][1] = w;
+        if (lane == 63) w = s1 >= 0 ? pool[(size_t)s1 * kUnitVox + ro] : make_float2(0.0f, 0.0f);
+        f[a | b << 1 | 4] = w;
       }
     bool valid = true;
     int cs = 0;
 #pragma unroll
     for (int c = 0; c < 8; c++) {
-      const float2 v = f[c & 1][(c >> 1) & 1][c >> 2];
-      valid = valid && v.y != 0.0f;
-      cs |= (v.x < 0.0f ? 1 : 0) << c;
+      valid = valid && f[c].y != 0.0f;
+      cs |= (f[c].x < 0.0f ? 1 : 0) << c;
     }
-    const unsigned char* __restrict__ row = s_tab + cs * 16;
+    row = tab + cs * 16;
     int nt = 0;
     if (valid)
       while (nt < 5 && row[3 * nt] != 255) nt++;
-    // wave-level exclusive prefix of the triangle counts (k order)
-    int incl = nt;
-    for (int sft = 1; sft < 64; sft <<= 1) {
-      const int t = __shfl_up(incl, sft);
-      if (lane >= sft) incl += t;
-    }
+    return nt;
+  }
+};
+
+__global__ __launch_bounds__(64) void k_mesh(VolumeView vol, const int* __restrict__ slots, const int* __restrict__ keys,
+                                             const unsigned char* __restrict__ table, long* __restrict__ slab_count,
+                                             const long* __restrict__ slab_offset, float* __restrict__ out, int pass) {
+  const Slab S(keys);
+  const CellWalk<false> W(vol, S, slots[S.rank], table, nullptr);
+  const float gx = S.x(), gz = S.z();
+  long base = pass ? slab_offset[blockIdx.x] : 0;
+  long total = 0;
+  for (int j = 0; j < 64; j++) {
+    float2 f[8];
+    const unsigned char* row;
+    const int nt = W.cell(j, f, row);
+    const int incl = wave_inclusive_sum(nt, S.lane);     // (k order)
     const int wave_total = __shfl(incl, 63);
     if (pass && nt > 0) {
-      const float gy = (float)((double)(j + (yi - 256) * 64) * kUnitLength);
+      const float gy = S.y(j);
       float* __restrict__ o = out + (size_t)(base + total + (incl - nt)) * 9;
       for (int t = 0; t < 3 * nt; t++) {
-        const int e = row[t];
-        const int axis = e >> 2, u = e & 1, v = (e >> 1) & 1;
-        // lower corner of the edge (coordinate 0 along its axis) and the corner one step up the axis; the eight corner values sit
-        // in registers, so they are picked with select chains, not with a runtime index (that would send them through scratch)
-        const int a0 = axis == 0 ? 0 : u, b0 = axis == 1 ? 0 : (axis == 0 ? u : v), c0 = axis == 2 ? 0 : v;
-        const int cl = a0 | b0 << 1 | c0 << 2, ch = cl | (1 << axis);
-        float2 lo = none, hi = none;
+        const CellEdge E(row[t]);
+        // the edge's two ends; the eight corner values sit in registers, so they are picked with select chains, not with a runtime index
+        const int cl = E.corner(), ch = cl | (1 << E.axis);
+        float2 lo = f[0], hi = f[0];
 #pragma unroll
-        for (int c = 0; c < 8; c++) {
-          const float2 fv = f[c & 1][(c >> 1) & 1][c >> 2];
-          lo = c == cl ? fv : lo;
-          hi = c == ch ? fv : hi;
+        for (int c = 1; c < 8; c++) {
+          lo = c == cl ? f[c] : lo;
+          hi = c == ch ? f[c] : hi;
         }
-        const float tt = lo.x / (lo.x - hi.x);
-        // lower end of the edge: lattice position of voxel (i + a0, j + b0, k + c0)
-        float px = a0 ? (float)((double)(i + 1 + (xi - 256) * 64) * kUnitLength) : gx;
-        float py = b0 ? (float)((double)(j + 1 + (yi - 256) * 64) * kUnitLength) : gy;
-        float pz = c0 ? (float)((double)(lane + 1 + (zi - 256) * 64) * kUnitLength) : gz;
-        if (axis == 0) px = px + tt * ulf;
-        if (axis == 1) py = py + tt * ulf;
-        if (axis == 2) pz = pz + tt * ulf;
-        o[3 * t] = px;
-        o[3 * t + 1] = py;
-        o[3 * t + 2] = pz;
+        // from the lower end of the edge, voxel (i + a0, j + b0, k + c0)
+        const float4 p = edge_point(E.a0 ? S.x(1) : gx, E.b0 ? S.y(j + 1) : gy, E.c0 ? S.z(1) : gz, E.axis, lo.x, hi.x);
+        o[3 * t] = p.x;
+        o[3 * t + 1] = p.y;
+        o[3 * t + 2] = p.z;
       }
     }
     total += wave_total;
   }
-  (void)lt;
-  if (!pass && lane == 0) slab_count[blockIdx.x] = total;
+  if (!pass && S.lane == 0) slab_count[blockIdx.x] = total;
 }
 
 // The INDEXED mesh (er_tsdf_extract_mesh_indexed): k_mesh's triangles as three int32 indices into a list of unique vertices.
@@ -310,21 +367,6 @@ __global__ __launch_bounds__(64) void k_mesh(const float2* __restrict__ pool, co
 //                          wave-uniform loads, once per row of cells -- and lane 63 alone four more in the +z unit.
 // The bitmap is 96 KiB per unit, the row prefixes 16 KiB.
 
-// element idx of a table of eight that lives in registers: a select chain over the VALUES (a run-time index, or a chain over references to
-// the array's elements, which the compiler folds back into one, sends the table through scratch)
-__device__ __forceinline__ int pick8v(int t0, int t1, int t2, int t3, int t4, int t5, int t6, int t7, int idx) {
-  int r = t0;
-  r = idx == 1 ? t1 : r;
-  r = idx == 2 ? t2 : r;
-  r = idx == 3 ? t3 : r;
-  r = idx == 4 ? t4 : r;
-  r = idx == 5 ? t5 : r;
-  r = idx == 6 ? t6 : r;
-  r = idx == 7 ? t7 : r;
-  return r;
-}
-#define ER_PICK8(t, idx) pick8v(t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], idx)
-
 // ORs a row mask into bitmap row (unit of rank r, i, j), axis: two 32-bit words (little endian: word 0 = k 0 .. 31)
 __device__ __forceinline__ void mark_row(unsigned long long* __restrict__ bm, int r, int i, int j, int axis, unsigned long long m) {
   if (r < 0) return;                           // (no such unit: cannot be the owner of an edge of a valid cell)
@@ -334,93 +376,38 @@ __device__ __forceinline__ void mark_row(unsigned long long* __restrict__ bm, in
   if (hi) atomicOr(w + 1, hi);
 }
 
-__global__ __launch_bounds__(64) void k_mesh_index(const float2* __restrict__ pool, const int* __restrict__ slots, const int* __restrict__ keys,
-                                                   const int* __restrict__ ht_key, const int* __restrict__ ht_slot, int cap_mask, int shift,
+__global__ __launch_bounds__(64) void k_mesh_index(VolumeView vol, const int* __restrict__ slots, const int* __restrict__ keys,
                                                    const unsigned char* __restrict__ table, const int* __restrict__ slot_rank,
                                                    unsigned long long* __restrict__ bm, const int* __restrict__ row_off,
                                                    const long* __restrict__ vslab_off, long* __restrict__ slab_count,
                                                    const long* __restrict__ slab_offset, int* __restrict__ out, int pass) {
-  __shared__ unsigned char s_tab[256 * 16];
-  for (int t = threadIdx.x; t < 256 * 16 / 4; t += 64) reinterpret_cast<unsigned*>(s_tab)[t] = reinterpret_cast<const unsigned*>(table)[t];
-  __syncthreads();
-  const int rank = blockIdx.x >> 6;          // unit in ascending key order
-  const int i = blockIdx.x & 63;
-  const int lane = threadIdx.x;              // = k
-  const int key = keys[rank];
-  const int xi = key >> 18, yi = (key >> 9) & 511, zi = key & 511;
-  // the (up to) eight units a slab of cells can touch, as in k_mesh: pool slots and ranks, [dx << 2 | dy << 1 | dz]; -1 = none (rank: or dropped)
-  int us[8], rk[8];
-#pragma unroll
-  for (int dx = 0; dx < 2; dx++)
-#pragma unroll
-    for (int dy = 0; dy < 2; dy++)
-#pragma unroll
-      for (int dz = 0; dz < 2; dz++) {
-        const bool need = (dx == 0 || i == 63);
-        const bool ok = xi + dx < 512 && yi + dy < 512 && zi + dz < 512;
-        const int s = (dx | dy | dz) == 0 ? slots[rank]
-                      : (need && ok ? ht_lookup_slot(ht_key, ht_slot, cap_mask, shift, key + dx * 512 * 512 + dy * 512 + dz) : -1);
-        us[dx << 2 | dy << 1 | dz] = s;
-        rk[dx << 2 | dy << 1 | dz] = s >= 0 ? slot_rank[s] : -1;
-      }
-  const int ia[2] = {i, i == 63 ? 0 : i + 1}, ux[2] = {0, i == 63 ? 1 : 0};      // slab index and unit offset of the two i layers (constant indices only)
-  const float2 none = make_float2(0.0f, 0.0f);
+  const Slab S(keys);
+  const CellWalk<true> W(vol, S, slots[S.rank], table, slot_rank);
+  const int lane = S.lane;
   const unsigned long long lt = (1ull << lane) - 1ull;
   long base = pass ? slab_offset[blockIdx.x] : 0;
   long total = 0;
   for (int j = 0; j < 64; j++) {
-    // the eight corners of this lane's cell: f[a][b][c] = voxel (i + a, j + b, k + c)
-    float2 f[2][2][2];
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-      for (int b = 0; b < 2; b++) {
-        const int jb = (j + b) & 63, uy = (j + b) >> 6;
-        const int s0 = ER_PICK8(us, ux[a] << 2 | uy << 1), s1 = ER_PICK8(us, ux[a] << 2 | uy << 1 | 1);
-        const size_t ro = (size_t)ia[a] * 4096 + (size_t)jb * 64;
-        const float2 v = s0 >= 0 ? pool[(size_t)s0 * kUnitVox + ro + lane] : none;
-        f[a][b][0] = v;
-        float2 w;
-        w.x = __shfl_down(v.x, 1);
-        w.y = __shfl_down(v.y, 1);
-        if (lane == 63) w = s1 >= 0 ? pool[(size_t)s1 * kUnitVox + ro] : none;
-        f[a][b][1] = w;
-      }
-    bool valid = true;
-    int cs = 0;
-#pragma unroll
-    for (int c = 0; c < 8; c++) {
-      const float2 v = f[c & 1][(c >> 1) & 1][c >> 2];
-      valid = valid && v.y != 0.0f;
-      cs |= (v.x < 0.0f ? 1 : 0) << c;
-    }
-    const unsigned char* __restrict__ row = s_tab + cs * 16;
-    int nt = 0;
-    if (valid)
-      while (nt < 5 && row[3 * nt] != 255) nt++;
-    // wave-level exclusive prefix of the triangle counts (k order)
-    int incl = nt;
-    for (int sft = 1; sft < 64; sft <<= 1) {
-      const int t = __shfl_up(incl, sft);
-      if (lane >= sft) incl += t;
-    }
+    float2 f[8];
+    const unsigned char* row;
+    const int nt = W.cell(j, f, row);
+    const int incl = wave_inclusive_sum(nt, lane);       // (k order)
     const int wave_total = __shfl(incl, 63);
     total += wave_total;
     if (wave_total == 0) continue;             // (wave-uniform)
     if (!pass) {
-      // the cell edges this lane's triangles use: bit e = edge id e of the table (axis = e >> 2, u = e & 1, v = (e >> 1) & 1)
+      // the cell edges this lane's triangles use: bit e = edge id e of the table
       unsigned used = 0;
       for (int t = 0; t < 3 * nt; t++) used |= 1u << row[t];
 #pragma unroll
       for (int e = 0; e < 12; e++) {
         const unsigned long long m = __ballot((used >> e) & 1u);
         if (m == 0 || lane != 0) continue;
-        const int axis = e >> 2, u = e & 1, v = (e >> 1) & 1;
-        const int a0 = axis == 0 ? 0 : u, b0 = axis == 1 ? 0 : (axis == 0 ? u : v), c0 = axis == 2 ? 0 : v;
-        const int jb = (j + b0) & 63, uy = (j + b0) >> 6;
+        const CellEdge E(e);
+        const int jb = (j + E.b0) & 63, u = W.unit_at(E.a0, j + E.b0);
         // owner voxel (i + a0, j + b0, k + c0): bit k + c0 of its row; k + c0 == 64 is voxel 0 of the row in the +z unit
-        mark_row(bm, ER_PICK8(rk, ux[a0] << 2 | uy << 1), ia[a0], jb, axis, c0 ? m << 1 : m);
-        if (c0 && (m >> 63)) mark_row(bm, ER_PICK8(rk, ux[a0] << 2 | uy << 1 | 1), ia[a0], jb, axis, 1ull);
+        mark_row(bm, W.rank_at(u), W.ia[E.a0], jb, E.axis, E.c0 ? m << 1 : m);
+        if (E.c0 && (m >> 63)) mark_row(bm, W.rank_at(u | 1), W.ia[E.a0], jb, E.axis, 1ull);
       }
       continue;
     }
@@ -431,16 +418,16 @@ __global__ __launch_bounds__(64) void k_mesh_index(const float2* __restrict__ po
     for (int a = 0; a < 2; a++)
 #pragma unroll
       for (int b = 0; b < 2; b++) {
-        const int jb = (j + b) & 63, uy = (j + b) >> 6;
-        const int r0 = ER_PICK8(rk, ux[a] << 2 | uy << 1), r1 = ER_PICK8(rk, ux[a] << 2 | uy << 1 | 1);
+        const int jb = (j + b) & 63, ia = W.ia[a];
+        const int r0 = W.rank_at(W.unit_at(a, j + b)), r1 = W.rank_at(W.unit_at(a, j + b) | 1);
         unsigned long long mx = 0, my = 0, mz = 0;
         int rb = 0;
         if (r0 >= 0) {                         // (wave-uniform: one fetch of the row serves all 64 lanes)
-          const size_t r = (size_t)r0 * 4096 + (size_t)ia[a] * 64 + jb;
+          const size_t r = (size_t)r0 * 4096 + (size_t)ia * 64 + jb;
           mx = bm[r * 3];
           my = bm[r * 3 + 1];
           mz = bm[r * 3 + 2];
-          rb = (int)vslab_off[r0 * 64 + ia[a]] + row_off[r];
+          rb = (int)vslab_off[r0 * 64 + ia] + row_off[r];
         }
         const int c = a | b << 1;
         P[c] = rb + __popcll(mx & lt) + __popcll(my & lt) + __popcll(mz & lt);
@@ -453,8 +440,8 @@ __global__ __launch_bounds__(64) void k_mesh_index(const float2* __restrict__ po
         if (lane == 63) {
           p1 = q1 = 0;
           if (r1 >= 0) {
-            const size_t r = (size_t)r1 * 4096 + (size_t)ia[a] * 64 + jb;
-            p1 = (int)vslab_off[r1 * 64 + ia[a]] + row_off[r];
+            const size_t r = (size_t)r1 * 4096 + (size_t)ia * 64 + jb;
+            p1 = (int)vslab_off[r1 * 64 + ia] + row_off[r];
             q1 = (int)(bm[r * 3] & 1ull) | (int)(bm[r * 3 + 1] & 1ull) << 1;
           }
         }
@@ -464,12 +451,9 @@ __global__ __launch_bounds__(64) void k_mesh_index(const float2* __restrict__ po
     if (nt > 0) {
       int* __restrict__ o = out + (size_t)(base + (total - wave_total) + (incl - nt)) * 3;
       for (int t = 0; t < 3 * nt; t++) {
-        const int e = row[t];
-        const int axis = e >> 2, u = e & 1, v = (e >> 1) & 1;
-        const int a0 = axis == 0 ? 0 : u, b0 = axis == 1 ? 0 : (axis == 0 ? u : v), c0 = axis == 2 ? 0 : v;
-        const int cl = a0 | b0 << 1 | c0 << 2;
-        const int bits = ER_PICK8(B, cl);
-        o[t] = ER_PICK8(P, cl) + (axis > 0 ? bits & 1 : 0) + (axis > 1 ? bits >> 1 : 0);
+        const CellEdge E(row[t]);
+        const int bits = ER_PICK8(B, E.corner());
+        o[t] = ER_PICK8(P, E.corner()) + (E.axis > 0 ? bits & 1 : 0) + (E.axis > 1 ? bits >> 1 : 0);
       }
     }
   }
@@ -483,59 +467,34 @@ __global__ __launch_bounds__(64) void k_mesh_rows(const unsigned long long* __re
   const int lane = threadIdx.x;
   const size_t r = (size_t)blockIdx.x * 64 + lane;
   const int c = __popcll(bm[r * 3]) + __popcll(bm[r * 3 + 1]) + __popcll(bm[r * 3 + 2]);
-  int incl = c;
-  for (int sft = 1; sft < 64; sft <<= 1) {
-    const int t = __shfl_up(incl, sft);
-    if (lane >= sft) incl += t;
-  }
+  const int incl = wave_inclusive_sum(c, lane);
   row_off[r] = incl - c;
   if (lane == 63) vslab_count[blockIdx.x] = incl;
 }
 
 // One wave per slab, lane = k: the vertices of the slab's marked edges, float4 = x y z axis like k_surface's points, the position by k_mesh's
 // expression pos(L) + (F_L / (F_L - F_H)) * voxel size.  The upper voxel H exists wherever a bit is set (the cell that set it was valid).
-__global__ __launch_bounds__(64) void k_mesh_verts(const float2* __restrict__ pool, const int* __restrict__ slots, const int* __restrict__ keys,
-                                                   const int* __restrict__ ht_key, const int* __restrict__ ht_slot, int cap_mask, int shift,
+__global__ __launch_bounds__(64) void k_mesh_verts(VolumeView vol, const int* __restrict__ slots, const int* __restrict__ keys,
                                                    const unsigned long long* __restrict__ bm, const int* __restrict__ row_off,
                                                    const long* __restrict__ vslab_off, float4* __restrict__ out) {
-  const int rank = blockIdx.x >> 6;          // unit in ascending key order
-  const int i = blockIdx.x & 63;
-  const int lane = threadIdx.x;              // = k
-  const int key = keys[rank];
-  const int xi = key >> 18, yi = (key >> 9) & 511, zi = key & 511;
-  const float2* unit = pool + (size_t)slots[rank] * kUnitVox;
-  const float2* slab = unit + (size_t)i * 4096;
-  const int sx = (i == 63 && xi < 511) ? ht_lookup_slot(ht_key, ht_slot, cap_mask, shift, key + 512 * 512) : -1;
-  const int sy = yi < 511 ? ht_lookup_slot(ht_key, ht_slot, cap_mask, shift, key + 512) : -1;
-  const int sz = zi < 511 ? ht_lookup_slot(ht_key, ht_slot, cap_mask, shift, key + 1) : -1;
-  const float2 none = make_float2(0.0f, 0.0f);
-  const float2* slab_x = i < 63 ? slab + 4096 : (sx >= 0 ? pool + (size_t)sx * kUnitVox : nullptr);
-  const float2* unit_y = sy >= 0 ? pool + (size_t)sy * kUnitVox + (size_t)i * 4096 : nullptr;
-  const float2* unit_z = sz >= 0 ? pool + (size_t)sz * kUnitVox + (size_t)i * 4096 : nullptr;
-  const float ulf = (float)kUnitLength;
-  const float gx = (float)((double)(i + (xi - 256) * 64) * kUnitLength);
-  const float gz = (float)((double)(lane + (zi - 256) * 64) * kUnitLength);
+  const Slab S(keys);
+  const SlabVoxels V(vol, S, slots[S.rank]);
+  const int lane = S.lane;
+  const float gx = S.x(), gz = S.z();
   const unsigned long long lt = (1ull << lane) - 1ull;
   const long base = vslab_off[blockIdx.x];
   for (int j = 0; j < 64; j++) {
     const size_t r = (size_t)blockIdx.x * 64 + j;
     const unsigned long long mx = bm[r * 3], my = bm[r * 3 + 1], mz = bm[r * 3 + 2];
     if ((mx | my | mz) == 0) continue;         // (wave-uniform)
-    const float2 v = slab[j * 64 + lane];
-    float nz = __shfl_down(v.x, 1);
-    if (lane == 63) nz = unit_z ? unit_z[j * 64].x : 0.0f;
+    const float2 v = V.at(j);
+    const float nz = V.up_z(j, v).x;
     const bool cx = (mx >> lane) & 1ull, cy = (my >> lane) & 1ull, cz = (mz >> lane) & 1ull;
     long o = base + row_off[r] + __popcll(mx & lt) + __popcll(my & lt) + __popcll(mz & lt);
-    const float gy = (float)((double)(j + (yi - 256) * 64) * kUnitLength);
-    if (cx) {
-      const float2 nx = slab_x ? slab_x[j * 64 + lane] : none;
-      out[o++] = make_float4(gx + (v.x / (v.x - nx.x)) * ulf, gy, gz, 0.0f);
-    }
-    if (cy) {
-      const float2 ny = j < 63 ? slab[(j + 1) * 64 + lane] : (unit_y ? unit_y[lane] : none);
-      out[o++] = make_float4(gx, gy + (v.x / (v.x - ny.x)) * ulf, gz, 1.0f);
-    }
-    if (cz) out[o++] = make_float4(gx, gy, gz + (v.x / (v.x - nz)) * ulf, 2.0f);
+    const float gy = S.y(j);
+    if (cx) out[o++] = edge_point(gx, gy, gz, 0, v.x, V.up_x(j).x);
+    if (cy) out[o++] = edge_point(gx, gy, gz, 1, v.x, V.up_y(j).x);
+    if (cz) out[o++] = edge_point(gx, gy, gz, 2, v.x, nz);
   }
 }
 
@@ -543,27 +502,26 @@ __global__ __launch_bounds__(64) void k_mesh_verts(const float2* __restrict__ po
 // the coordinates are integers on the lattice and has created the row's unit -- stores (intensity, 1) in its voxel, one 8-byte vector store.
 // The units were (+0, 0) everywhere, so afterwards the weights sum to the number of DISTINCT voxels listed: to the number of rows iff no
 // voxel is listed twice.  (Adding 1 to the weight instead would not tell: that sum is the number of rows whatever they name.)
-__global__ __launch_bounds__(256) void k_import_world(float2* __restrict__ pool, const int* __restrict__ ht_key, const int* __restrict__ ht_slot,
-                                                      int cap_mask, int shift, const float4* __restrict__ rows, long n) {
+__global__ __launch_bounds__(256) void k_import_world(float2* __restrict__ pool, UnitMap map, const float4* __restrict__ rows, long n) {
   const long r = (long)blockIdx.x * 256 + threadIdx.x;
   if (r >= n) return;
   const float4 p = rows[r];
   const int gx = (int)p.x + 256 * 64, gy = (int)p.y + 256 * 64, gz = (int)p.z + 256 * 64;
-  if ((unsigned)gx >= 512u * 64u || (unsigned)gy >= 512u * 64u || (unsigned)gz >= 512u * 64u) return;   // (refused by the host)
-  const int slot = ht_lookup_slot(ht_key, ht_slot, cap_mask, shift, (gx >> 6) << 18 | (gy >> 6) << 9 | (gz >> 6));
+  if (!on_lattice(gx, gy, gz)) return;                                                                   // (refused by the host)
+  const int slot = map.slot(unit_key_of(gx, gy, gz));
   if (slot < 0) return;                                                                                  // (the pool is exhausted: refused by the host)
-  float2* v = pool + (size_t)slot * kUnitVox + (size_t)(gx & 63) * 4096 + (size_t)(gy & 63) * 64 + (size_t)(gz & 63);
-  *v = make_float2(p.w, 1.0f);
+  pool[(size_t)slot * kUnitVox + unit_offset_of(gx, gy, gz)] = make_float2(p.w, 1.0f);
 }
 
 // The first of the two passes of one extraction call over the device temporaries of that call: they live in `scope`, the call's own (freed when
 // the call leaves, whichever way) or the one of the DeviceMesh that the call fills, and so does what the caller adds (its output, a table).
-// d_keys / d_slots: the units in ascending key order; cnt() / off(): per slab (64 per unit, one block each) what the count pass found and where
-// the write pass starts -- a list of `lists` (er_compact.h), which lives with the scope.  A call with n_lists = 2 compacts a second list over
-// the same slabs (the indexed mesh's vertices), counted and uploaded with the first.
+// keys / slots: the units in ascending key order, on the host and (d_keys / d_slots) on the device; cnt() / off(): per slab (64 per unit, one block
+// each) what the count pass found and where the write pass starts -- a list of `lists` (er_compact.h), which lives with the scope.  A call with
+// n_lists = 2 compacts a second list over the same slabs (the indexed mesh's vertices), counted and uploaded with the first.
 struct SlabPass {
   DevScope& scope;
   TwoPass& lists;
+  std::vector<int> keys, slots;                // (the host side of count()'s two copies; count() returns only behind a synchronise)
   int n = 0, nslab = 0;
   int *d_keys = nullptr, *d_slots = nullptr;
 
@@ -571,21 +529,33 @@ struct SlabPass {
   long* cnt(int list = 0) const { return lists.blk(list); }
   const long* off(int list = 0) const { return lists.off(list); }
 
-  int alloc(const char* who, int n_units, int n_lists = 1) {
-    n = n_units;
+  // Lists the units (sorted_units: behind every queued batch): -> n and nslab, 0 for an empty volume.
+  int units(er_tsdf_t h) {
+    if (sorted_units(h, keys, slots)) return 1;
+    n = (int)keys.size();
     nslab = n * 64;
+    return 0;
+  }
+
+  int alloc(const char* who, int n_lists = 1) {
     for (int l = 0; l < n_lists; l++) lists.add(nslab, 1);
     return scope.alloc(&d_keys, (size_t)n, who) || scope.alloc(&d_slots, (size_t)n, who) || lists.alloc(scope, who);
   }
 
   // Uploads the unit list, runs the caller's count launch (-> 0, or non-zero after reporting its failure), reads the slab counts back and
-  // sums them on the host: -> *total (and lists.total(1)).  Synchronises h->stream.
+  // sums them on the host: -> *total (and lists.total(1)).  Synchronises h->stream, on the ways out that fail too: nothing reads keys / slots
+  // or the count launch's own host arrays afterwards.
   template <typename Launch>
-  int count(er_tsdf_t h, const char* who, const std::vector<int>& keys, const std::vector<int>& slots, Launch count_launch, long* total) {
-    ER_W(who, hipMemcpyAsync(d_keys, keys.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    ER_W(who, hipMemcpyAsync(d_slots, slots.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    if (count_launch() || lists.read_counts(who, h->stream)) return 1;
-    ER_W(who, hipStreamSynchronize(h->stream));
+  int count(er_tsdf_t h, const char* who, Launch count_launch, long* total) {
+    auto enqueue = [&] {
+      ER_W(who, hipMemcpyAsync(d_keys, keys.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+      ER_W(who, hipMemcpyAsync(d_slots, slots.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+      return count_launch() || lists.read_counts(who, h->stream) ? 1 : 0;
+    };
+    const int rc = enqueue();
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    if (rc) return 1;
+    ER_W(who, e);
     lists.prefix();
     *total = lists.total(0);
     return 0;
@@ -595,40 +565,52 @@ struct SlabPass {
   int upload_offsets(er_tsdf_t h, const char* who) { return lists.upload_offsets(who, h->stream); }
 };
 
-int extract_points(er_tsdf_t h, float* out_host, long capacity, long* count, int surface) {
-  const char* who = "er_tsdf_extract_world";
-  if (!h || !count) return er::fail("er_tsdf_extract_world: NULL argument");
+// An extraction call that copies ONE list back to the host -- SaveWorld's voxels, the zero crossings, the triangle soup: the units, the count pass,
+// the refusal of a capacity that is too small (nothing has been written then), the write pass at the slabs' offsets, the copy back.  An element
+// is `per` Ts, called `what` in the refusal; launch(t, d_tab, out, pass) enqueues the list's kernel and returns 0, or non-zero after reporting;
+// d_tab is the marching-cubes case table on the device where `mc` asks for it.  Synchronises h->stream.
+template <typename T, typename Launch>
+int extract_list(er_tsdf_t h, const char* who, const char* what, bool mc, int per, T* out_host, long capacity, long* count, Launch launch) {
+  if (!h || !count) return er::fail("%s: NULL argument", who);
   ER_HIP_TRY(hipSetDevice(h->device));
-  std::vector<int> keys, slots;
-  if (sorted_units(h, keys, slots)) return 1;
-  const int n = (int)keys.size();
-  *count = 0;
-  if (n == 0) return 0;
-  const int nslab = n * 64;
   TwoPass lists;                               // (in this frame, outliving `own`: the call synchronises before it returns)
   DevScope own;
   SlabPass t(own, lists);
-  float4* d_out = nullptr;
+  if (t.units(h)) return 1;
+  *count = 0;
+  if (t.n == 0) return 0;
+  unsigned char* d_tab = nullptr;
+  T* d_out = nullptr;
   long total = 0;
-  auto launch = [&](float4* out, int pass) {
-    if (surface)
-      hipLaunchKernelGGL(k_surface, dim3(nslab), dim3(64), 0, h->stream, h->pool, t.d_slots, t.d_keys, h->ht_key, h->ht_slot, h->ht_cap - 1, h->ht_shift,
-                         t.cnt(), t.off(), out, pass);
-    else
-      hipLaunchKernelGGL(k_world, dim3(nslab), dim3(64), 0, h->stream, h->pool, t.d_slots, t.d_keys, t.cnt(), t.off(), out, pass);
-    ER_W(who, hipGetLastError());
-    return 0;
+  if (t.alloc(who)) return 1;
+  if (mc && own.alloc(&d_tab, 256 * 16, who)) return 1;
+  auto count_launch = [&] {
+    if (mc) ER_W(who, hipMemcpyAsync(d_tab, er::mc_table().tri, 256 * 16, hipMemcpyHostToDevice, h->stream));
+    return launch(t, d_tab, (T*)nullptr, 0);
   };
-  if (t.alloc(who, n) || t.count(h, who, keys, slots, [&] { return launch(nullptr, 0); }, &total)) return 1;
+  if (t.count(h, who, count_launch, &total)) return 1;
   *count = total;
   if (out_host && total > 0) {
-    if (capacity < total) return er::fail("er_tsdf_extract_world: capacity %ld < %ld points", capacity, total);
-    if (t.scope.alloc(&d_out, (size_t)total, who)) return 1;
-    if (t.upload_offsets(h, who) || launch(d_out, 1)) return 1;
-    ER_W(who, hipMemcpyAsync(out_host, d_out, (size_t)total * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
+    if (capacity < total) return er::fail("%s: capacity %ld < %ld %s", who, capacity, total, what);
+    if (own.alloc(&d_out, (size_t)total * per, who)) return 1;
+    if (t.upload_offsets(h, who) || launch(t, d_tab, d_out, 1)) return 1;
+    ER_W(who, hipMemcpyAsync(out_host, d_out, (size_t)total * per * sizeof(T), hipMemcpyDeviceToHost, h->stream));
     ER_W(who, hipStreamSynchronize(h->stream));
   }
   return 0;
+}
+
+int extract_points(er_tsdf_t h, float* out_host, long capacity, long* count, int surface) {
+  const char* who = "er_tsdf_extract_world";
+  return extract_list(h, who, "points", false, 1, reinterpret_cast<float4*>(out_host), capacity, count,
+                      [&](const SlabPass& t, const unsigned char*, float4* out, int pass) {
+                        if (surface)
+                          hipLaunchKernelGGL(k_surface, dim3(t.nslab), dim3(64), 0, h->stream, h->view(), t.d_slots, t.d_keys, t.cnt(), t.off(), out, pass);
+                        else
+                          hipLaunchKernelGGL(k_world, dim3(t.nslab), dim3(64), 0, h->stream, h->pool, t.d_slots, t.d_keys, t.cnt(), t.off(), out, pass);
+                        ER_W(who, hipGetLastError());
+                        return 0;
+                      });
 }
 
 // The oriented list on the device: *d_pts / *d_nrm are arrays of *total float4 that belong to t (both NULL when the list is empty or
@@ -636,26 +618,21 @@ int extract_points(er_tsdf_t h, float* out_host, long capacity, long* count, int
 int oriented_on_device(er_tsdf_t h, const char* who, bool want, SlabPass& t, float4** d_pts, float4** d_nrm, long* total_out) {
   *d_pts = *d_nrm = nullptr;
   *total_out = 0;
-  std::vector<int> keys, slots;
-  if (sorted_units(h, keys, slots)) return 1;
-  const int n = (int)keys.size();
-  if (n == 0) return 0;
-  const int nslab = n * 64;
+  if (t.units(h)) return 1;
+  if (t.n == 0) return 0;
   long total = 0;
   auto launch = [&](float4* out, int pass) {
-    hipLaunchKernelGGL(k_surface, dim3(nslab), dim3(64), 0, h->stream, h->pool, t.d_slots, t.d_keys, h->ht_key, h->ht_slot, h->ht_cap - 1, h->ht_shift,
-                       t.cnt(), t.off(), out, pass);
+    hipLaunchKernelGGL(k_surface, dim3(t.nslab), dim3(64), 0, h->stream, h->view(), t.d_slots, t.d_keys, t.cnt(), t.off(), out, pass);
     ER_W(who, hipGetLastError());
     return 0;
   };
-  if (t.alloc(who, n) || t.count(h, who, keys, slots, [&] { return launch(nullptr, 0); }, &total)) return 1;
+  if (t.alloc(who) || t.count(h, who, [&] { return launch(nullptr, 0); }, &total)) return 1;
   *total_out = total;
   if (want && total > 0) {
     if (t.scope.alloc(d_pts, (size_t)total, who)) return 1;
     if (t.scope.alloc(d_nrm, (size_t)total, who)) return 1;
     if (t.upload_offsets(h, who) || launch(*d_pts, 1)) return 1;
-    hipLaunchKernelGGL(k_surface_normals, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->pool, h->ht_key, h->ht_slot, h->ht_cap - 1,
-                       h->ht_shift, *d_pts, total, *d_nrm);
+    hipLaunchKernelGGL(k_surface_normals, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->view(), *d_pts, total, *d_nrm);
     ER_W(who, hipGetLastError());
     ER_W(who, hipStreamSynchronize(h->stream));
   }
@@ -745,42 +722,12 @@ int er_mc_table(unsigned char out[256 * 16]) {
 
 int er_tsdf_extract_mesh(er_tsdf_t h, float* tri_host, long capacity_triangles, long* n_triangles) {
   const char* who = "er_tsdf_extract_mesh";
-  if (!h || !n_triangles) return er::fail("er_tsdf_extract_mesh: NULL argument");
-  ER_HIP_TRY(hipSetDevice(h->device));
-  std::vector<int> keys, slots;
-  if (sorted_units(h, keys, slots)) return 1;
-  const int n = (int)keys.size();
-  *n_triangles = 0;
-  if (n == 0) return 0;
-  const int nslab = n * 64;
-  TwoPass lists;                               // (in this frame, outliving `own`: the call synchronises before it returns)
-  DevScope own;
-  SlabPass t(own, lists);
-  unsigned char* d_tab = nullptr;
-  float* d_out = nullptr;
-  long total = 0;
-  auto launch = [&](float* out, int pass) {
-    hipLaunchKernelGGL(k_mesh, dim3(nslab), dim3(64), 0, h->stream, h->pool, t.d_slots, t.d_keys, h->ht_key, h->ht_slot, h->ht_cap - 1, h->ht_shift, d_tab,
-                       t.cnt(), t.off(), out, pass);
-    ER_W(who, hipGetLastError());
-    return 0;
-  };
-  if (t.alloc(who, n)) return 1;
-  if (t.scope.alloc(&d_tab, 256 * 16, who)) return 1;
-  auto count_launch = [&] {
-    ER_W(who, hipMemcpyAsync(d_tab, er::mc_table().tri, 256 * 16, hipMemcpyHostToDevice, h->stream));
-    return launch(nullptr, 0);
-  };
-  if (t.count(h, who, keys, slots, count_launch, &total)) return 1;
-  *n_triangles = total;
-  if (tri_host && total > 0) {
-    if (capacity_triangles < total) return er::fail("er_tsdf_extract_mesh: capacity %ld < %ld triangles", capacity_triangles, total);
-    if (t.scope.alloc(&d_out, (size_t)total * 9, who)) return 1;
-    if (t.upload_offsets(h, who) || launch(d_out, 1)) return 1;
-    ER_W(who, hipMemcpyAsync(tri_host, d_out, (size_t)total * 9 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    ER_W(who, hipStreamSynchronize(h->stream));
-  }
-  return 0;
+  return extract_list(h, who, "triangles", true, 9, tri_host, capacity_triangles, n_triangles,
+                      [&](const SlabPass& t, const unsigned char* d_tab, float* out, int pass) {
+                        hipLaunchKernelGGL(k_mesh, dim3(t.nslab), dim3(64), 0, h->stream, h->view(), t.d_slots, t.d_keys, d_tab, t.cnt(), t.off(), out, pass);
+                        ER_W(who, hipGetLastError());
+                        return 0;
+                      });
 }
 
 int er_tsdf_extract_mesh_indexed(er_tsdf_t h, float* verts_host, float* normals_host, long capacity_vertices, int* tri_host,
@@ -810,27 +757,25 @@ int er_tsdf_extract_mesh_indexed(er_tsdf_t h, float* verts_host, float* normals_
 // first stage of er_tsdf_extract_mesh_cleaned (er_mesh_cc.hip), which goes on working on them in HBM.
 int er_tsdf_k::mesh_indexed_on_device(er_tsdf_t h, const char* who, bool want_v, bool want_n, bool want_t,
                                       long* n_vertices, long* n_triangles, const std::function<int(long, long)>& counted, DeviceMesh* m) {
-  std::vector<int> keys, slots;
-  if (sorted_units(h, keys, slots)) return 1;
-  const int n = (int)keys.size();
-  *n_vertices = *n_triangles = 0;
-  if (n == 0) return 0;                                     // (an empty volume: 0 and 0)
-  const int nslab = n * 64;
-  const size_t nrow = (size_t)nslab * 64;
   SlabPass t(m->owned, m->lists);         // every temporary belongs to the caller's mesh: the kernels that read them are in flight on return
+  if (t.units(h)) return 1;
+  *n_vertices = *n_triangles = 0;
+  if (t.n == 0) return 0;                                   // (an empty volume: 0 and 0)
+  const int nslab = t.nslab;
+  const size_t nrow = (size_t)nslab * 64;
   unsigned char* d_tab = nullptr;
   unsigned long long* d_bm = nullptr;     // [row][axis]: the edge bitmap
   int *d_rank = nullptr, *d_rowoff = nullptr;
   std::vector<int> rank((size_t)h->max_units, -1);           // pool slot -> position in the key order; -1: a dropped unit's slot
-  for (int r = 0; r < n; r++) rank[(size_t)slots[(size_t)r]] = r;
+  for (int r = 0; r < t.n; r++) rank[(size_t)t.slots[(size_t)r]] = r;
   long ntri = 0, nv = 0;
   auto launch = [&](int* out, int pass) {
-    hipLaunchKernelGGL(k_mesh_index, dim3(nslab), dim3(64), 0, h->stream, h->pool, t.d_slots, t.d_keys, h->ht_key, h->ht_slot, h->ht_cap - 1, h->ht_shift,
-                       d_tab, d_rank, d_bm, d_rowoff, t.off(1), t.cnt(), t.off(), out, pass);
+    hipLaunchKernelGGL(k_mesh_index, dim3(nslab), dim3(64), 0, h->stream, h->view(), t.d_slots, t.d_keys, d_tab, d_rank, d_bm, d_rowoff, t.off(1), t.cnt(),
+                       t.off(), out, pass);
     ER_W(who, hipGetLastError());
     return 0;
   };
-  if (t.alloc(who, n, 2)) return 1;                          // (the second list: the vertices of a slab)
+  if (t.alloc(who, 2)) return 1;                             // (the second list: the vertices of a slab)
   if (t.scope.alloc(&d_tab, 256 * 16, who)) return 1;
   if (t.scope.alloc(&d_bm, nrow * 3, who)) return 1;
   if (t.scope.alloc(&d_rank, rank.size(), who)) return 1;
@@ -844,7 +789,7 @@ int er_tsdf_k::mesh_indexed_on_device(er_tsdf_t h, const char* who, bool want_v,
     ER_W(who, hipGetLastError());
     return 0;
   };
-  if (t.count(h, who, keys, slots, count_launch, &ntri)) return 1;
+  if (t.count(h, who, count_launch, &ntri)) return 1;
   nv = t.lists.total(1);
   *n_vertices = m->nv = nv;
   *n_triangles = m->ntri = ntri;
@@ -853,13 +798,11 @@ int er_tsdf_k::mesh_indexed_on_device(er_tsdf_t h, const char* who, bool want_v,
   if (t.upload_offsets(h, who)) return 1;                    // (of both lists)
   if (want_v) {
     if (t.scope.alloc(&m->d_verts, (size_t)nv, who)) return 1;
-    hipLaunchKernelGGL(k_mesh_verts, dim3(nslab), dim3(64), 0, h->stream, h->pool, t.d_slots, t.d_keys, h->ht_key, h->ht_slot, h->ht_cap - 1, h->ht_shift,
-                       d_bm, d_rowoff, t.off(1), m->d_verts);
+    hipLaunchKernelGGL(k_mesh_verts, dim3(nslab), dim3(64), 0, h->stream, h->view(), t.d_slots, t.d_keys, d_bm, d_rowoff, t.off(1), m->d_verts);
     ER_W(who, hipGetLastError());
     if (want_n) {
       if (t.scope.alloc(&m->d_nrm, (size_t)nv, who)) return 1;
-      hipLaunchKernelGGL(k_surface_normals, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, h->stream, h->pool, h->ht_key, h->ht_slot, h->ht_cap - 1,
-                         h->ht_shift, m->d_verts, nv, m->d_nrm);
+      hipLaunchKernelGGL(k_surface_normals, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, h->stream, h->view(), m->d_verts, nv, m->d_nrm);
       ER_W(who, hipGetLastError());
     }
   }
@@ -899,7 +842,7 @@ int er_tsdf_import_world(er_tsdf_t h, const float* xyzi_host, long n, int* n_uni
       g[a] = (int)c + 256 * 64;
     }
     if (p[3] != p[3]) return er::fail("er_tsdf_import_world: row %ld: the intensity is NaN", r);
-    const int key = (g[0] >> 6) << 18 | (g[1] >> 6) << 9 | (g[2] >> 6);
+    const int key = unit_key_of(g[0], g[1], g[2]);
     if (key != last) ukeys.push_back(last = key);
   }
   std::sort(ukeys.begin(), ukeys.end());
@@ -922,8 +865,7 @@ int er_tsdf_import_world(er_tsdf_t h, const float* xyzi_host, long n, int* n_uni
   for (long r0 = 0; r0 < n; r0 += chunk) {
     const long m = std::min(chunk, n - r0);
     ER_W(who, hipMemcpyAsync(d_rows, xyzi_host + 4 * r0, (size_t)m * sizeof(float4), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_import_world, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, h->pool, h->ht_key, h->ht_slot, h->ht_cap - 1,
-                       h->ht_shift, d_rows, m);
+    hipLaunchKernelGGL(k_import_world, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, h->pool, h->view().map, d_rows, m);
     ER_W(who, hipGetLastError());
     ER_W(who, hipStreamSynchronize(h->stream));             // (the host rows may be pageable, the staging buffer is reused)
   }

@@ -27,25 +27,25 @@ using namespace er_tsdf_k;
 constexpr int kTilePx = 8;                    // a wave's tile is kTilePx x kTilePx pixels
 constexpr int kGroupPx = 2 * kTilePx;         // a workgroup's is 2 x 2 of them
 
+static_assert(er_rc::kLattice == kLatticeVox, "one lattice");
+
 struct DeviceVol {
-  const float2* __restrict__ pool;
-  const int* __restrict__ ht_key;
-  const int* __restrict__ ht_slot;
-  int cap_mask, shift, max_units;
+  VolumeView vol;
+  int max_units;
   int ckey, cslot;                            // the unit sampled last (ckey = kEmptyKey: none yet) and its slot, < 0 = it does not exist
   int ux, uy, uz;                             // its lattice position
 
   __device__ __forceinline__ bool fetch(int gx, int gy, int gz, float& F) {
-    if ((unsigned)gx >= (unsigned)er_rc::kLattice || (unsigned)gy >= (unsigned)er_rc::kLattice || (unsigned)gz >= (unsigned)er_rc::kLattice) return false;
-    const int key = (gx >> 6) << 18 | (gy >> 6) << 9 | (gz >> 6);
+    if (!on_lattice(gx, gy, gz)) return false;
+    const int key = unit_key_of(gx, gy, gz);
     if (key != ckey) {
-      const int s = ht_lookup_slot(ht_key, ht_slot, cap_mask, shift, key);
+      const int s = vol.map.slot(key);
       ckey = key;
       cslot = s < max_units ? s : -1;
       ux = gx >> 6, uy = gy >> 6, uz = gz >> 6;
     }
     if (cslot < 0) return false;
-    const float2 v = pool[(size_t)cslot * kUnitVox + ((size_t)(gx & 63) * 4096 + (size_t)(gy & 63) * 64 + (size_t)(gz & 63))];
+    const float2 v = vol.unit(cslot)[unit_offset_of(gx, gy, gz)];
     F = v.x;
     return v.y != 0.0f;
   }
@@ -54,20 +54,18 @@ struct DeviceVol {
   __device__ __forceinline__ int advance(float px, float py, float pz, float step) {
     int gx, gy, gz;
     if (!(er_rc::nearest_index(px, gx) & er_rc::nearest_index(py, gy) & er_rc::nearest_index(pz, gz))) return 1;
-    if (cslot >= 0 || ckey != ((gx >> 6) << 18 | (gy >> 6) << 9 | (gz >> 6))) return 1;
+    if (cslot >= 0 || ckey != unit_key_of(gx, gy, gz)) return 1;
     return er_rc::skip_steps(px, py, pz, ux, uy, uz, step);
   }
 };
 
-__global__ __launch_bounds__(kGroupPx * kGroupPx) void k_raycast(const float2* __restrict__ pool, const int* __restrict__ ht_key,
-                                                                 const int* __restrict__ ht_slot, int cap_mask, int shift, int max_units,
-                                                                 er_rc::Image I, int cols, int rows, float4* __restrict__ rec,
-                                                                 uint16_t* __restrict__ depth) {
+__global__ __launch_bounds__(kGroupPx * kGroupPx) void k_raycast(VolumeView volume, int max_units, er_rc::Image I, int cols, int rows,
+                                                                 float4* __restrict__ rec, uint16_t* __restrict__ depth) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int u = blockIdx.x * kGroupPx + (wave & 1) * kTilePx + (lane & 7);
   const int v = blockIdx.y * kGroupPx + (wave >> 1) * kTilePx + (lane >> 3);
   if (u >= cols || v >= rows) return;
-  DeviceVol vol{pool, ht_key, ht_slot, cap_mask, shift, max_units, kEmptyKey, -1, 0, 0, 0};
+  DeviceVol vol{volume, max_units, kEmptyKey, -1, 0, 0, 0};
   er_rc::Pixel px;
   er_rc::cast_pixel(vol, I, u, v, px);
   const size_t i = (size_t)v * cols + u;
@@ -80,12 +78,10 @@ __global__ __launch_bounds__(kGroupPx * kGroupPx) void k_raycast(const float2* _
 
 // One job of k_raycast_batch: what k_raycast takes as arguments.
 struct RayJob {
-  const float2* pool;
-  const int* ht_key;
-  const int* ht_slot;
+  VolumeView vol;
   float4* rec;
   uint16_t* depth;
-  int cap_mask, shift, max_units, cols, rows;
+  int max_units, cols, rows;
   er_rc::Image I;
 };
 static_assert(sizeof(RayJob) == 136, "five pointers, five ints and the image: the job table is read with scalar loads, keep it small");
@@ -98,7 +94,7 @@ __global__ __launch_bounds__(kGroupPx * kGroupPx) void k_raycast_batch(const Ray
   const int u = blockIdx.x * kGroupPx + (wave & 1) * kTilePx + (lane & 7);
   const int v = blockIdx.y * kGroupPx + (wave >> 1) * kTilePx + (lane >> 3);
   if (u >= cols || v >= rows) return;
-  DeviceVol vol{J.pool, J.ht_key, J.ht_slot, J.cap_mask, J.shift, J.max_units, kEmptyKey, -1, 0, 0, 0};
+  DeviceVol vol{J.vol, J.max_units, kEmptyKey, -1, 0, 0, 0};
   const er_rc::Image I = J.I;
   float4* __restrict__ rec = J.rec;
   uint16_t* __restrict__ depth = J.depth;
@@ -185,7 +181,7 @@ int er_tsdf_raycast(er_tsdf_t h, int cols, int rows, const float cam4[4], const 
     if (depth_out) d_depth = (uint16_t*)(tmp + npix * 2 * sizeof(float4));
   }
   hipLaunchKernelGGL(k_raycast, dim3((cols + kGroupPx - 1) / kGroupPx, (rows + kGroupPx - 1) / kGroupPx), dim3(kGroupPx * kGroupPx), 0, h->stream,
-                     h->pool, h->ht_key, h->ht_slot, h->ht_cap - 1, h->ht_shift, h->max_units, I, cols, rows, d_rec, d_depth);
+                     h->view(), h->max_units, I, cols, rows, d_rec, d_depth);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && !out_on_device && rec_out) e = hipMemcpyAsync(rec_out, d_rec, npix * 2 * sizeof(float4), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess && !out_on_device && depth_out) e = hipMemcpyAsync(depth_out, d_depth, npix * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream);
@@ -241,13 +237,9 @@ int er_tsdf_raycast_batch(int n_jobs, const er_tsdf_t* vol, const int* cols, con
     if (params) P = params[j];
     er_tsdf_t h = vol[j];
     RayJob& J = jobs.host[j];
-    J.pool = h->pool;
-    J.ht_key = h->ht_key;
-    J.ht_slot = h->ht_slot;
+    J.vol = h->view();
     J.rec = rec_out_dev ? (float4*)rec_out_dev[j] : nullptr;
     J.depth = depth_out_dev ? depth_out_dev[j] : nullptr;
-    J.cap_mask = h->ht_cap - 1;
-    J.shift = h->ht_shift;
     J.max_units = h->max_units;
     J.cols = cols[j];
     J.rows = rows[j];

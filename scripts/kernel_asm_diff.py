@@ -8,7 +8,11 @@ Kernels are matched by their demangled name with template arguments and paramete
 anonymous namespace and a named one).  For every kernel that is not a library's (rocprim / hipcub) the instruction text must be the same --
 comments and assembler directives dropped, local labels renumbered in order of appearance -- and so must .vgpr_count, .sgpr_count,
 .group_segment_fixed_size and .private_segment_fixed_size of its metadata.  The set of library kernels must be the same on both sides and,
-with --library-in STEM, every one of them defined only in the new file of that stem.  Prints one table row per kernel; exit status 1 on any difference."""
+with --library-in STEM, every one of them defined only in the new file of that stem.  Prints one table row per kernel, a figure that moved as
+"old -> new"; exit status 1 on any difference.
+
+A change that edits a kernel's parameter list changes its signature, and the kernel would show as "only in the old build" and "only in the new
+build".  --by-name pairs kernels by name and template arguments alone, so such a change reports as one row per kernel."""
 import argparse
 import os
 import re
@@ -89,7 +93,7 @@ def normalise(text, names):
     return out
 
 
-def load(paths):
+def load(paths, by_name=False):
     """-> {normalised signature: (file stem, instruction lines, metadata)}, {library signature: set of file stems}"""
     own, lib = {}, {}
     for p in paths:
@@ -105,6 +109,8 @@ def load(paths):
             if LIBRARY.search(sig):
                 lib.setdefault(sig, set()).add(stem)
                 continue
+            if by_name:
+                sig = short(sig)
             if sig in own:
                 sys.exit("kernel defined twice: %s (%s, %s)" % (sig, own[sig][0], stem))
             own[sig] = (stem, normalise(text, names), meta)
@@ -121,9 +127,11 @@ def main():
     ap.add_argument("--old", nargs="+", required=True)
     ap.add_argument("--new", nargs="+", required=True)
     ap.add_argument("--library-in", default=None, help="stem of the one new file that may define rocprim / hipcub kernels")
+    ap.add_argument("--by-name", action="store_true",
+                    help="pair kernels by name and template arguments alone: for a change that edits parameter lists (two kernels of one name then count as defined twice)")
     a = ap.parse_args()
-    old, old_lib = load(a.old)
-    new, new_lib = load(a.new)
+    old, old_lib = load(a.old, a.by_name)
+    new, new_lib = load(a.new, a.by_name)
     if not old or not new:
         sys.exit("no kernels found in the %s files" % ("old" if not old else "new"))
     bad = 0
@@ -142,8 +150,13 @@ def main():
             verdict = "; ".join(what) or "identical"
         bad += verdict != "identical"
         k = n or o
-        count = sum(1 for l in k[1] if not l.endswith(":"))
-        print("| %s | %s | %d | %s | %s | %s | %s | %s |" % ((short(sig), k[0], count) + tuple(k[2].get(f) for f in META) + (verdict,)))
+
+        def cell(get):                                            # "old -> new" where both builds have the kernel and the figure moved
+            vals = [get(x) for x in (o, n) if x is not None]
+            return str(vals[0]) if len(set(vals)) == 1 else "%s -> %s" % tuple(vals)
+
+        cells = [cell(lambda x: sum(1 for l in x[1] if not l.endswith(":")))] + [cell(lambda x, f=f: x[2].get(f)) for f in META]
+        print("| %s | %s | %s | %s |" % (short(sig), k[0], " | ".join(cells), verdict))
     print()
     print("%d kernels compared, %d not identical" % (len(set(old) | set(new)), bad))
     if set(old_lib) != set(new_lib):
