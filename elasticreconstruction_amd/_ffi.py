@@ -17,7 +17,7 @@ SYMBOLS = [
     "er_tsdf_wait_event", "er_tsdf_reset", "er_tsdf_status", "er_tsdf_set_unit_shard", "er_unit_owner",
     "er_tsdf_scale_depth", "er_tsdf_reproject", "er_tsdf_integrate", "er_tsdf_integrate_frames", "er_tsdf_prepass_trace", "er_tsdf_set_zbuf_epoch",
     "er_tsdf_unit_count", "er_tsdf_unit_keys", "er_tsdf_read_unit", "er_tsdf_sum_weight",
-    "er_tsdf_extract_world", "er_tsdf_extract_surface", "er_tsdf_extract_oriented", "er_tsdf_extract_mesh", "er_mc_table", "er_tsdf_extract_mesh_indexed", "er_mesh_components", "er_tsdf_extract_mesh_cleaned", "er_mesh_simplify", "er_tsdf_extract_mesh_simplified", "er_tsdf_import_world", "er_raycast_params_default", "er_tsdf_raycast", "er_tsdf_raycast_batch", "er_tsdf_export_weighted", "er_tsdf_import_weighted",
+    "er_tsdf_extract_world", "er_tsdf_extract_surface", "er_tsdf_extract_oriented", "er_tsdf_extract_mesh", "er_mc_table", "er_tsdf_extract_mesh_indexed", "er_mesh_components", "er_tsdf_extract_mesh_cleaned", "er_mesh_simplify", "er_tsdf_extract_mesh_simplified", "er_mesh_smooth", "er_tsdf_extract_mesh_smoothed", "er_tsdf_import_world", "er_raycast_params_default", "er_tsdf_raycast", "er_tsdf_raycast_batch", "er_tsdf_export_weighted", "er_tsdf_import_weighted",
     "er_tsdf_export_raw", "er_tsdf_import_raw",
     "er_tsdf_color_enable", "er_tsdf_read_unit_color", "er_tsdf_write_unit_color", "er_tsdf_color_frames", "er_tsdf_reproject_color", "er_tsdf_sample_colors",
     "er_tsdf_band_sizes", "er_tsdf_export_band", "er_tsdf_merge_band", "er_tsdf_import_band", "er_tsdf_drop_units",
@@ -147,6 +147,11 @@ def lib():
         lp = C.POINTER(C.c_long)
         L.er_mesh_simplify.argtypes = [vp, vp, vp, C.c_long, vp, C.c_long, C.c_float, C.c_int, vp, vp, vp, vp, C.c_long, vp, vp, C.c_long, vp, lp, lp, vp, vp]
         L.er_tsdf_extract_mesh_simplified.argtypes = [vp, C.c_float, C.c_long, C.c_int, C.c_int, vp, vp, vp, vp, C.c_long, vp, C.c_long, lp, lp, vp, vp, vp]
+    if hasattr(L, "er_mesh_smooth"):
+        lp = C.POINTER(C.c_long)
+        L.er_mesh_smooth.argtypes = [vp, C.c_long, vp, C.c_long, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
+        L.er_tsdf_extract_mesh_smoothed.argtypes = [vp, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, C.c_long, C.c_int, C.c_int, vp, vp, vp, C.c_long, vp,
+                                                    C.c_long, lp, lp, vp, vp, vp]
     if hasattr(L, "er_tsdf_raycast"):                           # (absent from an older build selected with ER_HIP_LIB)
         L.er_raycast_params_default.argtypes = [C.POINTER(ErRaycastParams)]
         L.er_tsdf_raycast.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.POINTER(ErRaycastParams), vp, vp, C.c_int]

@@ -307,25 +307,11 @@ unsigned long sc_table_size(long n) {
   return size;
 }
 
-struct ScWant {
-  bool verts, nrm, rgba, members, tri, tri_index, cluster;
-  bool any() const { return verts || nrm || rgba || members || tri || tri_index || cluster; }
-};
+}  // namespace
 
-// What the clustering leaves in device memory: every array belongs to `owned` of the call and is NULL when it was not asked for.
-struct ScMesh {
-  long nv = 0, ntri = 0;
-  long stats[4] = {0, 0, 0, 0};
-  long probes[2] = {0, 0};
-  float4 *d_verts = nullptr, *d_nrm = nullptr;
-  uchar4* d_rgba = nullptr;
-  int *d_members = nullptr, *d_tri = nullptr, *d_tri_index = nullptr, *d_cluster = nullptr;
-  TwoPass lists;                                               // the vertex and the triangle list between their passes
-};
+namespace er_tsdf_k {
 
-// The clustering of nv > 0 vertices (d_nrm, d_rgba nullable) and nt > 0 triangles in device memory, on stream s, which it synchronises twice.
-// The refusals of the input come first; then the counts and stats are set and counted(*out) refuses what the caller has to refuse (non-zero
-// ends the call with 1); then the arrays of `want` are made.  Temporaries and results go to `owned`.
+// (declared in er_mesh.h)
 int simplify_on_device(const char* who, hipStream_t s, const float4* d_verts, const float4* d_nrm, const uchar4* d_rgba, long nv, const int* d_tri, long nt,
                        float cell, const ScWant& want, const std::function<int(const ScMesh&)>& counted, er::DevScope& owned, ScMesh* out) {
   // the first offenders
@@ -456,7 +442,6 @@ int simplify_on_device(const char* who, hipStream_t s, const float4* d_verts, co
   return 0;
 }
 
-// The way back of whatever simplify_on_device left, on stream s, which it synchronises.
 int sc_copy_back(const char* who, hipStream_t s, const ScMesh& r, long nv_in, float* verts, float* nrm, uint8_t* rgba, int* members, int* tri, int* tri_index,
                  int* cluster) {
   if (verts && r.d_verts) ER_W(who, hipMemcpyAsync(verts, r.d_verts, (size_t)r.nv * sizeof(float4), hipMemcpyDeviceToHost, s));
@@ -470,7 +455,7 @@ int sc_copy_back(const char* who, hipStream_t s, const ScMesh& r, long nv_in, fl
   return 0;
 }
 
-}  // namespace
+}  // namespace er_tsdf_k
 
 extern "C" {
 

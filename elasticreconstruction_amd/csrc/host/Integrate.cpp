@@ -26,6 +26,8 @@
 //                         (er_tsdf_extract_mesh_indexed; bin/MeshOutput makes the same kind of file from world.pcd); single-GPU runs only
 //   --mesh_min_triangles <n>, --mesh_largest_only   with --save_mesh: the mesh without the connected components that have fewer than n
 //                         triangles / without all but the largest (er_tsdf_extract_mesh_cleaned); refused without --save_mesh
+//   --mesh_smooth <n> [--mesh_smooth_lambda <l>] [--mesh_smooth_mu <m>] [--mesh_smooth_fix_boundary]  with --save_mesh: n Taubin iterations
+//                        on that mesh in device memory, before the clustering (er_tsdf_extract_mesh_smoothed)
 //   --mesh_cell <metres>  with --save_mesh: that mesh simplified by vertex clustering, one vertex per occupied cell of that size
 //                         (er_tsdf_extract_mesh_simplified: the unsimplified mesh never leaves the device); refused without --save_mesh
 //   --color_raw <file> | --color_list <txt>   the colour stream registered to the depth stream: raw 640x480x3 bytes per frame,
@@ -86,6 +88,8 @@ int print_help() {
   std::cout << "    --mesh_min_triangles <n>        : with --save_mesh: drop the connected components of the mesh that have fewer than n triangles" << std::endl;
   std::cout << "    --mesh_largest_only             : with --save_mesh: keep only the connected component with the most triangles" << std::endl;
   std::cout << "    --mesh_cell <metres>            : with --save_mesh: simplify the mesh by vertex clustering, one vertex per cell of that size" << std::endl;
+  std::cout << "    --mesh_smooth <n>               : with --save_mesh: n Taubin iterations on the mesh, after the cleaning and before the clustering" << std::endl;
+  std::cout << "    --mesh_smooth_lambda <l>, --mesh_smooth_mu <m>, --mesh_smooth_fix_boundary : its two factors (0.5, -0.53); hold the boundary vertices" << std::endl;
   std::cout << "    --color_raw <raw_file> | --color_list <txt> : 640x480x3 bytes per frame | 8-bit RGB PNG per line; needs --save_mesh, which then writes colours (single GPU only)" << std::endl;
   std::cout << "    --gpus <N> (1)  --shard frame|unit (frame: frame blocks + the merge by unit owner over RCCL; unit: bit-exact, no collective)  --merge_root <g>  --force_merge" << std::endl;
   return 0;
@@ -415,7 +419,11 @@ struct App {
   // min_triangles > 1 or largest_only: without its small connected components (er_tsdf_extract_mesh_cleaned; the unfiltered mesh stays on the device)
   // cell > 0: that mesh simplified by vertex clustering in device memory (er_tsdf_extract_mesh_simplified; colours are sampled at the
   // unsimplified vertices and averaged per cluster)
-  bool SaveMesh(const std::string& filename, long min_triangles = 0, bool largest_only = false, float cell = 0.0f) {
+  // smooth.iterations > 0: Taubin smoothing after the cleaning and before the clustering, all in device memory (er_tsdf_extract_mesh_smoothed;
+  // colours are sampled at the unsmoothed vertices, the normals are those of the smoothed triangles)
+  bool SaveMesh(const std::string& filename, long min_triangles = 0, bool largest_only = false, float cell = 0.0f,
+                const erfmt::SmoothOptions& smooth = erfmt::SmoothOptions()) {
+    if (smooth.iterations > 0) return SaveSmoothedMesh(filename, min_triangles, largest_only, cell, smooth);
     if (cell > 0.0f) return SaveSimplifiedMesh(filename, min_triangles, largest_only, cell);
     long nv = 0, nt = 0, stats[4] = {0, 0, 0, 0};
     const bool clean = min_triangles > 1 || largest_only;
@@ -455,6 +463,30 @@ struct App {
     erfmt::stage_done("mesh simplification (er_tsdf_extract_mesh_simplified)");
     printf("mesh simplified with cells of %g m: %ld vertices and %ld triangles in %ld cells -> %ld vertices and %ld triangles (%ld degenerate and %ld duplicate triangles, %ld cells dropped).\n",
            (double)cell, before[0], before[1], stats[0], nv, nt, stats[1], stats[2], stats[3]);
+    static const float none[4] = {0.f, 0.f, 0.f, 0.f};                 // (an empty mesh still declares nx ny nz)
+    if (!erfmt::save_ply(filename, verts.data(), 4, nv > 0 ? nrm.data() : none, 4, (size_t)nv, tris.data(), (size_t)nt, true, color_ ? rgba.data() : nullptr)) { fprintf(stderr, "Integrate: cannot write %s\n", filename.c_str()); return false; }
+    printf("%ld mesh vertices and %ld triangles have been written.\n", nv, nt);
+    return true;
+  }
+
+  bool SaveSmoothedMesh(const std::string& filename, long min_triangles, bool largest_only, float cell, const erfmt::SmoothOptions& sm) {
+    long nv = 0, nt = 0, smooth_stats[4] = {0, 0, 0, 0}, stats[4] = {0, 0, 0, 0}, before[2] = {0, 0};
+    auto extract = [&](float* v, float* q, uint8_t* c, int* t) {
+      return er_tsdf_extract_mesh_smoothed(volume_, sm.iterations, sm.lambda, sm.mu, sm.fix_boundary ? 1 : 0, cell, min_triangles, largest_only ? 1 : 0,
+                                           color_ ? 1 : 0, v, q, c, nv, t, nt, &nv, &nt, smooth_stats, stats, before);
+    };
+    if (extract(nullptr, nullptr, nullptr, nullptr) != 0) { fprintf(stderr, "Integrate: %s\n", er_last_error()); return false; }
+    std::vector<float> verts((size_t)nv * 4), nrm((size_t)nv * 4);
+    std::vector<int> tris((size_t)nt * 3);
+    std::vector<uint8_t> rgba((size_t)nv * 4 + 4);
+    if (nv > 0 && extract(verts.data(), nrm.data(), color_ ? rgba.data() : nullptr, tris.data()) != 0) { fprintf(stderr, "Integrate: %s\n", er_last_error()); return false; }
+    erfmt::stage_done("mesh smoothing (er_tsdf_extract_mesh_smoothed)");
+    printf("mesh smoothed with %d iterations of lambda %g, mu %g%s: %ld vertices and %ld triangles, %ld edges (%ld boundary, %ld non-manifold), %ld vertices held.\n",
+           sm.iterations, (double)sm.lambda, (double)sm.mu, sm.fix_boundary ? ", boundary fixed" : "", before[0], before[1], smooth_stats[0], smooth_stats[1],
+           smooth_stats[2], smooth_stats[3]);
+    if (cell > 0.0f)
+      printf("mesh simplified with cells of %g m: %ld vertices and %ld triangles in %ld cells -> %ld vertices and %ld triangles (%ld degenerate and %ld duplicate triangles, %ld cells dropped).\n",
+             (double)cell, before[0], before[1], stats[0], nv, nt, stats[1], stats[2], stats[3]);
     static const float none[4] = {0.f, 0.f, 0.f, 0.f};                 // (an empty mesh still declares nx ny nz)
     if (!erfmt::save_ply(filename, verts.data(), 4, nv > 0 ? nrm.data() : none, 4, (size_t)nv, tris.data(), (size_t)nt, true, color_ ? rgba.data() : nullptr)) { fprintf(stderr, "Integrate: cannot write %s\n", filename.c_str()); return false; }
     printf("%ld mesh vertices and %ld triangles have been written.\n", nv, nt);
@@ -568,6 +600,8 @@ int main(int argc, char* argv[]) {
   const bool mesh_cell_given = find_argument(argc, argv, "--mesh_cell") > 0;
   parse_argument(argc, argv, "--mesh_cell", mesh_cell_text);
   float mesh_cell = 0.0f;
+  erfmt::SmoothOptions mesh_smooth;                                     // --mesh_smooth N [--mesh_smooth_lambda L] [--mesh_smooth_mu M] [--mesh_smooth_fix_boundary]
+  if (!erfmt::parse_smooth(argc, argv, "Integrate", "--mesh_smooth", &mesh_smooth)) return 1;
   std::string color_raw, color_list;                                    // --color_raw <file> | --color_list <txt>: the colour stream
   parse_argument(argc, argv, "--color_raw", color_raw);
   parse_argument(argc, argv, "--color_list", color_list);
@@ -595,6 +629,7 @@ int main(int argc, char* argv[]) {
   }
   if (mesh_clean_given && mesh_file.empty()) { fprintf(stderr, "Integrate: --mesh_min_triangles / --mesh_largest_only need --save_mesh\n"); return 1; }
   if (mesh_min_triangles < 0) { fprintf(stderr, "Integrate: --mesh_min_triangles must not be negative\n"); return 1; }
+  if (mesh_smooth.given && mesh_file.empty()) { fprintf(stderr, "Integrate: --mesh_smooth needs --save_mesh\n"); return 1; }
   if (mesh_cell_given && mesh_file.empty()) { fprintf(stderr, "Integrate: --mesh_cell needs --save_mesh\n"); return 1; }
   if (mesh_cell_given && !parse_cell(mesh_cell_text, &mesh_cell)) { fprintf(stderr, "Integrate: --mesh_cell needs a finite size above 0, in metres\n"); return 1; }
   if (color) {
@@ -733,7 +768,7 @@ int main(int argc, char* argv[]) {
     stage_done("SaveFragment");
   }
   if (rc == 0 && !mesh_file.empty()) {
-    if (!apps[0].SaveMesh(mesh_file, mesh_min_triangles, mesh_largest_only, mesh_cell)) rc = 1;
+    if (!apps[0].SaveMesh(mesh_file, mesh_min_triangles, mesh_largest_only, mesh_cell, mesh_smooth)) rc = 1;
     stage_done("SaveMesh");
   }
   std::cout << "Total " << last_id << " frames processed." << std::endl;

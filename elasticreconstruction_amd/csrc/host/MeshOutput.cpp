@@ -1,7 +1,8 @@
 // MeshOutput -- the last box of the reference workflow (README.txt:100-103: "pcl_kinfu_largeScale_mesh_output world.pcd", a tool of the
 // author's PCL fork, outside the reference tree): world.pcd in, a triangle mesh out, with the numeric core on MI355X through liber_hip.so.
 //
-//   MeshOutput <world.pcd> [--save_to mesh.ply] [--ascii] [--no_normals] [--min_triangles N] [--largest_only] [--cell C] [--device D]
+//   MeshOutput <world.pcd> [--save_to mesh.ply] [--ascii] [--no_normals] [--min_triangles N] [--largest_only] [--cell C]
+//              [--smooth N [--smooth_lambda L] [--smooth_mu M] [--smooth_fix_boundary]] [--device D]
 //
 // world.pcd is TSDFVolume::SaveWorld's voxel list (FIELDS x y z intensity; ascii, binary or binary_compressed): integer voxel indices and
 // the sdf.  The list goes back into a volume sized from its own unit keys (er_tsdf_import_world: every listed voxel observed with weight 1),
@@ -11,7 +12,9 @@
 // `Integrate --save_mesh`, which reads the resident volume.  --min_triangles N drops the connected components of the mesh that have fewer than
 // N triangles, --largest_only all but the one with the most (er_tsdf_extract_mesh_cleaned: the unfiltered mesh never leaves the device);
 // without the two the file is the unfiltered mesh.  --cell C simplifies what is left by vertex clustering, one vertex per occupied cell of C
-// metres (er_tsdf_extract_mesh_simplified, in device memory too).  ER_TIMING=1 prints the stages.
+// metres (er_tsdf_extract_mesh_simplified, in device memory too).  --smooth N runs N Taubin iterations (a pass with --smooth_lambda, 0.5, then
+// a pass with --smooth_mu, -0.53; --smooth_fix_boundary holds the boundary vertices) after the cleaning and before the clustering, and the
+// normals become those of the smoothed triangles (er_tsdf_extract_mesh_smoothed).  ER_TIMING=1 prints the stages.
 #include <cmath>
 #include <cstdio>
 #include <string>
@@ -33,6 +36,10 @@ int print_help() {
          "  --min_triangles <n> (=0)  drop the connected components of the mesh that have fewer than n triangles\n"
          "  --largest_only            keep only the connected component with the most triangles\n"
          "  --cell <metres>           simplify the mesh by vertex clustering: one vertex per occupied cell of that size\n"
+         "  --smooth <n>              smooth the mesh with n Taubin iterations (after the cleaning, before the clustering)\n"
+         "  --smooth_lambda <l> (=0.5)   the factor of an iteration's first pass, at most 1 in magnitude\n"
+         "  --smooth_mu <m> (=-0.53)     the factor of its second pass; 0 gives plain Laplacian smoothing\n"
+         "  --smooth_fix_boundary     boundary vertices stay where they are\n"
          "  --device <gpu> (=0)\n"
          "  -h [ --help ]             print this message\n");
   return 0;
@@ -64,6 +71,9 @@ int main(int argc, char** argv) {
     fprintf(stderr, "%s: --cell needs a finite size above 0, in metres\n", kWho);
     return 1;
   }
+  SmoothOptions sm;
+  if (!parse_smooth(argc, argv, kWho, "--smooth", &sm)) return 1;
+  const bool smooth = sm.given && sm.iterations > 0;
 
   std::vector<std::vector<float>> cols;
   size_t n = 0;
@@ -110,12 +120,15 @@ int main(int argc, char** argv) {
   }
   stage_done("HIP runtime up, volume created");
   int rc = 0, n_units = 0;
-  long nv = 0, nt = 0, stats[4] = {0, 0, 0, 0}, before[2] = {0, 0};
+  long nv = 0, nt = 0, stats[4] = {0, 0, 0, 0}, before[2] = {0, 0}, smooth_stats[4] = {0, 0, 0, 0};
   std::vector<float> verts, nrm;
   std::vector<int> tris;
   if (er_tsdf_import_world(vol, rows.data(), (long)n, &n_units) != 0) rc = 1;
   stage_done("import (er_tsdf_import_world)");
   auto extract = [&](float* v, float* q, int* t) {
+    if (smooth)
+      return er_tsdf_extract_mesh_smoothed(vol, sm.iterations, sm.lambda, sm.mu, sm.fix_boundary ? 1 : 0, cell, min_triangles, largest_only ? 1 : 0, 0, v, q, nullptr,
+                                           nv, t, nt, &nv, &nt, smooth_stats, stats, before);
     if (simplify)
       return er_tsdf_extract_mesh_simplified(vol, cell, min_triangles, largest_only ? 1 : 0, 0, v, q, nullptr, nullptr, nv, t, nt, &nv, &nt, stats, before, nullptr);
     return clean ? er_tsdf_extract_mesh_cleaned(vol, min_triangles, largest_only ? 1 : 0, v, q, nullptr, nv, t, nt, &nv, &nt, stats)
@@ -128,7 +141,7 @@ int main(int argc, char** argv) {
     tris.resize((size_t)nt * 3);
     if (extract(verts.data(), no_normals ? nullptr : nrm.data(), tris.data()) != 0) rc = 1;
   }
-  stage_done(simplify ? "mesh and simplification (er_tsdf_extract_mesh_simplified)" : clean ? "mesh and cleaning (er_tsdf_extract_mesh_cleaned)" : "mesh (er_tsdf_extract_mesh_indexed)");
+  stage_done(smooth ? "mesh and smoothing (er_tsdf_extract_mesh_smoothed)" : simplify ? "mesh and simplification (er_tsdf_extract_mesh_simplified)" : clean ? "mesh and cleaning (er_tsdf_extract_mesh_cleaned)" : "mesh (er_tsdf_extract_mesh_indexed)");
   if (rc != 0) {
     fprintf(stderr, "%s: %s\n", kWho, er_last_error());
     er_tsdf_destroy(vol);
@@ -141,10 +154,14 @@ int main(int argc, char** argv) {
     return 1;
   }
   stage_done("write PLY");
+  if (smooth)
+    printf("%s: %d iterations of lambda %g, mu %g%s: %ld vertices and %ld triangles, %ld edges (%ld boundary, %ld non-manifold), %ld vertices held\n", kWho,
+           sm.iterations, (double)sm.lambda, (double)sm.mu, sm.fix_boundary ? ", boundary fixed" : "", before[0], before[1], smooth_stats[0], smooth_stats[1],
+           smooth_stats[2], smooth_stats[3]);
   if (simplify)
     printf("%s: cells of %g m: %ld vertices and %ld triangles in %ld cells -> %ld vertices and %ld triangles (%ld degenerate and %ld duplicate triangles, %ld cells dropped)\n",
            kWho, (double)cell, before[0], before[1], stats[0], nv, nt, stats[1], stats[2], stats[3]);
-  else if (clean) printf("%s: %ld of %ld components kept, %ld vertices and %ld triangles dropped\n", kWho, stats[1], stats[0], stats[2], stats[3]);
+  else if (clean && !smooth) printf("%s: %ld of %ld components kept, %ld vertices and %ld triangles dropped\n", kWho, stats[1], stats[0], stats[2], stats[3]);
   printf("%s: %zu voxels in %d units -> %ld vertices, %ld triangles -> %s\n", kWho, n, n_units, nv, nt, out_file.c_str());
   er_tsdf_destroy(vol);
   return 0;

@@ -646,6 +646,49 @@ inline bool parse_cell(const std::string& text, float* cell) {
   return true;
 }
 
+// The smoothing switches of a command line: <flag> N, <flag>_lambda L, <flag>_mu M, <flag>_fix_boundary.  given: one of them
+// stands on the line.  parse_smooth returns false, with its words on stderr under `who`, for a value that is not a whole number in [0, 1024]
+// or not a finite factor of at most 1 in magnitude, and for a factor or the flag to fix the boundary without <flag> itself.
+struct SmoothOptions {
+  int iterations = 0;
+  float lambda = 0.5f, mu = -0.53f;
+  bool fix_boundary = false, given = false;
+};
+inline bool parse_smooth(int argc, char** argv, const char* who, const std::string& flag, SmoothOptions* o) {
+  const std::string names[3] = {flag, flag + "_lambda", flag + "_mu"};
+  std::string text[3];
+  bool has[3];
+  for (int q = 0; q < 3; q++) {
+    has[q] = find_switch(argc, argv, names[q].c_str());
+    parse_argument(argc, argv, names[q].c_str(), text[q]);
+  }
+  o->fix_boundary = find_switch(argc, argv, (flag + "_fix_boundary").c_str());
+  o->given = has[0] || has[1] || has[2] || o->fix_boundary;
+  if (!o->given) return true;
+  if (!has[0]) {
+    fprintf(stderr, "%s: %s_lambda, %s_mu and %s_fix_boundary need %s <iterations>\n", who, flag.c_str(), flag.c_str(), flag.c_str(), flag.c_str());
+    return false;
+  }
+  char* end = nullptr;
+  const long n = strtol(text[0].c_str(), &end, 10);
+  if (text[0].empty() || end != text[0].c_str() + text[0].size() || n < 0 || n > 1024) {
+    fprintf(stderr, "%s: %s needs a whole number of iterations in [0, 1024]\n", who, flag.c_str());
+    return false;
+  }
+  o->iterations = (int)n;
+  float* factor[2] = {&o->lambda, &o->mu};
+  for (int q = 1; q < 3; q++) {
+    if (!has[q]) continue;
+    const float f = strtof(text[q].c_str(), &end);
+    if (text[q].empty() || end != text[q].c_str() + text[q].size() || !(std::fabs(f) <= 1.0f)) {
+      fprintf(stderr, "%s: %s needs a finite factor of at most 1 in magnitude\n", who, names[q].c_str());
+      return false;
+    }
+    *factor[q - 1] = f;
+  }
+  return true;
+}
+
 // ER_TIMING=1 in the environment: the wall time of each stage of a host program on stderr (bench.py's boundary leg reads them).
 inline void stage_done(const char* what) {
   static const bool on = getenv("ER_TIMING") != nullptr;

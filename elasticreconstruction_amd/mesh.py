@@ -77,3 +77,33 @@ def simplify(verts, tris, cell, normals=None, colors=None, device=0, probes=Fals
     if probes:
         out["probes"] = (pr[0], pr[1])
     return out
+
+
+def smooth(verts, tris, iterations=10, lam=0.5, mu=-0.53, fix_boundary=False, device=0, probes=False):
+    """Taubin lambda|mu smoothing of an indexed mesh on the GPU and the vertex normals of its triangles (er_mesh_smooth; the definitions stand
+    in include/er_hip.h): verts float32[nv, 3] or [nv, 4] (a fourth column is ignored), tris int32[nt, 3].  An iteration is a pass with
+    factor lam and a pass with factor mu; a pass moves every vertex by its factor towards the mean of its distinct neighbours' positions
+    quantised to 2^-20 m (all vertices read the positions the pass started with); a vertex without a neighbour stays, and with fix_boundary
+    so does every end of an edge that only one triangle corner pair gives.  mu = 0 is plain Laplacian smoothing; iterations = 0 gives the
+    normals of the mesh as it is.  A pass that takes a coordinate to 4096 m or beyond is refused, naming the pass and the vertex.
+    Returns a dict: verts float32[nv, 4] (x y z 0), normals float32[nv, 3] (area-weighted, from the triangles at the smoothed positions; NaN
+    for a vertex without one), degree int32[nv], boundary uint8[nv], stats = (distinct edges, boundary edges, non-manifold edges, vertices
+    that never move).  probes = True adds "probes", the longest probe sequence of the edge table (a diagnostic that depends on arrival
+    order; every other entry is the same bytes on every call)."""
+    v = np.asarray(verts, np.float32)
+    if v.ndim != 2 or v.shape[1] not in (3, 4):
+        raise ValueError("smooth: verts must be [n, 3] or [n, 4], not %s" % (v.shape,))
+    nv = v.shape[0]
+    if v.shape[1] == 3:
+        v = np.concatenate([v, np.zeros((nv, 1), np.float32)], axis=1)
+    v = np.ascontiguousarray(v)
+    t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    vo, no = np.zeros((nv, 4), np.float32), np.zeros((nv, 4), np.float32)
+    deg, bnd = np.zeros(nv, np.int32), np.zeros(nv, np.uint8)
+    st, pr = (C.c_long * 4)(0, 0, 0, 0), (C.c_long * 1)(0)
+    _ffi.check(_ffi.lib().er_mesh_smooth(_ffi.ptr(v), nv, _ffi.ptr(t), t.shape[0], int(iterations), C.c_float(lam), C.c_float(mu), int(bool(fix_boundary)),
+                                         int(device), _ffi.ptr(vo), _ffi.ptr(no), _ffi.ptr(deg), _ffi.ptr(bnd), st, pr), "er_mesh_smooth")
+    out = dict(verts=vo, normals=np.ascontiguousarray(no[:, :3]), degree=deg, boundary=bnd, stats=(st[0], st[1], st[2], st[3]))
+    if probes:
+        out["probes"] = pr[0]
+    return out

@@ -362,14 +362,50 @@ class TSDFVolume:
             out += ((st[0], st[1], st[2], st[3], before[0], before[1]),)
         return out
 
-    def SaveMesh(self, filename, normals=True, binary=True, colors=None, min_triangles=0, largest_only=False, cell=0.0):
+    def extract_smoothed_mesh(self, iterations, lam=0.5, mu=-0.53, fix_boundary=False, cell=0.0, min_triangles=0, largest_only=False, colors=False,
+                              stats=False):
+        """The mesh of the resident volume after Taubin smoothing (er_tsdf_extract_mesh_smoothed; no intermediate mesh leaves
+        the device): (verts float32[n, 4], normals float32[n, 3], tris int32[m, 3][, rgba][, stats]).  The mesh that is smoothed is
+        extract_indexed_mesh's or, with min_triangles > 1 or largest_only, extract_clean_mesh's; the result is mesh.smooth(verts, tris,
+        iterations, lam, mu, fix_boundary) of it -- positions x y z 0 and the normals of the smoothed triangles -- and, with cell > 0,
+        mesh.simplify(.., cell, ..) of that.  colors = True samples the UNSMOOTHED vertices (sample_colors), where the surface was observed.
+        iterations = 0 skips the smoothing: the arrays are those of extract_indexed_mesh, extract_clean_mesh or extract_simplified_mesh.
+        stats = True appends (distinct edges, boundary edges, non-manifold edges, vertices that never move, then the four of
+        extract_simplified_mesh, vertices before, triangles before)."""
+        nv, nt = C.c_long(0), C.c_long(0)
+        ss, cs, before = (C.c_long * 4)(0, 0, 0, 0), (C.c_long * 4)(0, 0, 0, 0), (C.c_long * 2)(0, 0)
+        call = self._lib.er_tsdf_extract_mesh_smoothed
+        head = (self._h, int(iterations), C.c_float(lam), C.c_float(mu), int(bool(fix_boundary)), C.c_float(cell), int(min_triangles), int(bool(largest_only)),
+                int(bool(colors)))
+        first = (ss, cs, before) if cell != 0 else (None, None, None)       # (without the clustering the counts need no smoothing)
+        _ffi.check(call(*head, None, None, None, 0, None, 0, C.byref(nv), C.byref(nt), *first), "er_tsdf_extract_mesh_smoothed")
+        verts = np.zeros((nv.value, 4), dtype=np.float32)
+        nrm = np.zeros((nv.value, 4), dtype=np.float32)
+        rgba = np.zeros((nv.value, 4), dtype=np.uint8)
+        tris = np.zeros((nt.value, 3), dtype=np.int32)
+        if nv.value:
+            _ffi.check(call(*head, _ffi.ptr(verts), _ffi.ptr(nrm), _ffi.ptr(rgba) if colors else None, nv.value, _ffi.ptr(tris), nt.value,
+                            C.byref(nv), C.byref(nt), ss, cs, before), "er_tsdf_extract_mesh_smoothed")
+        out = (verts, np.ascontiguousarray(nrm[:, :3]), tris)
+        if colors:
+            out += (rgba,)
+        if stats:
+            out += ((ss[0], ss[1], ss[2], ss[3], cs[0], cs[1], cs[2], cs[3], before[0], before[1]),)
+        return out
+
+    def SaveMesh(self, filename, normals=True, binary=True, colors=None, min_triangles=0, largest_only=False, cell=0.0, smooth=0, smooth_lambda=0.5,
+                 smooth_mu=-0.53, smooth_fix_boundary=False):
         """The indexed mesh of the resident volume as PLY (formats.save_ply; NaN normals become 0 0 0).  colors = None: per-vertex colours iff
         colour is enabled on the volume; False suppresses them; True demands them.  min_triangles > 1 or largest_only: the cleaned mesh of
         extract_clean_mesh.  cell > 0: that mesh simplified by vertex clustering with cells of `cell` metres (extract_simplified_mesh); 0 writes
-        the unsimplified mesh.  Returns (vertices, triangles)."""
+        the unsimplified mesh.  smooth > 0: that many Taubin iterations (extract_smoothed_mesh) after the cleaning and before the clustering.
+        Returns (vertices, triangles)."""
         if colors is None:
             colors = self.color_enabled_
-        if cell != 0:
+        if smooth != 0:
+            got = self.extract_smoothed_mesh(smooth, smooth_lambda, smooth_mu, smooth_fix_boundary, cell, min_triangles, largest_only, colors=bool(colors))
+            verts, nrm, tris, rgba = got[0], got[1], got[2], (got[3] if colors else None)
+        elif cell != 0:
             got = self.extract_simplified_mesh(cell, min_triangles, largest_only, colors=bool(colors))
             verts, nrm, tris, rgba = got[0], got[1], got[2], (got[3] if colors else None)
         elif min_triangles > 1 or largest_only:

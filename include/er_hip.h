@@ -282,6 +282,62 @@ int er_tsdf_extract_mesh_simplified(er_tsdf_t h, float cell, long min_triangles,
                                     float* normals_host, uint8_t* colors_host, int* members_host, long capacity_vertices, int* tri_host,
                                     long capacity_triangles, long* n_vertices, long* n_triangles, long stats[4], long before[2], long probes[2]);
 
+/* Mesh smoothing (Taubin lambda|mu) and vertex normals from the triangles.  Definitions, for nv vertices as float4 rows
+ * (x y z .; the 4th column is ignored), nt triangles int32[nt][3], iterations, lambda and mu (float32) and a flag fix_boundary.  All
+ * arithmetic is float64 or int64, never fused, every operation rounded on its own:
+ *   - edges: triangle t and corner c give the unordered pair {tri[t][c], tri[t][(c + 1) % 3]}; a pair whose two entries are equal is skipped.
+ *     The multiplicity of an edge is the number of (t, c) that give it.  N(v) is the SET of w with {v, w} an edge and deg(v) = |N(v)|: a
+ *     duplicated triangle, or two triangles on one edge, give that neighbour once.  A boundary edge has multiplicity 1, a boundary vertex is
+ *     an end of one, a non-manifold edge has multiplicity >= 3;
+ *   - a pass with factor f: a vertex with deg == 0 keeps its position bits and, with fix_boundary, so does every boundary vertex.  Every other
+ *     vertex moves, per axis: S_a the int64 sum over w in N(v) of llrint((double)p_w,a * 2^20) (half to even), m_a = ((double)S_a /
+ *     (double)deg) * 2^-20, x'_a = (float)((double)p_a + (double)f * (m_a - (double)p_a)).  All vertices read the positions the pass started
+ *     with.  A pass whose factor is exactly 0 is not run;
+ *   - an iteration is a pass with lambda, then a pass with mu; pass 2 i is iteration i's first, pass 2 i + 1 its second, run or not.  mu = 0 is
+ *     plain Laplacian smoothing;
+ *   - the output position has 0.0f in its 4th column; with iterations == 0 it is the input's bits, 4th column 0;
+ *   - range guard: after every pass every coordinate has to be finite and below 4096 m in magnitude (a negative mu extrapolates); otherwise the
+ *     call is refused with nothing written, naming the smallest such pass and in it the smallest vertex;
+ *   - normals, from the OUTPUT positions: per triangle (a, b, c), d1 = (double)p_b - (double)p_a, d2 = (double)p_c - (double)p_a per
+ *     component, cross_x = d1_y d2_z - d1_z d2_y and cyclic (each product rounded before the subtraction), k_a = llrint(cross_a * 2^32).  k is
+ *     added once per corner to that corner's vertex sum N_a; the sums are uint64 in two's complement, so wrapping is the definition.  Then
+ *     g = (double)(int64)N, len = sqrt((g_x g_x + g_y g_y) + g_z g_z), the normal (float)(g_a / len); NaN NaN NaN iff len == 0, which covers
+ *     a vertex no triangle names; the 4th column is 0;
+ *   - side outputs: degree[v] int32; boundary[v] uint8 (1 or 0, whether or not fix_boundary is set); stats: distinct edges, boundary edges,
+ *     non-manifold edges, vertices that no pass moves (deg == 0, and with fix_boundary the boundary vertices).
+ * Every result is defined without reference to any order of execution: the same bytes on every call.  probes (nullable) is a diagnostic
+ * outside that promise: the longest probe sequence of the call in the edge table.
+ *
+ * Refused, each before any kernel uses an index as an address, with nothing written, the message naming the FIRST offender in input order
+ * (vertices before triangles): a NULL required argument (the vertices and the triangles where there are any) or negative sizes; n_vertices
+ * > 2^31 - 1 or 3 n_triangles > 2^31 - 1 (int32 edge instances); no device; iterations outside [0, 1024]; lambda or mu not finite or above
+ * 1 in magnitude; a coordinate that is not finite or is >= 4096 m in magnitude ("vertex <v> ..."); a triangle index outside [0, n_vertices)
+ * ("triangle <t> names vertex <i>, outside [0, <nv>)").  n_vertices == 0 succeeds with no array written (stats 0); n_triangles == 0
+ * succeeds: the positions pass through, normals NaN, degrees 0.
+ *
+ * er_mesh_smooth smooths any indexed mesh held in host memory on `device`.  Every output pointer is nullable (verts_out, normals_out: 4 floats
+ * per vertex; degree_out: int32, boundary_out: uint8 [n_vertices]).  iterations == 0 with normals_out is the library's "vertex normals from
+ * triangles" call. */
+int er_mesh_smooth(const float* verts_host, long n_vertices, const int* tri_host, long n_triangles, int iterations, float lambda, float mu,
+                   int fix_boundary, int device, float* verts_out, float* normals_out, int* degree_out, uint8_t* boundary_out, long stats[4],
+                   long probes[1]);
+
+/* The smoothed mesh of the resident volume, without an intermediate mesh leaving device memory.  Stages: er_tsdf_extract_mesh_indexed's mesh;
+ * er_tsdf_extract_mesh_cleaned's filter if min_triangles > 1 || largest_only; the smoothing above; er_mesh_simplify's clustering if cell > 0
+ * (cell == 0 is legal here and skips it; a negative or non-finite cell is refused).  want_colors: the vertices are coloured at their
+ * UNSMOOTHED positions -- the voxels the surface was observed in -- by er_tsdf_sample_colors' rule and the colours travel unchanged by vertex
+ * index (the clustering then averages them); refused before er_tsdf_color_enable, and colors_host without it is refused.  The normals are
+ * the triangle normals of the smoothed mesh (the clustering then combines them by its own rule).  With iterations == 0 the smoothing stage is
+ * skipped entirely and the arrays are the existing routes' bit for bit (the 4th column of a vertex and the TSDF-gradient normals included).
+ * Refusals are those of the stages that run.  Counts first: *n_vertices and *n_triangles are set, then a capacity that is too small is
+ * refused with nothing written.  smooth_stats, simplify_stats (as the two calls above; zero for a stage that did not run) and before
+ * (vertices and triangles of the mesh that was smoothed) are nullable.  An empty volume gives 0 and 0.  Without the clustering the counts
+ * are those of the mesh that is smoothed: a call with every output and smooth_stats NULL returns them without smoothing. */
+int er_tsdf_extract_mesh_smoothed(er_tsdf_t h, int iterations, float lambda, float mu, int fix_boundary, float cell, long min_triangles,
+                                  int largest_only, int want_colors, float* verts_host, float* normals_host, uint8_t* colors_host,
+                                  long capacity_vertices, int* tri_host, long capacity_triangles, long* n_vertices, long* n_triangles,
+                                  long smooth_stats[4], long simplify_stats[4], long before[2]);
+
 /* TSDFVolume::SaveWorld's inverse: a world.pcd voxel list back into a volume.  xyzi_host: n rows x y z intensity in er_tsdf_extract_world's
  * layout -- x, y, z integer voxel indices as floats, i + (xi - 256) * 64; intensity = the sdf.  Afterwards every listed voxel is (intensity, 1)
  * and every other voxel of a created unit (+0, 0); the created units are those with at least one listed voxel, *n_units (nullable) their number.
